@@ -14,8 +14,8 @@ resident in HBM before the timed region.  ``--workload c2`` runs BASELINE config
 ``--workload c2-weak`` is round 1's weak-scaled C2-per-GPU run.
 
 The default algorithm is what a one-shot recovery runs: AUTO — the fold straight from the CSR log, no copy of it (the
-10 M-aggregate Zipf log: SORTED; C2: ROWS); ``one_shot`` carries its index build and first (cold) fold.  At N = 1 the line
-also carries ``tile_major`` — the same log through the tile-major copy (SURGE_ALGO_TILED: group-major 8 KiB subtiles
+10 M-aggregate Zipf log: SORTED; C2: ROWS); ``one_shot`` carries its index build and first (cold) fold.  With ``--full``, at N = 1
+the line also carries ``tile_major`` — the same log through the tile-major copy (SURGE_ALGO_TILED: group-major 8 KiB subtiles
 streamed linearly), with what that copy costs once — ``secondary`` (config C2, both transports), ``c5`` (config 5, bounded),
 ``v2`` (the ABI v2 slot path), ``c4_shard`` (what ONE GPU of config C4 folds: rank 0's 1.25 M aggregates of the 8-GPU split,
 AUTO, 100 folds, every aggregate checked) and ``e2e`` (events-topic BYTES -> states over 3e7 records of the same population on
@@ -29,9 +29,11 @@ Rank 0 prints ONE JSON line.  ``roofline`` prices the dominant fold kernel again
 algorithmic bytes 16*E + 8*(A+1) + 64*A and the kernel's HIP-event times measured inside the timed region on
 the launch stream (mean for ``achieved``; min / median / max reported).  ``traffic`` comes from the rocprofv3 PMC passes
 committed under profiles/ for exactly this kernel and shape (profiles/traffic_manifest.json; null when there is none or
-the kernel sources changed since).  At N = 1 ``secondary`` carries config C2 with its own roofline, and ``cpu_baseline``
-times the CPU restatement (oracle/, "port") on a bounded sample of the same log on this box's host cores; the GPU result
-for that sample is checked bit-for-bit against it.
+the kernel sources changed since).  With ``--full``, at N = 1 ``roofline`` adds a stream-read probe, ``secondary`` carries
+config C2 with its own roofline, and ``cpu_baseline`` times the CPU restatement (oracle/, "port") on a bounded sample of the
+same log on this box's host cores; the GPU result for that sample (and, by default, for the whole log) is checked
+bit-for-bit against it.  A plain run sets up, warms up, times the K steps and prints the line; ``--dump-outputs DIR``
+writes the states of the last timed step (a fixed sample of them) before it does.
 """
 import argparse
 import hashlib
@@ -171,6 +173,33 @@ def time_folds(eng, torch, dev, algo, steps, warmup):
     return dt, eng.stats(), eng.fold_times_ms()
 
 
+DUMP_SAMPLE, DUMP_SEED = 1 << 19, 7  # --dump-outputs: at most 2^19 aggregates x 8 float64 fields (+ ids) = 36 MB
+
+
+def dump_states(out_dir, states, agg_ids):
+    """``--dump-outputs``: the states a fold left in ``states`` ((n, 64) uint8 rows, one per aggregate, as a caller of the fold
+    receives them), for every aggregate or, when there are more than DUMP_SAMPLE, for a fixed sample drawn with DUMP_SEED —
+    one float64 array per field of the state record, ``out_dir/state_<field>.npy``, and the aggregates' global ids (``agg_ids``)
+    in ``out_dir/aggregate_id.npy``, all in the same (ascending row) order."""
+    import numpy as np
+    import torch
+
+    from surge_amd import schema as S
+
+    n = int(states.shape[0])
+    if n > DUMP_SAMPLE:
+        pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    else:
+        pick = np.arange(n)
+    idx = torch.from_numpy(pick).to(states.device)
+    rows = states.index_select(0, idx).cpu().numpy().view(S.STATE_DTYPE).reshape(-1)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "aggregate_id.npy"), agg_ids.index_select(0, idx.to(agg_ids.device)).cpu().numpy().astype(np.float64))
+    for name in S.STATE_DTYPE.names:
+        if name != "reserved":
+            np.save(os.path.join(out_dir, f"state_{name}.npy"), rows[name].astype(np.float64))
+
+
 def roofline_of(S, st, times_ms, probe_gbps=None):
     import numpy as np
 
@@ -200,8 +229,16 @@ def roofline_of(S, st, times_ms, probe_gbps=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; --workload c4-shard 100, c5 600, e2e every fetch of the topic)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="the default workload at N = 1: also measure what sits beside the headline — the stream-read probe, cpu_baseline (+ full-log "
+                         "parity), the other transport (tile_major / csr_direct), secondary (C2), c5, v2, c4_shard and e2e (minutes); without it the "
+                         "run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="fold workloads: after the timed steps write the states the last step computed as float64 arrays, one per field of the "
+                         "state record, DIR/state_<field>.npy, with DIR/aggregate_id.npy — a fixed, seeded sample of %d aggregates when there "
+                         "are more (rank 0's shard at N > 1)" % (1 << 19))
     ap.add_argument("--workload", default="c4", choices=["c4", "c3", "c2", "c2-weak", "c5", "v2", "e2e", "c4-shard"],
                     help="c4 / c3 (default): the 10 M-aggregate Zipf log, strong-scaled over the GPUs; c2: 1 M x 256 fixed fan-in "
                          "(strong-scaled); c2-weak: 1 M x 256 PER GPU (round 1's run); c5: streaming micro-batches onto a resident "
@@ -250,16 +287,18 @@ def main():
     ap.add_argument("--events-per-aggregate", type=int, default=C2_EVENTS, help="c2 only")
     ap.add_argument("--algo", default=None,
                     help="auto | fixed | flat | rows | sorted | chunked | tiled (or the SURGE_ALGO_* number); default: auto — the "
-                         "kernel the engine picks for a log it folds straight from CSR (the tile-major fold is reported beside it at N = 1)")
+                         "kernel the engine picks for a log it folds straight from CSR (with --full the tile-major fold is reported beside it at N = 1)")
     ap.add_argument("--parity", default="full", choices=["full", "sample", "none"],
-                    help="N = 1: check the GPU states against the CPU restatement on the whole log (default), on the cpu_baseline "
+                    help="N = 1 with --full: check the GPU states against the CPU restatement on the whole log (default), on the cpu_baseline "
                          "sample only, or not at all")
     ap.add_argument("--gather", default="native", choices=["native", "torch", "none"],
                     help="N > 1 snapshot exchange: native = RCCL behind the C ABI (default), torch = torch.distributed, none = fold only")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU-time budget of the cpu_baseline leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the config-C2 secondary line at N = 1")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the config-C2 secondary line and the legs after it at N = 1")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.workload in ("c5", "v2", "e2e", "c4-shard"):
+        raise SystemExit("--dump-outputs: the fold workloads (c4, c3, c2, c2-weak) only")
     if args.workload == "c5":
         print(json.dumps(run_c5(args)))
         return
@@ -274,7 +313,7 @@ def main():
         from surge_amd.replay import ReplayEngine
 
         world, rank, local_rank, dev, ctl, dist, rehearsal = init_ranks(args, torch)
-        print(json.dumps(run_c4_shard(args, S, synth, ReplayEngine, torch, dev, local_rank, steps=args.steps if args.steps != 20 else 100,
+        print(json.dumps(run_c4_shard(args, S, synth, ReplayEngine, torch, dev, local_rank, steps=args.steps if args.steps is not None else 100,
                                       algo=parse_algo(args.algo), check=not args.no_cpu_baseline)))
         return
     if args.workload == "e2e":
@@ -291,6 +330,8 @@ def main():
     from surge_amd.replay import ReplayEngine
 
     world, rank, local_rank, dev, ctl, dist, rehearsal = init_ranks(args, torch)
+    if args.steps is None:
+        args.steps = 20
 
     zipf = args.workload in ("c4", "c3")
     weak = args.workload == "c2-weak"
@@ -438,12 +479,15 @@ def main():
 
     result = None
     if rank == 0:
+        if args.dump_outputs is not None:
+            dump_states(args.dump_outputs, bufs[last][:n_local], agg_ids)
         probe_gbps = None
-        try:
-            ms = min(eng.stream_probe_ms(events[: min(events.shape[0], 1 << 29)]) for _ in range(5))  # an 8 GB window, best of five
-            probe_gbps = min(events.shape[0], 1 << 29) * 16 / (ms * 1e-3) / 1e9
-        except Exception as e:  # pragma: no cover
-            print(f"stream probe failed: {e}", file=sys.stderr)
+        if args.full:
+            try:
+                ms = min(eng.stream_probe_ms(events[: min(events.shape[0], 1 << 29)]) for _ in range(5))  # an 8 GB window, best of five
+                probe_gbps = min(events.shape[0], 1 << 29) * 16 / (ms * 1e-3) / 1e9
+            except Exception as e:  # pragma: no cover
+                print(f"stream probe failed: {e}", file=sys.stderr)
         ms_per_step = elapsed_s / args.steps * 1e3
         roof = roofline_of(S, st, times_ms, probe_gbps)
         # what ONE recovery pays: the bound log's index + its first (cold) fold — a recovery folds once, the warm-replay rate
@@ -454,7 +498,7 @@ def main():
             roof["one_shot_ms"] = {"index_build": layout.index_build_ms, "first_fold_kernel": first_fold_kernel_ms, "prepare_wall": prepare_wall_ms,
                                    "first_fold_wall": first_fold_wall_ms}
         cpu_baseline = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu_baseline = run_cpu_baseline(args, seg_off, events, bufs[last])
         one_shot = {
             "index_algo": algo_name(S, layout.algo) if layout.algo else None,
@@ -473,7 +517,7 @@ def main():
         # the other transport, measured in the same run on the same log (N = 1): the tile-major fold when the primary folds
         # straight from the CSR log (the default), the CSR fold when --algo tiled was asked for
         csr_direct, tile_major = None, None
-        if world == 1 and st.last_algo == S.ALGO_TILED:
+        if args.full and world == 1 and st.last_algo == S.ALGO_TILED:
             eng.set_state_out(bufs[1 - last])
             t_p = time.perf_counter()
             eng.fold(S.ALGO_AUTO)
@@ -488,7 +532,7 @@ def main():
                           "events_per_sec": total_events / (float(np.mean(tm2)) * 1e-3),
                           "states_equal_primary": bool(torch.equal(bufs[0], bufs[1]))}
             eng.set_state_out(bufs[last])
-        elif world == 1 and zipf and not args.no_secondary:
+        elif args.full and world == 1 and zipf and not args.no_secondary:
             try:
                 eng.set_state_out(bufs[1 - last])
                 torch.cuda.synchronize(dev)
@@ -558,7 +602,7 @@ def main():
         }
     eng.close()
     del events, seg_off
-    if rank == 0 and world == 1 and zipf and not args.no_secondary:
+    if rank == 0 and world == 1 and zipf and args.full and not args.no_secondary:
         torch.cuda.empty_cache()
         result["secondary"] = run_secondary_c2(args, S, synth, ReplayEngine, torch, dev, local_rank)
         # BASELINE config 5 and the ABI v2 path, bounded to a few seconds each, so that the driver's run times them too
@@ -753,7 +797,7 @@ def run_c5(args):
     dev = torch.device("cuda:0")
     A = args.aggregates or N_AGGREGATES
     B, every = args.batch_events, args.snapshot_every
-    K = args.steps if args.steps != 20 else 600  # the generic default (20) means "not given": C5 is 600 batches = 60 s of stream
+    K = args.steps if args.steps is not None else 600  # C5 is 600 batches = 60 s of stream unless --steps says otherwise
     W = max(args.warmup, 3)
     so, ev = synth.fixed_log_device(A, 16, 5, dev, mix=synth.C1_MIX)  # initial recovery: a short uniform log
     eng = ReplayEngine()
@@ -922,7 +966,7 @@ def run_v2(args):
     val = (torch.rand(E, device=dev, generator=g, dtype=torch.float64) * 1e6).view(torch.int64)
     ev = torch.stack((ty | (torch.arange(E, device=dev) % 1000 + 1) << 32, val), dim=1)
     del ty, val
-    K, W = args.steps, args.warmup
+    K, W = args.steps if args.steps is not None else 20, args.warmup
     variants, first_states, info_spec, one_shot = {}, None, None, None
     for build in ("specialised", "interpreter"):
         os.environ["SURGE_REPLAY_RTC"] = "1" if build == "specialised" else "0"
@@ -1227,7 +1271,7 @@ def run_e2e(args):
     order = np.argsort(synth._h(E2E_SEED, my_ids, 23), kind="stable")  # the order aggregates take turns in, every round
     my_ids, my_part, counts = my_ids[order], my_part[order], counts[order]
     n_total = int(counts.sum())
-    if args.steps != 20:  # an explicit --steps: that many timed fetches
+    if args.steps is not None:  # an explicit --steps: that many timed fetches
         n_total = min(n_total, (W + args.steps) * n_fetch)
     # ---- the topic, fetch by fetch: (agg, j) stream -> record text -> record batches per partition ----------------------
     fetches, n_pub = [], 0

@@ -85,8 +85,8 @@ def run_single(args):
 def test_default_bench_line_carries_the_tile_major_fold_c2_c5_and_v2_beside_the_headline():
     """The default invocation at a small size: the headline is the fold AUTO picks from the CSR log, `tile_major` the fold over
     the re-laid copy with its one-off cost, `secondary` config C2 (AUTO + tile-major), `c5` / `v2` the streaming config and
-    the ABI v2 path — all timed by whoever runs bench.py, not only by a builder's own invocations."""
-    d = run_single(["--aggregates", "200000", "--steps", "5", "--warmup", "2", "--cpu-seconds", "2"])
+    the ABI v2 path — all timed by whoever runs bench.py --full, not only by a builder's own invocations."""
+    d = run_single(["--full", "--aggregates", "200000", "--steps", "5", "--warmup", "2", "--cpu-seconds", "2"])
     assert d["config"]["algo"] in ("chunked", "sorted", "flat") and d["csr_direct"] is None
     tm = d["tile_major"]
     assert tm["algo"] == "tiled" and tm["states_equal_primary"] is True and tm["one_shot"]["relayout_ms"] > 0 and tm["frac"] > 0
@@ -95,6 +95,40 @@ def test_default_bench_line_carries_the_tile_major_fold_c2_c5_and_v2_beside_the_
     assert d["c5"]["cpu_baseline"]["gpu_matches_cpu_full_run"] is True and d["c5"]["value"] > 0
     assert d["v2"]["cpu_baseline"]["gpu_matches_cpu_full_log"] is True and d["v2"]["roofline"]["kernel"] == "surge_slots_tiled2"
     assert d["roofline"]["stream_read_probe_GBps"] > 1000 and d["cpu_baseline"]["gpu_matches_cpu_full_log"] is True
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_alone_and_dumps_the_states_of_its_last_step(tmp_path):
+    """Without --full the default invocation times the headline fold and nothing beside it; --dump-outputs writes the states
+    the last timed step left, field by field as float64 — here every aggregate of a small log, equal to the oracle's fold."""
+    import numpy as np
+    import torch
+
+    from oracle import oracle
+    from surge_amd import schema as S
+    from surge_amd import synth
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    out = tmp_path / "out"
+    d = run_single(["--gpus", "1", "--aggregates", "100000", "--steps", "7", "--warmup", "2", "--dump-outputs", str(out)])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["roofline"]["timed_launches"] == 7 and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["config"]["events"] * 7 / (d["ms_per_step"] * 7 * 1e-3)) < 1e-6 * d["value"]
+    assert d["metric"] == "events/sec replayed" and d["unit"] == "events/s" and d["higher_is_better"] is True and d["dtype"]
+    assert d["cpu_baseline"] is None and d["tile_major"] is None and d["csr_direct"] is None and "stream_read_probe_GBps" not in d["roofline"]
+    assert not {"secondary", "c5", "v2", "c4_shard", "e2e"} & set(d)
+    fields = [n for n in S.STATE_DTYPE.names if n != "reserved"]
+    assert sorted(p.name for p in out.iterdir()) == sorted(["aggregate_id.npy"] + [f"state_{n}.npy" for n in fields])
+    got = {n: np.load(out / f"state_{n}.npy") for n in fields}
+    assert all(a.dtype == np.float64 and a.shape == (100000,) for a in got.values())
+    np.testing.assert_array_equal(np.load(out / "aggregate_id.npy"), np.arange(100000, dtype=np.float64))
+    dev = torch.device("cuda:0")
+    ids = torch.arange(100000, dtype=torch.int64, device=dev)
+    so, ev = synth.csr_log_device(synth.zipf_lengths(ids, bench.ZIPF_SEED), bench.ZIPF_SEED, agg_ids=ids, global_seg_off=bench._LazyGlobalOffsets())
+    exp = oracle.fold_csr(so.cpu().numpy(), synth.to_event_records(ev))
+    for n in fields:
+        np.testing.assert_array_equal(got[n], exp[n].astype(np.float64), err_msg=n)
 
 
 @pytest.mark.gpu
