@@ -74,8 +74,11 @@ int32_t surge_snapshot_writer_reset(surge_snapshot_writer* w);
  * aggregates, orders them by partition (stable: aggregate index order inside a partition, like the writer above), cuts
  * the batches by the same rule (a batch closes with the record that brings it to max_records or max_bytes) and writes
  * every record and header where it goes; one copy brings the bytes to page-locked host memory, where the batches get
- * their CRCs.  BYTE-IDENTICAL to surge_snapshot_writer_append + _flush on the same input (uncompressed batches;
- * tests/test_frame_gpu.py).  What it is for: the state-topic side of KafkaProducerActorImpl's publish
+ * their CRCs.  Uncompressed batches (the default) are BYTE-IDENTICAL to surge_snapshot_writer_append + _flush on the same
+ * input (tests/test_frame_gpu.py).  LZ4 batches (surge_device_framer_set_compression) have the same cuts, offsets and
+ * header fields, attributes = 3, and their records section is ONE LZ4 frame as kafka-clients writes it, compressed on the
+ * device in independent blocks of 64 KiB of input, a block that does not shrink stored: not the host compressor's bytes,
+ * but the same records to any LZ4 decoder, about as small (tests/test_frame_lz4_gpu.py).  What it is for: the state-topic side of KafkaProducerActorImpl's publish
  * (modules/command-engine/core/src/main/scala/surge/internal/kafka/KafkaProducerActorImpl.scala:421-453) when a whole
  * commit interval's worth of changed aggregates is published at once (config C5). */
 typedef struct surge_device_framer surge_device_framer;
@@ -86,17 +89,23 @@ int32_t surge_device_framer_create(int32_t device_id, void* hip_stream, int32_t 
                                    int64_t max_batch_bytes, surge_device_framer** out);
 int32_t surge_device_framer_destroy(surge_device_framer* f);
 const char* surge_device_framer_last_error(const surge_device_framer* f);
+/* Codec of the batches framed from now on: SURGE_SNAPSHOT_CODEC_NONE (default) or SURGE_SNAPSHOT_CODEC_LZ4.
+ * Anything else: SURGE_E_INVALID, codec unchanged.  May be called between any two surge_device_framer_frame calls. */
+int32_t surge_device_framer_set_compression(surge_device_framer* f, int32_t codec);
 /* One publish.  Device inputs, all indexed by aggregate: d_kind[n] (SURGE_SNAP_SKIP / VALUE / TOMBSTONE), d_partition[n],
  * d_key_off[n + 1] into d_keys_utf8, d_val_off[n + 1] into d_values (read for VALUE aggregates only; the filtered
  * encoder's output as it is).  Outputs: *bytes_out = the record batches of all partitions, partition after partition, in
  * host memory owned by the framer (valid until its next call); (*part_byte_off_out)[p .. p+1] = partition p's span in
- * it (n_partitions + 1 entries).  Each partition's log continues where the framer's previous call left it
+ * it (n_partitions + 1 entries; in LZ4 mode both describe the compressed batches).  Each partition's log continues where the framer's previous call left it
  * (surge_device_framer_next_offsets).  Synchronous.  On an error nothing is advanced. */
 int32_t surge_device_framer_frame(surge_device_framer* f, int64_t n_aggregates, const uint8_t* d_kind, const int32_t* d_partition,
                                   const uint8_t* d_keys_utf8, const int64_t* d_key_off, const uint8_t* d_values, const int64_t* d_val_off,
                                   int64_t timestamp_ms, const uint8_t** bytes_out, const int64_t** part_byte_off_out, int64_t* n_records_out,
                                   int64_t* n_batches_out);
 int32_t surge_device_framer_next_offsets(const surge_device_framer* f, int64_t* out /* n_partitions */);
+/* Bytes the record batches of the last successful surge_device_framer_frame call have UNCOMPRESSED (headers included):
+ * the length of its output in the default mode, what the LZ4 mode's output is to be compared with.  -1 for NULL. */
+int64_t surge_device_framer_uncompressed_bytes(const surge_device_framer* f);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,14 @@
 #!/usr/bin/env python3
 """N2 x N3 timing: a full and an incremental state-topic snapshot of a large resident state, GPU delta + encode, D2H,
-RecordBatch v2 encoding (scripts/snapshot_bench.py [aggregates]); prints one JSON line (profiles/r02_snapshot_n2.json)."""
+RecordBatch v2 encoding (scripts/snapshot_bench.py [aggregates] [none|lz4] [host|device|compare]); prints one JSON line
+(profiles/r02_snapshot_n2.json; lz4 runs: profiles/snapshot_lz4_compare.json, profiles/snapshot_lz4_device.json).
+
+The third argument says who compresses lz4 batches: "host" (default: the host writer's compressor), "device" (the device
+framer's LZ4 mode) or "compare": both routes in this one process, on the same engine state, host / device alternating
+after a warm-up publish of each — a full snapshot of all aggregates, then the delta after events to 3/4 of them (about
+10^6 changed aggregates at the default 2 M: a C5-shaped publish) — every publish uncommitted, so that every repeat
+publishes the same records; SNAPSHOT_BENCH_PAIRS (environment, default 5) is the number of timed pairs.  Every lz4 result
+carries record_batch_bytes (compressed) and uncompressed_bytes."""
 import json
 import os
 import sys
@@ -16,32 +24,99 @@ from surge_amd.snapshot import BulkSnapshotPublisher
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 2_000_000
 compression = sys.argv[2] if len(sys.argv) > 2 else "none"  # "lz4": compress the record batches like the reference producer
+compressor = sys.argv[3] if len(sys.argv) > 3 else "host"   # lz4 only: "host", "device" or "compare"
+if compressor not in ("host", "device", "compare") or (compressor != "host" and compression != "lz4"):
+    sys.exit("usage: [SNAPSHOT_BENCH_PAIRS=5] snapshot_bench.py [aggregates] [none|lz4] [host|device|compare]   (device / compare need lz4)")
+PAIRS = int(os.environ.get("SNAPSHOT_BENCH_PAIRS", "5"))
 dev = torch.device("cuda:0")
 lens = synth.zipf_lengths(torch.arange(n, dtype=torch.int64, device=dev), 3, max_len=64)
 so, ev = synth.csr_log_device(lens, 3, mix=synth.C1_MIX)
 keys = [f"acct-{i:08d}" for i in range(n)]
+
+
+def touch(eng, m):
+    idx = torch.randperm(n, device=dev)[:m].to(torch.int64)
+    be = synth.to_event_records(synth.event_words(torch.arange(m, device=dev), idx, torch.arange(m, device=dev), 9, synth.C1_MIX))
+    eng.append_events(idx.cpu().numpy(), be)
+
+
+def sizes(pub, out):
+    s = {"record_batch_bytes": sum(len(b) for b in out.values())}
+    if pub.framer is not None:
+        s["uncompressed_bytes"] = pub.framer.uncompressed_bytes
+    return s
+
+
+def compare(eng, pubs):
+    """{route: [seconds of publish(commit=False) ending in its synchronise]} for PAIRS alternating pairs, after one warm-up
+    publish of each route."""
+    runs = {route: [] for route in pubs}
+    info = {}
+    for rep in range(PAIRS + 1):
+        for route, pub in pubs.items():
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            out = pub.publish(commit=False)
+            torch.cuda.synchronize(dev)
+            dt = time.perf_counter() - t0
+            if rep:
+                runs[route].append(dt)
+            info[route] = {**sizes(pub, out), **pub.timings}
+            del out
+    res = {}
+    for route, ts in runs.items():
+        res[route] = {"seconds": ts, "median_s": float(np.median(ts)), "spread_s": max(ts) - min(ts), **info[route]}
+    # both routes publish the same records in the same batches, so what they have uncompressed is one number
+    res["host"]["uncompressed_bytes"] = res["device"]["uncompressed_bytes"]
+    res["device_faster_in_every_pair"] = all(d < h for h, d in zip(runs["host"], runs["device"]))
+    spread = max(res["host"]["spread_s"], res["device"]["spread_s"])  # between repeats of the same route
+    res["device_faster_by_more_than_the_spread_in_every_pair"] = all(h - d > spread for h, d in zip(runs["host"], runs["device"]))
+    res["host_over_device_median"] = res["host"]["median_s"] / res["device"]["median_s"]
+    return res
+
+
 with ReplayEngine() as eng:
     eng.load_csr(so, ev)
     eng.fold()
+    if compressor == "compare":
+        pubs = {"host": BulkSnapshotPublisher(eng, keys, 64, compression="lz4"),
+                "device": BulkSnapshotPublisher(eng, keys, 64, compression="lz4", device_compression=True)}
+        full = compare(eng, pubs)
+        pubs["host"].publish()  # commit the baseline, then send events to 3/4 of the aggregates: about 2/3 of those change state
+        touch(eng, 3 * n // 4)
+        delta = compare(eng, pubs)
+        # the device route without the compressor, for what the compression costs or saves on the device
+        plain = BulkSnapshotPublisher(eng, keys, 64)
+        ts = []
+        for rep in range(PAIRS + 1):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            out = plain.publish(commit=False)
+            torch.cuda.synchronize(dev)
+            ts.append(time.perf_counter() - t0)
+            nbytes = sum(len(b) for b in out.values())
+            del out
+        delta["device_uncompressed"] = {"seconds": ts[1:], "median_s": float(np.median(ts[1:])), "record_batch_bytes": nbytes}
+        print(json.dumps({"aggregates": n, "partitions": 64, "compression": "lz4", "pairs": PAIRS, "full_snapshot": full, "delta": delta}))
+        for pub in list(pubs.values()) + [plain]:
+            pub.close()
+        sys.exit(0)
     t0 = time.perf_counter()
-    pub = BulkSnapshotPublisher(eng, keys, 64, compression=compression)
+    pub = BulkSnapshotPublisher(eng, keys, 64, compression=compression, device_compression=compressor == "device")
     setup_s = time.perf_counter() - t0
     t0 = time.perf_counter()
     full = pub.publish()
     full_s = time.perf_counter() - t0
-    full_t = dict(pub.timings)
+    full_t = {**sizes(pub, full), **pub.timings}
     # touch 1 % of the aggregates, publish the delta
-    m = n // 100
-    idx = torch.randperm(n, device=dev)[:m].to(torch.int64)
-    be = synth.to_event_records(synth.event_words(torch.arange(m, device=dev), idx, torch.arange(m, device=dev), 9, synth.C1_MIX))
-    eng.append_events(idx.cpu().numpy(), be)
+    touch(eng, n // 100)
     t0 = time.perf_counter()
     delta = pub.publish()
     delta_s = time.perf_counter() - t0
     print(json.dumps({
-        "aggregates": n, "partitions": 64, "key_table_setup_s": setup_s,
-        "full_snapshot": {"seconds": full_s, "record_batch_bytes": sum(len(b) for b in full.values()), **full_t,
-                          "aggregates_per_sec": n / full_s},
-        "incremental_1pct": {"seconds": delta_s, "record_batch_bytes": sum(len(b) for b in delta.values()), **pub.timings},
+        "aggregates": n, "partitions": 64, "compression": compression, "compressor": compressor if compression == "lz4" else None,
+        "key_table_setup_s": setup_s,
+        "full_snapshot": {"seconds": full_s, **full_t, "aggregates_per_sec": n / full_s},
+        "incremental_1pct": {"seconds": delta_s, **sizes(pub, delta), **pub.timings},
     }))
     pub.close()

@@ -169,8 +169,10 @@ SNAPSHOT_EXPORTS = (
     "surge_device_framer_create",
     "surge_device_framer_destroy",
     "surge_device_framer_last_error",
+    "surge_device_framer_set_compression",
     "surge_device_framer_frame",
     "surge_device_framer_next_offsets",
+    "surge_device_framer_uncompressed_bytes",
 )
 
 _lib: Optional[ctypes.CDLL] = None
@@ -402,8 +404,10 @@ def load() -> ctypes.CDLL:
         "surge_device_framer_create": ([i32, vp, i32, i32, i64, ctypes.POINTER(vp)], i32),
         "surge_device_framer_destroy": ([vp], i32),
         "surge_device_framer_last_error": ([vp], ctypes.c_char_p),
+        "surge_device_framer_set_compression": ([vp, i32], i32),
         "surge_device_framer_frame": ([vp, i64, vp, vp, vp, vp, vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "surge_device_framer_next_offsets": ([vp, vp], i32),
+        "surge_device_framer_uncompressed_bytes": ([vp], i64),
     })
     for name in EXPORTS + INGEST_EXPORTS + SNAPSHOT_EXPORTS:
         try:

@@ -21,6 +21,21 @@
 // Steps (all on the framer's stream): select the changed aggregates (rocPRIM select) -> their partition + base size ->
 // stable radix sort by partition -> the three scans -> batches per partition (count, then emit at scanned offsets) ->
 // one thread per record writes its bytes, one per batch its 61-byte header -> one device -> host copy -> host CRCs.
+//
+// LZ4 mode (surge_device_framer_set_compression): what the reference's producer writes (compression.type = lz4).  The
+// batch cuts, offsets and counts are those of the uncompressed framing — they are decided on the uncompressed sizes, as
+// the host writer decides them —; the records section of every batch then becomes ONE LZ4 frame as kafka-clients writes
+// it (magic, FLG 0x60, BD 0x40, HC 0x82, independent blocks of 64 KiB of input, EndMark; no checksums), attributes = 3,
+// and the CRC covers the compressed batch.  After the write kernel has put the records into the uncompressed buffer:
+//     block table (batch, block) -> frame_lz4_block_kernel, ONE WAVE PER BLOCK, into a scratch slot per block ->
+//     scan of the block sizes -> every batch's frame size and final place -> frame_lz4_pack_kernel moves size words and
+//     block bytes (from the scratch slot, or from the uncompressed buffer for a block that did not shrink: stored) ->
+//     header kernel -> device -> host copy of the COMPRESSED bytes -> host CRCs.
+// The output is not the host compressor's byte for byte (a wave looks at 64 positions at once and sees the hash table
+// differently); it decodes to the same records and is about as small (tests/test_frame_lz4_gpu.py).
+// Device memory at the peak of an LZ4 publish of U uncompressed batch bytes: the uncompressed buffer (U), the scratch
+// slots (U: a slot is as long as its block, a block that would not shrink is abandoned before it outgrows it) and the
+// final buffer (at most U + 11 bytes per batch + 4 per block) — about 3 U, beside the tables of the uncompressed mode.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -223,7 +238,7 @@ __global__ void frame_write_kernel(const Batch* __restrict__ batches, int64_t n_
   *p = 0;  // no headers
 }
 
-__global__ void frame_header_kernel(const Batch* __restrict__ batches, int64_t n_batches, int64_t timestamp_ms, uint8_t* __restrict__ out) {
+__global__ void frame_header_kernel(const Batch* __restrict__ batches, int64_t n_batches, int64_t timestamp_ms, int32_t codec, uint8_t* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_batches) return;
   const Batch b = batches[i];
@@ -233,7 +248,7 @@ __global__ void frame_header_kernel(const Batch* __restrict__ batches, int64_t n
   put_be(o + 12, 0, 4);                                           // partitionLeaderEpoch
   o[16] = 2;                                                      // magic
   put_be(o + 17, 0, 4);                                           // crc: the host fills it in
-  put_be(o + 21, 0, 2);                                           // attributes: no codec, CreateTime, not transactional
+  put_be(o + 21, (uint64_t)codec, 2);                             // attributes: the codec, CreateTime, not transactional
   put_be(o + 23, (uint64_t)(b.count - 1), 4);                     // lastOffsetDelta
   put_be(o + 27, (uint64_t)timestamp_ms, 8);                      // baseTimestamp
   put_be(o + 35, (uint64_t)timestamp_ms, 8);                      // maxTimestamp
@@ -241,6 +256,222 @@ __global__ void frame_header_kernel(const Batch* __restrict__ batches, int64_t n
   put_be(o + 51, 0xffffull, 2);                                   // producerEpoch -1
   put_be(o + 53, 0xffffffffull, 4);                               // baseSequence -1
   put_be(o + 57, (uint64_t)b.count, 4);
+}
+
+// ---- LZ4 mode -------------------------------------------------------------------------------------------------------
+constexpr int32_t kLzBlock = 65536;     // input bytes per block: the device decoder places block k at k * 64 KiB
+constexpr int kLzFrameHeader = 7;       // magic, FLG, BD, HC
+constexpr int32_t kLzSmall = 4096;      // blocks up to this size are compressed with the small hash table
+constexpr int kLzHashLogSmall = 11, kLzHashLog = 13;  // 4 KiB / 16 KiB of LDS per wave
+
+struct LzBlock {
+  int64_t src_off;  // first byte of the block in the uncompressed buffer (and of its slot in the scratch buffer)
+  int32_t n;        // input bytes: 65536 for all but a frame's last block
+  int32_t batch;
+};
+
+__global__ void frame_lz4_count_kernel(const Batch* __restrict__ batches, int64_t n_batches, int64_t* __restrict__ nblk) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n_batches) return;
+  nblk[i] = i == n_batches ? 0 : (batches[i].records_bytes + kLzBlock - 1) / kLzBlock;
+}
+
+// one thread per block: find its batch in blk_first (the exclusive scan of the counts; every batch has a block, so it
+// rises strictly), its place in it, write its entry
+__global__ void frame_lz4_blocks_kernel(const Batch* __restrict__ batches, int64_t n_batches, const int64_t* __restrict__ blk_first, int64_t n_blocks,
+                                        LzBlock* __restrict__ blocks) {
+  const int64_t blk = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (blk >= n_blocks) return;
+  int64_t lo = 0, hi = n_batches;  // last batch whose first block is <= blk
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (blk_first[mid] <= blk) lo = mid; else hi = mid;
+  }
+  const Batch b = batches[lo];
+  const int64_t k = blk - blk_first[lo];
+  const int64_t rest = b.records_bytes - k * kLzBlock;
+  LzBlock e;
+  e.src_off = b.out_off + kHeader + k * kLzBlock;
+  e.n = (int32_t)(rest < kLzBlock ? rest : kLzBlock);
+  e.batch = (int32_t)lo;
+  blocks[blk] = e;
+}
+
+__device__ inline uint32_t load32(const uint8_t* p) {
+  uint32_t v;
+  __builtin_memcpy(&v, p, 4);
+  return v;
+}
+
+// bytes of the 255-continued length that follows a saturated token nibble
+__device__ inline int32_t lz4_len_bytes(int32_t len) { return len >= 15 ? (len - 15) / 255 + 1 : 0; }
+
+__device__ inline void lz4_put_len(uint8_t* dst, int32_t len, int lane) {  // the whole wave; len >= 15
+  const int32_t v = len - 15, nb = v / 255 + 1;
+  for (int32_t i = lane; i < nb; i += 64) dst[i] = i < nb - 1 ? (uint8_t)255 : (uint8_t)(v % 255);
+}
+
+// One wave compresses one block (LZ4 block format) into the block's scratch slot; bsz[blk] = 4 + its compressed size, or
+// 4 + n when it is to be stored.  Launched once per size class (n_lo < n <= n_hi) with a hash table to match, so that
+// the many small batches of a many-partition publish do not each hold the LDS a 64 KiB block wants.
+//
+// The wave looks at the 64 positions ip .. ip + 63: every lane hashes its 4 bytes, reads its candidate from the table and
+// tests it; the lowest matching lane f wins, the wave extends its match 64 bytes per step, emits the sequence together
+// and goes on behind the match; with no match in the window it moves on by 64.  Two rules that a lane-for-lane
+// simulation of this scheme showed to matter:
+//   * only the lanes up to and including f insert their position into the table (all of them when nothing matched).
+//     Were all 64 to insert before the decision, the positions behind a short match would overwrite the very entries
+//     the next window needs, and then point at themselves: the ratio on Counter state records fell from 2.54 to 1.23;
+//   * a candidate must lie strictly BEFORE the lane's position.  The table starts as all zeros (position 0 is a valid
+//     candidate for every later position: what counts is that the bytes are equal) and a 16-bit entry has no value to
+//     spare for "empty", so a lane at position 0 meets itself; one compare keeps the offset in 1 .. 65535.
+// The table holds 16-bit positions (a block is at most 64 KiB), the block's bytes are read from global memory (the write
+// kernel has just put them there) — 16 KiB of LDS per wave leaves room for ten waves per CU.
+// Writes: a sequence is emitted only if the output stays BELOW n bytes with it; otherwise the block is given up as
+// stored (the output only grows, so it would have ended up stored anyway).  So whatever the input, nothing is written
+// beyond the n bytes of the block's own slot, and table indices are hash values of HASH_LOG bits.
+template <int HASH_LOG>
+__global__ __launch_bounds__(64) void frame_lz4_block_kernel(const LzBlock* __restrict__ blocks, int64_t n_blocks, int32_t n_lo, int32_t n_hi,
+                                                             const uint8_t* __restrict__ src_base, uint8_t* __restrict__ tmp_base,
+                                                             int64_t* __restrict__ bsz) {
+  __shared__ uint16_t table[1 << HASH_LOG];
+  const int64_t blk = blockIdx.x;
+  if (blk >= n_blocks) return;
+  const LzBlock B = blocks[blk];
+  const int32_t n = B.n;
+  if (n <= n_lo || n > n_hi) return;
+  const int lane = threadIdx.x;
+  const uint8_t* __restrict__ src = src_base + B.src_off;
+  uint8_t* __restrict__ dst = tmp_base + B.src_off;
+  for (int i = lane; i < (1 << HASH_LOG); i += 64) table[i] = 0;
+  __syncthreads();
+  const int32_t mflimit = n - 12;    // no match starts after this position ...
+  const int32_t matchlimit = n - 5;  // ... and none reaches this one: the last 5 bytes are literals
+  int32_t ip = 0, anchor = 0, op = 0;
+  while (ip <= mflimit) {  // (a block below 13 bytes is one literal run, longer than its input: stored)
+    const int32_t pos = ip + lane;
+    const bool active = pos <= mflimit;
+    const uint32_t v = active ? load32(src + pos) : 0u;
+    const uint32_t h = (v * 2654435761u) >> (32 - HASH_LOG);
+    const int32_t cand = active ? (int32_t)table[h] : 0;
+    const bool hit = active && cand < pos && load32(src + cand) == v;
+    const uint64_t hits = __ballot(hit);
+    const int f = hits ? __ffsll((long long)hits) - 1 : 63;
+    if (active && lane <= f) table[h] = (uint16_t)pos;
+    __syncthreads();  // one wave: orders this window's inserts before the next window's reads
+    if (!hits) {
+      ip += 64;
+      continue;
+    }
+    const int32_t mpos = ip + f;
+    const int32_t off = mpos - __shfl(cand, f);
+    int32_t len = 4;
+    for (;;) {
+      const int32_t q = mpos + len + lane;
+      const bool same = q < matchlimit && src[q] == src[q - off];
+      const uint64_t diff = __ballot(!same);
+      if (diff) {
+        len += __ffsll((long long)diff) - 1;
+        break;
+      }
+      len += 64;
+    }
+    const int32_t lit = mpos - anchor, ml = len - 4;
+    const int32_t lit_lb = lz4_len_bytes(lit), ml_lb = lz4_len_bytes(ml);
+    const int32_t need = 1 + lit_lb + lit + 2 + ml_lb;
+    if (op + need >= n) {
+      if (lane == 0) bsz[blk] = 4 + (int64_t)n;
+      return;
+    }
+    uint8_t* o = dst + op;
+    if (lane == 0) o[0] = (uint8_t)((lit >= 15 ? 15 : lit) << 4 | (ml >= 15 ? 15 : ml));
+    if (lit >= 15) lz4_put_len(o + 1, lit, lane);
+    o += 1 + lit_lb;
+    for (int32_t i = lane; i < lit; i += 64) o[i] = src[anchor + i];
+    o += lit;
+    if (lane == 0) {
+      o[0] = (uint8_t)off;
+      o[1] = (uint8_t)(off >> 8);
+    }
+    if (ml >= 15) lz4_put_len(o + 2, ml, lane);
+    op += need;
+    ip = mpos + len;
+    anchor = ip;
+  }
+  const int32_t lit = n - anchor;  // the last sequence is literals only
+  const int32_t lit_lb = lz4_len_bytes(lit);
+  const int32_t need = 1 + lit_lb + lit;
+  if (op + need >= n) {
+    if (lane == 0) bsz[blk] = 4 + (int64_t)n;
+    return;
+  }
+  uint8_t* o = dst + op;
+  if (lane == 0) o[0] = (uint8_t)((lit >= 15 ? 15 : lit) << 4);
+  if (lit >= 15) lz4_put_len(o + 1, lit, lane);
+  o += 1 + lit_lb;
+  for (int32_t i = lane; i < lit; i += 64) o[i] = src[anchor + i];
+  if (lane == 0) bsz[blk] = 4 + (int64_t)(op + need);
+}
+
+// per batch (and one entry beyond): bytes of the compressed batch, from the scanned block sizes (bscan[b] = bytes of
+// the size words and blocks before block b)
+__global__ void frame_lz4_batch_size_kernel(int64_t n_batches, const int64_t* __restrict__ blk_first, const int64_t* __restrict__ bscan,
+                                            int64_t* __restrict__ bbytes) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n_batches) return;
+  bbytes[i] = i == n_batches ? 0 : kHeader + kLzFrameHeader + (bscan[blk_first[i + 1]] - bscan[blk_first[i]]) + 4;
+}
+
+// the partitions' spans in the compressed output: nb[p] = first batch of partition p, new_off = scanned batch bytes
+__global__ void frame_lz4_spans_kernel(int32_t n_part, const int64_t* __restrict__ nb, const int64_t* __restrict__ new_off, int64_t* __restrict__ pspan) {
+  const int32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p > n_part) return;
+  pspan[p] = new_off[nb[p]];
+}
+
+// One workgroup per block moves it to its final place: size word + bytes; the batch's first block also writes the frame
+// header, its last the EndMark.  Reads blocks[].src_off (the uncompressed layout), so it runs before the batches are
+// re-addressed.
+__global__ __launch_bounds__(256) void frame_lz4_pack_kernel(const LzBlock* __restrict__ blocks, const int64_t* __restrict__ blk_first,
+                                                             const int64_t* __restrict__ bscan, const int64_t* __restrict__ new_off,
+                                                             const uint8_t* __restrict__ src_base, const uint8_t* __restrict__ tmp_base,
+                                                             uint8_t* __restrict__ out) {
+  const int64_t blk = blockIdx.x;
+  const LzBlock B = blocks[blk];
+  const int64_t first = blk_first[B.batch], last = blk_first[B.batch + 1] - 1;
+  const int64_t csize = bscan[blk + 1] - bscan[blk] - 4;
+  const bool stored = csize >= B.n;
+  uint8_t* frame = out + new_off[B.batch] + kHeader;
+  uint8_t* o = frame + kLzFrameHeader + (bscan[blk] - bscan[first]);
+  const int t = threadIdx.x;
+  if (t < 4) {
+    const uint32_t word = stored ? ((uint32_t)B.n | 0x80000000u) : (uint32_t)csize;
+    o[t] = (uint8_t)(word >> (8 * t));
+  }
+  if (blk == first && t >= 32 && t < 32 + kLzFrameHeader) {
+    const uint8_t head[kLzFrameHeader] = {0x04, 0x22, 0x4D, 0x18, 0x60, 0x40, 0x82};  // HC = (XXH32(FLG BD) >> 8) & 0xff
+    frame[t - 32] = head[t - 32];
+  }
+  if (blk == last && t >= 64 && t < 68) o[4 + csize + (t - 64)] = 0;  // EndMark
+  const uint8_t* s = (stored ? src_base : tmp_base) + B.src_off;
+  o += 4;
+  for (int64_t i = (int64_t)t * 8; i < csize; i += 256 * 8) {
+    if (i + 8 <= csize) {
+      uint64_t v;
+      __builtin_memcpy(&v, s + i, 8);
+      __builtin_memcpy(o + i, &v, 8);
+    } else {
+      for (int64_t k = i; k < csize; ++k) o[k] = s[k];
+    }
+  }
+}
+
+// the batches in the compressed layout: what the header kernel, the copy and the host CRCs work from
+__global__ void frame_lz4_readdress_kernel(Batch* __restrict__ batches, int64_t n_batches, const int64_t* __restrict__ new_off) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_batches) return;
+  batches[i].out_off = new_off[i];
+  batches[i].records_bytes = new_off[i + 1] - new_off[i] - kHeader;
 }
 
 struct Buf {
@@ -269,10 +500,13 @@ struct surge_device_framer {
   hipStream_t stream = nullptr;
   int32_t n_part = 0, max_records = 10000;
   int64_t max_bytes = 1 << 20;
+  int32_t codec = SURGE_SNAPSHOT_CODEC_NONE;
+  int64_t uncompressed_bytes = 0;  // of the last publish's batches
   std::string err;
   std::vector<int64_t> next_offset, part_byte_off;
   std::vector<Batch> h_batches;
   Buf sel, n_sel, keys_a, keys_b, vals_a, vals_b, base, c, pstart, nb, pbytes, d_next, batches, out, bad, temp;
+  Buf lz_nblk, lz_blocks, lz_bsz, lz_bbytes, lz_tmp, lz_out;  // LZ4 mode only
   uint8_t* pinned = nullptr;
   size_t pinned_cap = 0;
 };
@@ -335,7 +569,7 @@ int32_t surge_device_framer_destroy(surge_device_framer* f) {
   Guard g(f->device);
   (void)hipStreamSynchronize(f->stream);
   for (Buf* b : {&f->sel, &f->n_sel, &f->keys_a, &f->keys_b, &f->vals_a, &f->vals_b, &f->base, &f->c, &f->pstart, &f->nb, &f->pbytes, &f->d_next,
-                 &f->batches, &f->out, &f->bad, &f->temp})
+                 &f->batches, &f->out, &f->bad, &f->temp, &f->lz_nblk, &f->lz_blocks, &f->lz_bsz, &f->lz_bbytes, &f->lz_tmp, &f->lz_out})
     b->release();
   if (f->pinned) (void)hipHostFree(f->pinned);
   delete f;
@@ -344,11 +578,21 @@ int32_t surge_device_framer_destroy(surge_device_framer* f) {
 
 const char* surge_device_framer_last_error(const surge_device_framer* f) { return f ? f->err.c_str() : g_frame_err.c_str(); }
 
+int32_t surge_device_framer_set_compression(surge_device_framer* f, int32_t codec) {
+  if (!f) return ffail(nullptr, E_INVALID, "framer is NULL");
+  if (codec != SURGE_SNAPSHOT_CODEC_NONE && codec != SURGE_SNAPSHOT_CODEC_LZ4)
+    return ffail(f, E_INVALID, "unknown codec (the device framer writes uncompressed or LZ4 batches)");
+  f->codec = codec;
+  return OK;
+}
+
 int32_t surge_device_framer_next_offsets(const surge_device_framer* f, int64_t* out) {
   if (!f || !out) return ffail(nullptr, E_INVALID, "bad argument");
   std::memcpy(out, f->next_offset.data(), f->next_offset.size() * 8);
   return OK;
 }
+
+int64_t surge_device_framer_uncompressed_bytes(const surge_device_framer* f) { return f ? f->uncompressed_bytes : -1; }
 
 int32_t surge_device_framer_frame(surge_device_framer* f, int64_t n_aggregates, const uint8_t* d_kind, const int32_t* d_partition,
                                   const uint8_t* d_keys_utf8, const int64_t* d_key_off, const uint8_t* d_values, const int64_t* d_val_off,
@@ -363,10 +607,16 @@ int32_t surge_device_framer_frame(surge_device_framer* f, int64_t n_aggregates, 
   const int32_t P = f->n_part;
   const int64_t n = n_aggregates;
   std::fill(f->part_byte_off.begin(), f->part_byte_off.end(), 0);
+  struct SpanReset {  // on an error nothing advances, and no partition has a span: whichever return it is
+    std::vector<int64_t>& spans;
+    bool done = false;
+    ~SpanReset() { if (!done) std::fill(spans.begin(), spans.end(), 0); }
+  } span_reset{f->part_byte_off};
   *bytes_out = f->pinned;
   *part_byte_off_out = f->part_byte_off.data();
   if (n_records_out) *n_records_out = 0;
   if (n_batches_out) *n_batches_out = 0;
+  f->uncompressed_bytes = 0;
   if (n == 0) return OK;
 
   // 1. the changed aggregates, in index order
@@ -436,23 +686,13 @@ int32_t surge_device_framer_frame(surge_device_framer* f, int64_t n_aggregates, 
   FCHK(f, hipMemcpyAsync(&bad, f->bad.p, 4, hipMemcpyDeviceToHost, st));
   FCHK(f, hipMemcpyAsync(f->part_byte_off.data(), f->pbytes.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToHost, st));
   FCHK(f, hipStreamSynchronize(st));
-  if (bad) {
-    std::fill(f->part_byte_off.begin(), f->part_byte_off.end(), 0);
+  if (bad)
     return ffail(f, E_RANGE, "a changed aggregate has an unknown kind, a partition outside [0, n_partitions), a negative key / value span, or bytes in a table that was passed as NULL");
-  }
-  const int64_t n_batches = totals[0], n_bytes = totals[1];
+  const int64_t n_batches = totals[0];
+  const bool lz4 = f->codec == SURGE_SNAPSHOT_CODEC_LZ4;
+  int64_t n_bytes = totals[1];  // of the uncompressed layout; LZ4 mode replaces it below
   FCHK(f, f->batches.reserve((size_t)n_batches * sizeof(Batch)));
   FCHK(f, f->out.reserve((size_t)n_bytes));
-  if ((size_t)n_bytes > f->pinned_cap) {
-    if (f->pinned) (void)hipHostFree(f->pinned);
-    f->pinned = nullptr;
-    f->pinned_cap = 0;
-    const size_t want = (size_t)n_bytes + (size_t)n_bytes / 4;
-    void* hp = nullptr;
-    FCHK(f, hipHostMalloc(&hp, want, hipHostMallocDefault));
-    f->pinned = (uint8_t*)hp;
-    f->pinned_cap = want;
-  }
   try {
     f->h_batches.resize((size_t)n_batches);
   } catch (const std::bad_alloc&) {
@@ -464,9 +704,72 @@ int32_t surge_device_framer_frame(surge_device_framer* f, int64_t n_aggregates, 
   // 4. the bytes
   hipLaunchKernelGGL(frame_write_kernel, dim3(grid(n_sel)), dim3(256), 0, st, (const Batch*)f->batches.p, n_batches, order, (const int64_t*)f->sel.p, n_sel,
                      d_kind, (const uint32_t*)f->base.p, c1, c2, c3, d_keys_utf8, d_key_off, d_values, d_val_off, (uint8_t*)f->out.p);
-  hipLaunchKernelGGL(frame_header_kernel, dim3(grid(n_batches)), dim3(256), 0, st, (const Batch*)f->batches.p, n_batches, timestamp_ms, (uint8_t*)f->out.p);
+  const uint8_t* d_final = (const uint8_t*)f->out.p;
+  if (lz4) {
+    // 4b. every batch's records section -> one LZ4 frame, the batches packed at their compressed sizes
+    auto scan = [&](int64_t* v, size_t count) -> int32_t {  // exclusive, in place
+      size_t need = 0;
+      FCHK(f, rocprim::exclusive_scan(nullptr, need, (const int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, count, rocprim::plus<int64_t>(), st));
+      if (need > f->temp.cap) {
+        FCHK(f, hipStreamSynchronize(st));  // earlier scans may still use the scratch
+        FCHK(f, f->temp.reserve(need));
+      }
+      FCHK(f, rocprim::exclusive_scan(f->temp.p, need, (const int64_t*)v, v, (int64_t)0, count, rocprim::plus<int64_t>(), st));
+      return OK;
+    };
+    FCHK(f, f->lz_nblk.reserve((size_t)(n_batches + 1) * 8));
+    FCHK(f, f->lz_bbytes.reserve((size_t)(n_batches + 1) * 8));
+    FCHK(f, f->lz_tmp.reserve((size_t)n_bytes));
+    int64_t* blk_first = (int64_t*)f->lz_nblk.p;
+    int64_t* new_off = (int64_t*)f->lz_bbytes.p;
+    hipLaunchKernelGGL(frame_lz4_count_kernel, dim3(grid(n_batches + 1)), dim3(256), 0, st, (const Batch*)f->batches.p, n_batches, blk_first);
+    if (const int32_t rc = scan(blk_first, (size_t)n_batches + 1)) return rc;
+    int64_t n_blocks = 0;
+    FCHK(f, hipMemcpyAsync(&n_blocks, blk_first + n_batches, 8, hipMemcpyDeviceToHost, st));
+    FCHK(f, hipStreamSynchronize(st));
+    if (n_blocks < n_batches || n_blocks > 0x7fffffffll)  // (every batch has a block; LzBlock.batch and the grids are 32 bits wide)
+      return ffail(f, E_RANGE, n_blocks < n_batches ? "the LZ4 block count is inconsistent with the batches" : "more than 2^31 LZ4 blocks in one publish");
+    FCHK(f, f->lz_blocks.reserve((size_t)n_blocks * sizeof(LzBlock)));
+    FCHK(f, f->lz_bsz.reserve((size_t)(n_blocks + 1) * 8));
+    const LzBlock* blocks = (const LzBlock*)f->lz_blocks.p;
+    int64_t* bscan = (int64_t*)f->lz_bsz.p;
+    hipLaunchKernelGGL(frame_lz4_blocks_kernel, dim3(grid(n_blocks)), dim3(256), 0, st, (const Batch*)f->batches.p, n_batches, (const int64_t*)blk_first,
+                       n_blocks, (LzBlock*)f->lz_blocks.p);
+    FCHK(f, hipMemsetAsync(bscan + n_blocks, 0, 8, st));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(frame_lz4_block_kernel<kLzHashLogSmall>), dim3((unsigned)n_blocks), dim3(64), 0, st, blocks, n_blocks, 0, kLzSmall,
+                       (const uint8_t*)f->out.p, (uint8_t*)f->lz_tmp.p, bscan);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(frame_lz4_block_kernel<kLzHashLog>), dim3((unsigned)n_blocks), dim3(64), 0, st, blocks, n_blocks, kLzSmall, kLzBlock,
+                       (const uint8_t*)f->out.p, (uint8_t*)f->lz_tmp.p, bscan);
+    if (const int32_t rc = scan(bscan, (size_t)n_blocks + 1)) return rc;
+    hipLaunchKernelGGL(frame_lz4_batch_size_kernel, dim3(grid(n_batches + 1)), dim3(256), 0, st, n_batches, (const int64_t*)blk_first, (const int64_t*)bscan,
+                       new_off);
+    if (const int32_t rc = scan(new_off, (size_t)n_batches + 1)) return rc;
+    // (nb is the scanned batch index of every partition, pbytes is free again: the spans of the compressed output)
+    hipLaunchKernelGGL(frame_lz4_spans_kernel, dim3(grid(P + 1)), dim3(256), 0, st, P, (const int64_t*)f->nb.p, (const int64_t*)new_off, (int64_t*)f->pbytes.p);
+    FCHK(f, hipGetLastError());
+    FCHK(f, hipMemcpyAsync(f->part_byte_off.data(), f->pbytes.p, (size_t)(P + 1) * 8, hipMemcpyDeviceToHost, st));
+    FCHK(f, hipStreamSynchronize(st));
+    n_bytes = f->part_byte_off[(size_t)P];
+    FCHK(f, f->lz_out.reserve((size_t)n_bytes));
+    hipLaunchKernelGGL(frame_lz4_pack_kernel, dim3((unsigned)n_blocks), dim3(256), 0, st, blocks, (const int64_t*)blk_first, (const int64_t*)bscan,
+                       (const int64_t*)new_off, (const uint8_t*)f->out.p, (const uint8_t*)f->lz_tmp.p, (uint8_t*)f->lz_out.p);
+    hipLaunchKernelGGL(frame_lz4_readdress_kernel, dim3(grid(n_batches)), dim3(256), 0, st, (Batch*)f->batches.p, n_batches, (const int64_t*)new_off);
+    d_final = (const uint8_t*)f->lz_out.p;
+  }
+  if ((size_t)n_bytes > f->pinned_cap) {
+    if (f->pinned) (void)hipHostFree(f->pinned);
+    f->pinned = nullptr;
+    f->pinned_cap = 0;
+    const size_t want = (size_t)n_bytes + (size_t)n_bytes / 4;
+    void* hp = nullptr;
+    FCHK(f, hipHostMalloc(&hp, want, hipHostMallocDefault));
+    f->pinned = (uint8_t*)hp;
+    f->pinned_cap = want;
+  }
+  hipLaunchKernelGGL(frame_header_kernel, dim3(grid(n_batches)), dim3(256), 0, st, (const Batch*)f->batches.p, n_batches, timestamp_ms, f->codec,
+                     (uint8_t*)d_final);
   FCHK(f, hipGetLastError());
-  FCHK(f, hipMemcpyAsync(f->pinned, f->out.p, (size_t)n_bytes, hipMemcpyDeviceToHost, st));
+  FCHK(f, hipMemcpyAsync(f->pinned, d_final, (size_t)n_bytes, hipMemcpyDeviceToHost, st));
   FCHK(f, hipMemcpyAsync(f->h_batches.data(), f->batches.p, (size_t)n_batches * sizeof(Batch), hipMemcpyDeviceToHost, st));
   FCHK(f, hipStreamSynchronize(st));
 
@@ -497,6 +800,8 @@ int32_t surge_device_framer_frame(surge_device_framer* f, int64_t n_aggregates, 
     for (std::thread& t : th) t.join();
   }
   for (const Batch& b : f->h_batches) f->next_offset[(size_t)b.partition] += b.count;
+  f->uncompressed_bytes = totals[1];
+  span_reset.done = true;
   *bytes_out = f->pinned;
   if (n_records_out) *n_records_out = n_sel;
   if (n_batches_out) *n_batches_out = n_batches;

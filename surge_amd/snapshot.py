@@ -140,17 +140,39 @@ class RecordBatchWriter:
 class DeviceFramer:
     """Record batches of a bulk publish framed ON THE GPU (``surge_device_framer_*`` in ``include/surge_snapshot.h``): the
     inputs are the device arrays a publish already has (the delta's kinds, the encoder's text + offsets, the key table,
-    the partitions); the output is byte-identical to ``RecordBatchWriter.append`` + flush on the same input
-    (uncompressed batches).  Needs a GPU."""
+    the partitions).  Uncompressed batches (the default) are byte-identical to ``RecordBatchWriter.append`` + flush on
+    the same input; ``compression="lz4"`` keeps the cuts, offsets and header fields and compresses every batch's
+    records on the device into one LZ4 frame (the same records to any LZ4 decoder, not the host compressor's bytes).
+    Needs a GPU."""
 
-    def __init__(self, n_partitions: int, device: int = 0, max_records_per_batch: int = 0, max_batch_bytes: int = 0):
+    CODECS = RecordBatchWriter.CODECS
+
+    def __init__(self, n_partitions: int, device: int = 0, max_records_per_batch: int = 0, max_batch_bytes: int = 0, compression: str = "none"):
+        if compression not in self.CODECS:
+            raise ValueError(f"unknown compression {compression!r} (one of {sorted(self.CODECS)})")
         self._lib = _native.load()
         self._h = ctypes.c_void_p()
         self.n_partitions = n_partitions
         rc = self._lib.surge_device_framer_create(device, None, n_partitions, max_records_per_batch, max_batch_bytes, ctypes.byref(self._h))
         if rc != 0:
             raise RuntimeError(f"surge_device_framer_create: {rc}: {(self._lib.surge_device_framer_last_error(None) or b'').decode()}")
-        self.records = self.batches = 0
+        self.records = self.batches = self.uncompressed_bytes = 0
+        self.compression = "none"
+        if compression != "none":
+            try:
+                self.set_compression(compression)
+            except BaseException:
+                self.close()  # nobody else will: the object is never handed out
+                raise
+
+    def set_compression(self, compression: str) -> None:
+        """Codec of the batches framed from now on ("none" or "lz4"); the partitions' logs continue."""
+        if compression not in self.CODECS:
+            raise ValueError(f"unknown compression {compression!r} (one of {sorted(self.CODECS)})")
+        rc = self._lib.surge_device_framer_set_compression(self._h, self.CODECS[compression])
+        if rc != 0:
+            raise RuntimeError(f"surge_device_framer_set_compression: {rc}: {(self._lib.surge_device_framer_last_error(self._h) or b'').decode()}")
+        self.compression = compression
 
     def close(self):
         if self._h:
@@ -178,6 +200,7 @@ class DeviceFramer:
         if rc != 0:
             raise RuntimeError(f"surge_device_framer_frame: {rc}: {(self._lib.surge_device_framer_last_error(self._h) or b'').decode()}")
         self.records, self.batches = nrec.value, nbat.value
+        self.uncompressed_bytes = int(self._lib.surge_device_framer_uncompressed_bytes(self._h))
         off = np.ctypeslib.as_array(ctypes.cast(offs, ctypes.POINTER(ctypes.c_int64)), shape=(self.n_partitions + 1,)).copy()
         total = int(off[-1])
         if total == 0:
@@ -198,16 +221,18 @@ class BulkSnapshotPublisher:
           -> GPU encoder restricted to the changed Some aggregates (writeState text; N3)
           -> K4 partitions of the aggregate ids (once per key table)
           -> uncompressed batches: DeviceFramer (records + headers written on the GPU, one D2H, CRC-32C on the host)
-             lz4 batches: one D2H of {kinds, text, offsets} -> RecordBatch v2 encoder (C++; N2)
+             lz4 batches, ``device_compression=True``: the same, every batch's records compressed on the GPU first
+             lz4 batches otherwise: one D2H of {kinds, text, offsets} -> RecordBatch v2 encoder (C++; N2)
           -> bytes per partition (device framing: views of a page-locked buffer, valid until the next publish).
 
     ``keys`` are the aggregate ids in dense-index order; ``template`` declares the model's serialized state."""
 
     def __init__(self, engine, keys: Optional[Sequence[str]], n_partitions: int, template=None, device=None, tables=None,
-                 compression: str = "none", device_framing: bool = True):
+                 compression: str = "none", device_framing: bool = True, device_compression: bool = False):
         """``keys``: aggregate ids in dense-index order; or ``tables = (keys_utf8, key_off, keys_utf16, off16)`` as
         tensors / arrays built without Python strings (large synthetic populations).  ``compression``: "none" or "lz4"
-        (the reference producer's ``compression.type``)."""
+        (the reference producer's ``compression.type``).  ``device_compression``: lz4 batches are framed AND compressed
+        by the ``DeviceFramer`` (needs ``device_framing``); without it they go through the host writer and its compressor."""
         import torch
 
         from .encode import JsonTemplate, key_table_utf8
@@ -235,8 +260,9 @@ class BulkSnapshotPublisher:
         self.partitions = d_part.cpu().numpy()
         self.d_part = d_part
         # uncompressed batches are framed on the device (DeviceFramer: byte-identical to the host writer); lz4 batches
-        # go through the host writer, whose compressor it is
-        self.framer = DeviceFramer(n_partitions, device=self.device.index or 0) if compression == "none" and device_framing else None
+        # go through the host writer and its compressor unless the device's compressor was asked for
+        on_device = device_framing and (compression == "none" or device_compression)
+        self.framer = DeviceFramer(n_partitions, device=self.device.index or 0, compression=compression) if on_device else None
         self.timings: Dict[str, float] = {}
 
     def close(self):
@@ -281,6 +307,9 @@ class BulkSnapshotPublisher:
             t3 = time.perf_counter()
             self.timings = {"gpu_delta_and_encode_ms": (t1 - t0) * 1e3, "device_framing_copy_crc_ms": (t3 - t1) * 1e3, "values": nv.value,
                             "tombstones": nt.value, "text_bytes": int(d_off[n].item()), "batches": self.framer.batches}
+            if self.framer.compression != "none":
+                self.timings["record_batch_bytes"] = sum(len(v) for v in out.values())
+                self.timings["uncompressed_bytes"] = self.framer.uncompressed_bytes
             return out
         # compact on the device: only what changed crosses PCIe and is walked by the writer (the encoder wrote text for
         # VALUE aggregates only, so the text is already contiguous and the selected offsets are its record boundaries)
