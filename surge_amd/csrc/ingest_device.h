@@ -1,0 +1,235 @@
+// ingest_device.h — what the translation units of the device decoder share.  Internal, like replay_internal.h: not part of
+// the C ABI.  Each stage is a unit of its own that knows the plain structs below and nothing of the decoder around it
+// (ingest_decoder.hip, the host object): ingest_crc.hip, ingest_lz4.hip, ingest_records.hip, ingest_intern.hip.  Their
+// launch_* functions enqueue on the stream they are given and return what the runtime said; none of them waits for the device.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "../../include/surge_ingest.h"
+#include "f64_parse.h"
+
+namespace surge {
+namespace ingest {
+
+// per-record status
+enum : uint32_t {
+  RS_OK = 0,
+  RS_SKIP = 1,          // the producer's flush record (empty key, empty value): not an event
+  RS_NULL = 2,          // null key or null value: not an event
+  RS_MALFORMED = 3,     // varint / span runs past its record or batch
+  RS_JSON = 4,          // value is not the JSON the template describes
+  RS_TYPE = 5,          // unknown discriminator value
+  RS_FIELD = 6,         // a field the template names is missing or is not the number it should be
+  RS_SIZE = 7,          // fixed-16 topic: value is not 16 bytes
+  RS_F64_HOST = 8,      // a Double the fast parser cannot decide: the host re-parses this value exactly
+  RS_COLLISION = 9,     // two different keys with the same 64-bit hash
+};
+
+struct RecMeta {
+  int64_t key_off, val_off, offset;
+  uint64_t hash;
+  int32_t key_len;   // aggregate id length (key up to ':')
+  int32_t val_len;
+  uint32_t slot;
+  uint32_t status;
+};
+
+struct Section {  // = surge_batch_section + the batch's first record index in this push
+  int64_t byte_off, byte_len, base_offset;
+  int32_t n_records, reserved;
+  int64_t rec_first;
+};
+
+struct ErrorCell {
+  unsigned long long first_bad;  // min over (record index << 8 | status)
+  unsigned int reserved, n_f64_host;
+  unsigned int lz4_bad;          // the first section whose LZ4 frame did not decode (~0 = none)
+  unsigned int crc_bad;          // the first section whose bytes do not give the batch's CRC-32C (~0 = none; SURGE_INGEST_DEVICE_CRC)
+};
+
+__device__ __forceinline__ void report(ErrorCell* err, int64_t rec, uint32_t status) {
+  atomicMin(&err->first_bad, ((unsigned long long)rec << 8) | status);
+}
+
+// a batch whose CRC-32C the device finishes (ingest_crc.hip)
+struct CrcSpan {
+  int64_t off;      // first byte the device still has to run the CRC over, in the staged bytes
+  int32_t len;
+  int32_t section;
+  uint32_t expect;  // the batch's CRC-32C
+  uint32_t state;   // the CRC register in front of `off`: after the 40 header bytes (the host ran those), or ~0 (in-place framing:
+                    // off points at the header bytes, the device runs everything)
+};
+
+// one block of an LZ4 frame (ingest_lz4.hip)
+struct Lz4Block {
+  int64_t src_off;   // in the staged bytes
+  int64_t dst_off;   // in the decompressed area
+  int32_t src_len;   // bit 31: stored uncompressed
+  int32_t section;   // the section this block belongs to
+  int32_t last;      // the frame's last block: sets the section's length
+  int32_t index;     // k: this block's number inside its frame
+  int64_t seq_off;   // first entry of this block in the sequence table (two-pass decode); -1: the one-pass kernel takes it
+};
+
+// The scratch of the two-pass LZ4 decode, per push.  The caller allocates what lz4_scratch_bytes asks for and sets the four
+// pointers; launch_lz4 clears the class counters and lays the class lists out behind them.
+struct Lz4Work {
+  int32_t dbg = 0;     // SURGE_DBG_DECODE (timing experiments only): 1 = image in, image out; 2 = the byte maps are built, never applied
+  int32_t* state;      // per block: >= 0 decoded (its size), -1 malformed
+  int32_t* n_seq;      // per block: entries written
+  uint2* seq;          // the sequence table
+  int32_t* cls_count;  // [kLz4Classes + 1]: blocks per LDS class; the last is "stored" (no LDS: copied as they are)
+  int32_t* cls_list;   // [kLz4Classes + 1][n_blocks]
+};
+constexpr int kLz4Classes = 6;
+
+struct Lz4ScratchBytes {  // bytes behind Lz4Block table, Lz4Work::state, ::n_seq, ::seq and ::cls_count (all 0: a push without LZ4 blocks)
+  size_t blocks = 0, state = 0, n_seq = 0, seq = 0, cls = 0;
+};
+
+// The LZ4 work of one push, built up section by section by lz4_plan_section.
+struct Lz4Plan {
+  std::vector<Lz4Block> blocks;  // (the source of an asynchronous copy: it lives as long as the push)
+  int64_t area = 0;              // bytes of the device-side decompressed area handed out so far (multiples of 64 KiB)
+  int64_t n_seq = 0;             // sequence-table entries handed out (two-pass decode)
+  void clear() { blocks.clear(); area = 0; n_seq = 0; }
+};
+
+enum Lz4Route {
+  LZ4_ON_DEVICE,  // the frame's blocks joined the plan; its output starts at *area_off of the decompressed area
+  LZ4_ON_HOST,    // a frame the device does not take block by block: decompressed here, appended to host_out
+  LZ4_TOO_LARGE,  // ... which expands beyond 2 GiB
+  LZ4_BAD_FRAME,  // ... which does not decode
+};
+
+typedef const __attribute__((address_space(3))) uint8_t* lds_ptr_t;
+
+// Four bytes from p on, whatever its alignment, as ONE load instruction: the two aligned dwords that hold them
+// (ds_read2_b32 / global_load_dwordx2), funnel-shifted into place.  Reads up to 7 bytes past p: the staged bytes and the
+// LDS copies of a section end at least 16 bytes after their last byte.  (Round 5: the record and JSON walks read their bytes
+// one ds_read_u8 at a time — ~200 dependent LDS reads per record; section_kernel waited 71 % of its wave cycles.)
+// (the aligned pointer is derived from p by pointer arithmetic, not through an integer: the compiler keeps p's address space —
+// global_load for the staged bytes, not flat_load)
+__device__ __forceinline__ uint32_t load4(lds_ptr_t p) {
+  const uint32_t sh = (uint32_t)(uintptr_t)p & 3u;
+  const __attribute__((address_space(3))) uint32_t* q = (const __attribute__((address_space(3))) uint32_t*)(p - sh);
+  return __builtin_amdgcn_alignbyte(q[1], q[0], sh);
+}
+__device__ __forceinline__ uint32_t load4(const uint8_t* p) {
+  const uint32_t sh = (uint32_t)((uintptr_t)p & 3u);
+  const uint32_t* q = (const uint32_t*)(p - sh);
+  return __builtin_amdgcn_alignbyte(q[1], q[0], sh);
+}
+
+// 64-bit hash of an aggregate id under the table's seed (a re-seed follows a detected collision); 0 marks an empty slot.
+// (begin / end: the record parser hashes the id while it looks for its ':')
+__device__ __forceinline__ uint64_t hash_key_begin(uint64_t seed) { return 0x9E3779B97F4A7C15ull + seed * 0xC2B2AE3D27D4EB4Full; }
+__device__ __forceinline__ uint64_t hash_key_end(uint64_t h, int n, uint64_t seed) {
+  h ^= (uint64_t)n * 0xFF51AFD7ED558CCDull;
+  h ^= h >> 29;
+  h *= 0xD6E8FEB86659FD93ull;
+  h ^= h >> 32;
+  if (seed >> 63) h &= 0xffull;  // test hook (SURGE_INGEST_DEBUG_WEAK_HASH): collisions guaranteed until the first re-seed
+  return h == 0ull ? 1ull : h;
+}
+template <typename P>
+__device__ __forceinline__ uint64_t hash_key(P p, int n, uint64_t seed) {
+  uint64_t h = hash_key_begin(seed);
+  for (int i = 0; i < n; ++i) h = (h ^ p[i]) * 0x100000001B3ull;
+  return hash_key_end(h, n, seed);
+}
+
+// The template as the kernels use it: the distinct field names the decoder has to look for, with their lengths, and per
+// event type which of them carry its sequence number / argument — so ONE pass over the object finds everything (round 3
+// walked the text twice: once for the discriminator, once for the fields of the type it selected).
+constexpr int kEvjNames = 1 + 2 * SURGE_EVJ_MAX_TYPES;
+struct EvjDevice {
+  uint32_t n_types, n_names;                  // names[0] is the discriminator ("" when the template has none)
+  alignas(8) char names[kEvjNames][SURGE_EVJ_NAME];
+  uint8_t name_len[kEvjNames];
+  alignas(8) char type_name[SURGE_EVJ_MAX_TYPES][SURGE_EVJ_NAME];
+  uint8_t type_name_len[SURGE_EVJ_MAX_TYPES];
+  uint8_t seq_name[SURGE_EVJ_MAX_TYPES], arg_name[SURGE_EVJ_MAX_TYPES];  // index into names, 0xff = none
+  uint32_t event_type[SURGE_EVJ_MAX_TYPES], arg_kind[SURGE_EVJ_MAX_TYPES];
+};
+
+constexpr int kEvjTrack = 8;  // numeric field names tracked in registers; templates with more use the generic lookup below
+
+struct JsonCtx {  // what the value decoder needs besides the value
+  const EvjDevice* tmpl;  // nullptr: 16-byte fixed events
+  const surge::F64ParseTable* ptab;
+  int32_t dbg = 0;  // SURGE_DBG_DECODE (timing experiments only, results are NOT the topic's): 1 = sections are staged, nothing else; 2 = staged and chained, no record decoded
+#ifdef SURGE_EXPERIMENTS
+  unsigned long long* ticks = nullptr;  // per workgroup: wall clock (10 ns) at start, after staging, after the chain, at the end
+#endif
+};
+
+// ---- the key table (ingest_intern.hip) -------------------------------------------------------------------------------------
+// One 16-byte slot per entry (round 5; three parallel arrays before): a probe, the flag pass and the final gather each touch
+// ONE random line of the 2^25-slot table per record instead of two or three.
+struct TableSlot {
+  unsigned long long hash;  // 0 = empty
+  uint32_t key_id;          // 0xffffffff = not assigned yet (inserted by the push in flight)
+  uint32_t first_rec;       // of a slot inserted by the push in flight: its first record (0xffffffff otherwise)
+};
+static_assert(sizeof(TableSlot) == 16, "one slot = one 16-byte store");
+struct Table {
+  TableSlot* s;
+  uint64_t mask;
+};
+
+struct KeyTable {  // the table with what stands behind its ids
+  Table t;
+  uint8_t* arena;                // the key bytes, one id after the other
+  int64_t* key_off;              // [n_keys + 1] into the arena
+  unsigned long long* key_hash;  // [n_keys] under the current seed
+  int64_t n_keys, arena_bytes;
+};
+
+struct InternScratch {  // per push: (n_rec + 1) entries each, and rocPRIM's temporary storage
+  unsigned long long *first, *first_scan;
+  uint32_t *keep, *keep_pos;
+  void* temp;
+  size_t temp_bytes;
+};
+
+// ---- ingest_crc.hip: one wave per span over the staged bytes; a mismatch lowers err->crc_bad to the span's section ----------
+hipError_t launch_crc(const uint8_t* bytes, const CrcSpan* spans, int32_t n_spans, ErrorCell* err, hipStream_t st);
+
+// ---- ingest_lz4.hip ----------------------------------------------------------------------------------------------------------
+// plans the section whose records are the LZ4 frame [frame, frame + frame_len), staged at src_off of the device bytes
+Lz4Route lz4_plan_section(Lz4Plan& plan, const uint8_t* frame, int64_t frame_len, int64_t src_off, int32_t section, int64_t* area_off,
+                          std::vector<uint8_t>& host_out);
+Lz4ScratchBytes lz4_scratch_bytes(const Lz4Plan& plan);
+// decodes the plan's blocks (d_blocks: their table on the device) from `bytes` into `area`; a frame's last block sets its
+// section's byte_len, a frame that does not decode zeroes it and lowers err->lz4_bad
+hipError_t launch_lz4(const Lz4Plan& plan, const uint8_t* bytes, uint8_t* area, const Lz4Block* d_blocks, Lz4Work w, Section* sections, ErrorCell* err, hipStream_t st);
+
+// ---- ingest_records.hip: meta / ev_tmp / f64_host_list per record ---------------------------------------------------------------
+// one workgroup per section, as wide as max_recs (the push's largest batch) needs
+hipError_t launch_sections(const uint8_t* bytes, const Section* sections, int64_t n_sections, int32_t max_recs, uint64_t seed, JsonCtx jc, RecMeta* meta,
+                           uint4* ev_tmp, uint32_t* f64_host_list, ErrorCell* err, hipStream_t st);
+// records that arrive already framed: the bytes hold the keys first, the values from val_base on
+hipError_t launch_records(const uint8_t* bytes, const int64_t* key_off, const int64_t* val_off, const int64_t* offsets, int64_t val_base, int64_t n_rec,
+                          uint64_t seed, JsonCtx jc, RecMeta* meta, uint4* ev_tmp, uint32_t* f64_host_list, ErrorCell* err, hipStream_t st);
+
+// ---- ingest_intern.hip -------------------------------------------------------------------------------------------------------
+hipError_t intern_temp_bytes(int64_t n_rec, size_t* bytes, hipStream_t st);  // of InternScratch::temp
+void launch_table_build(const KeyTable& k, hipStream_t st);                  // a fresh table: every slot empty, then the known keys by their hashes
+void launch_rekey_records(RecMeta* meta, int64_t n_rec, const uint8_t* bytes, uint64_t seed, hipStream_t st);  // the table was re-seeded after stage 1 hashed the keys
+// probe + flag + the two scans: afterwards first_scan[n_rec] = new keys << 40 | their bytes, keep_pos[n_rec] = records delivered
+hipError_t launch_intern_probe(RecMeta* meta, int64_t n_rec, const uint8_t* bytes, const KeyTable& k, const InternScratch& sc, ErrorCell* err, hipStream_t st);
+// a detected collision: the push's slots out, every known key and every record of the push re-hashed under `seed`, the table rebuilt
+void launch_intern_reseed(RecMeta* meta, int64_t n_rec, const uint8_t* bytes, const KeyTable& k, uint64_t seed, hipStream_t st);
+// the commit: the n_new keys the push discovered get their ids and arena bytes, the delivered records go to the result arrays
+void launch_intern_commit(const RecMeta* meta, int64_t n_rec, const uint8_t* bytes, const KeyTable& k, const InternScratch& sc, int64_t n_new,
+                          const uint4* ev_tmp, int64_t out_base, int64_t* agg_out, uint4* ev_out, int64_t* off_out, hipStream_t st);
+void launch_intern_rollback(const RecMeta* meta, int64_t n_rec, const Table& t, hipStream_t st);  // a failed push takes the keys it probed out again
+
+}  // namespace ingest
+}  // namespace surge

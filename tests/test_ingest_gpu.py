@@ -250,7 +250,7 @@ def test_device_decoder_decodes_play_json_counter_and_bank_account_events_like_t
 @pytest.mark.parametrize("per_batch", [1, 64, 65, 128, 129, 192, 193, 600])
 def test_every_workgroup_size_of_the_record_kernel_decodes_like_the_host_decoder(per_batch):
     """section_kernel runs with 64 / 128 / 192 / 256 lanes — the smallest that takes the push's largest batch in one round
-    (ingest_kernels.hip) — out of three LDS classes (sections up to 8 KiB, up to 16.25 KiB, the rest): batches of every size
+    (ingest_records.hip) — out of three LDS classes (sections up to 8 KiB, up to 16.25 KiB, the rest): batches of every size
     around the boundaries, lz4 and plain, small and long values, one push and several."""
     rng = random.Random(1000 + per_batch)
     bl = CounterBusinessLogic()
