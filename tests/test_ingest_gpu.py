@@ -749,9 +749,10 @@ def test_two_host_threads_drive_one_decoder_and_the_fold_takes_the_results_witho
 @pytest.mark.gpu
 def test_a_batchs_crc32c_is_finished_on_the_device_and_a_damaged_byte_fails_the_push_like_the_host_check():
     """SURGE_INGEST_DEVICE_CRC: the framer checksums the 40 header bytes a batch's CRC-32C covers and
-    passes the register on; one wave per section finishes it over the section's bytes on the device (crc_kernel: 16 KiB tiles,
-    lane pieces combined by multiplications with x^(8 n) mod P).  Sections of every shape — one record, a few hundred bytes,
-    more than one 16 KiB tile, more than two, lz4 frames and plain ones, at whatever alignment the arena gives them: the
+    passes the register on; one wave per section finishes it over the section's bytes on the device (crc_kernel: 4 KiB tiles,
+    a 64-byte piece per lane, the pieces combined by multiplications with x^(8 n) mod P).  Sections of every shape — one record,
+    a few hundred bytes, more than one 4 KiB tile, more than ten, lz4 frames and plain ones, at whatever alignment the arena gives
+    them (tests/test_ingest_stage_edges_gpu.py sweeps the lengths and alignments): the
     decoded records are the host-checked framer's; one damaged byte — first / middle / last of a section, inside the covered
     header fields, the CRC field itself — fails the PUSH with the host check's status (SURGE_E_CORRUPT), delivers nothing,
     interns nothing, and the decoder takes the undamaged bytes afterwards."""
