@@ -325,6 +325,14 @@ __device__ inline void lz4_put_len(uint8_t* dst, int32_t len, int lane) {  // th
 //   * a candidate must lie strictly BEFORE the lane's position.  The table starts as all zeros (position 0 is a valid
 //     candidate for every later position: what counts is that the bytes are equal) and a 16-bit entry has no value to
 //     spare for "empty", so a lane at position 0 meets itself; one compare keeps the offset in 1 .. 65535.
+// A third rule is for what the window scheme cannot see: all 64 lanes read their candidates before any of them inserts, so
+// a repeat that begins inside a window of new content is found one window late -- and in the block's LAST window
+// (ip + 64 > n - 12) not at all.  There, when the table gave no hit, every lane takes the nearest earlier lane of the
+// window with the same 4 bytes as its candidate: one shuffle per active lane of that window, in every block whose last
+// window has no table hit -- every incompressible block, and every small block without a repeat, of which a
+// many-partition publish has many (200 000 blocks of 35 to 75 random bytes: 232 us for the launch, 73 us without the
+// search, in a publish of 25 ms).  Without it no block below 76 bytes could shrink unless it repeated its own first
+// bytes, and a batch of one small record of zeros was stored.
 // The table holds 16-bit positions (a block is at most 64 KiB), the block's bytes are read from global memory (the write
 // kernel has just put them there) — 16 KiB of LDS per wave leaves room for ten waves per CU.
 // Writes: a sequence is emitted only if the output stays BELOW n bytes with it; otherwise the block is given up as
@@ -353,9 +361,20 @@ __global__ __launch_bounds__(64) void frame_lz4_block_kernel(const LzBlock* __re
     const bool active = pos <= mflimit;
     const uint32_t v = active ? load32(src + pos) : 0u;
     const uint32_t h = (v * 2654435761u) >> (32 - HASH_LOG);
-    const int32_t cand = active ? (int32_t)table[h] : 0;
-    const bool hit = active && cand < pos && load32(src + cand) == v;
-    const uint64_t hits = __ballot(hit);
+    int32_t cand = active ? (int32_t)table[h] : 0;
+    bool hit = active && cand < pos && load32(src + cand) == v;
+    uint64_t hits = __ballot(hit);
+    if (!hits && ip + 64 > mflimit) {  // the block's last window: nearest earlier lane with the same 4 bytes
+      const int live = mflimit - ip + 1;  // its active lanes, 1 .. 64: the same for the whole wave
+      for (int d = 1; d < live; ++d) {
+        const uint32_t w = __shfl_up(v, d);
+        if (!hit && active && lane >= d && w == v) {
+          hit = true;
+          cand = pos - d;
+        }
+      }
+      hits = __ballot(hit);
+    }
     const int f = hits ? __ffsll((long long)hits) - 1 : 63;
     if (active && lane <= f) table[h] = (uint16_t)pos;
     __syncthreads();  // one wave: orders this window's inserts before the next window's reads

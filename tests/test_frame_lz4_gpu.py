@@ -10,16 +10,13 @@ import uuid
 import numpy as np
 import pytest
 
-import kafka_wire as kw
+from lz4_blockgen import BLOCK, check_against_uncompressed, walk_batches, walk_frame
 
 pytestmark = pytest.mark.gpu
 
 pa = pytest.importorskip("pyarrow")  # liblz4 as Apache Arrow bundles it: the pin every test here rests on
 if not pa.Codec.is_available("lz4"):
     pytest.skip("this pyarrow build has no LZ4 frame codec", allow_module_level=True)
-
-FRAME_HEAD = bytes([0x04, 0x22, 0x4D, 0x18, 0x60, 0x40, 0x82])
-BLOCK = 65536
 
 
 # ---- inputs ---------------------------------------------------------------------------------------------------------
@@ -102,110 +99,6 @@ def device_frames(framer, inp, ts):
     t = [torch.from_numpy(a).to(dev) for a in inp]
     torch.cuda.synchronize(dev)
     return {p: bytes(v) for p, v in framer.frame(*t, timestamp_ms=ts).items()}
-
-
-# ---- test-side walkers ----------------------------------------------------------------------------------------------
-def walk_batches(data):
-    """[(61-byte header, records section)] of back-to-back RecordBatch v2 bytes."""
-    out, pos = [], 0
-    while pos < len(data):
-        assert len(data) - pos >= 61
-        (length,) = struct.unpack_from(">i", data, pos + 8)
-        assert length >= 49 and pos + 12 + length <= len(data)
-        out.append((data[pos:pos + 61], data[pos + 61:pos + 12 + length]))
-        pos += 12 + length
-    return out
-
-
-def walk_frame(frame):
-    """[(stored, block bytes)] of one LZ4 frame as kafka-clients writes it; its size words must tile it exactly."""
-    assert frame[:7] == FRAME_HEAD, frame[:7].hex()
-    assert frame[-4:] == b"\0\0\0\0"
-    blocks, pos = [], 7
-    while True:
-        (word,) = struct.unpack_from("<I", frame, pos)
-        pos += 4
-        if word == 0:
-            break
-        size = word & 0x7FFFFFFF
-        assert 0 < size <= BLOCK and pos + size + 4 <= len(frame)
-        blocks.append((bool(word >> 31), frame[pos:pos + size]))
-        pos += size
-    assert pos == len(frame)
-    return blocks
-
-
-def walk_block(b):
-    """One compressed LZ4 block: (decoded size, [(start, length) of every match], literals of the last sequence); the
-    offsets are checked on the way."""
-    i = out = 0
-    matches = []
-    while True:
-        tok = b[i]; i += 1
-        lit = tok >> 4
-        if lit == 15:
-            while True:
-                x = b[i]; i += 1
-                lit += x
-                if x != 255:
-                    break
-        i += lit
-        out += lit
-        assert i <= len(b)
-        if i == len(b):
-            assert tok & 15 == 0  # the last sequence is literals only
-            return out, matches, lit
-        off = b[i] | b[i + 1] << 8
-        i += 2
-        assert 1 <= off <= 65535 and off <= out, (off, out)  # never before the block's start: blocks are independent
-        ml = tok & 15
-        if ml == 15:
-            while True:
-                x = b[i]; i += 1
-                ml += x
-                if x != 255:
-                    break
-        ml += 4
-        matches.append((out, ml))
-        out += ml
-
-
-def lz4_decompress(frame, size):
-    return pa.Codec("lz4").decompress(frame, decompressed_size=size).to_pybytes()
-
-
-def check_against_uncompressed(got, exp):
-    """Same batches, same records, block rules, for one publish: got = device LZ4 output, exp = the host writer's uncompressed output.
-    Returns (compressed blocks, stored blocks) seen."""
-    assert sorted(got) == sorted(exp)
-    n_comp = n_stored = 0
-    for p in exp:
-        gb, eb = walk_batches(got[p]), walk_batches(exp[p])
-        assert len(gb) == len(eb), (p, len(gb), len(eb))
-        pos = 0
-        for (gh, frame), (eh, records) in zip(gb, eb):
-            assert gh[0:8] == eh[0:8] and gh[12:17] == eh[12:17] and gh[23:61] == eh[23:61]  # all but batchLength, crc, attributes
-            assert struct.unpack(">h", gh[21:23])[0] == 3
-            assert struct.unpack(">i", gh[8:12])[0] == 49 + len(frame)
-            batch = got[p][pos:pos + 61 + len(frame)]
-            assert struct.unpack(">I", gh[17:21])[0] == kw.crc32c(batch[21:])
-            pos += len(batch)
-            blocks = walk_frame(frame)
-            assert len(blocks) == (len(records) + BLOCK - 1) // BLOCK
-            for k, (stored, body) in enumerate(blocks):
-                want = BLOCK if k < len(blocks) - 1 else len(records) - BLOCK * (len(blocks) - 1)
-                if stored:
-                    assert len(body) == want
-                    n_stored += 1
-                    continue
-                n_comp += 1
-                size, matches, last_lit = walk_block(body)
-                assert size == want
-                assert len(body) < size               # a block that does not shrink is stored
-                assert last_lit >= 5                  # the last 5 bytes are literals
-                assert all(start <= size - 12 for start, _ in matches)  # no match starts within the last 12 bytes
-            assert lz4_decompress(frame, len(records)) == records  # liblz4 is the pin
-    return n_comp, n_stored
 
 
 # ---- 1, 2: same batches, same records, block rules ------------------------------------------------------------------
