@@ -53,7 +53,9 @@ extern "C" {
 #define SURGE_E_NOMEM       (-4) /* host or device allocation failed                            */
 #define SURGE_E_UNSUPPORTED (-5) /* schema / algorithm not supported by this build              */
 #define SURGE_E_RANGE       (-6) /* aggregate index out of range                                */
-/* (-7 is SURGE_E_CORRUPT of surge_ingest.h)                                                        */
+#ifndef SURGE_E_CORRUPT
+#define SURGE_E_CORRUPT (-7)     /* bytes that are not what they should be (shared with surge_ingest.h)  */
+#endif
 #define SURGE_E_COMM        (-8) /* RCCL not loadable / a collective call failed                    */
 
 /* ---- fixed-width layouts (little-endian) ----------------------------------
@@ -489,6 +491,66 @@ int32_t surge_replay_encode_json(surge_replay_handle* h, const surge_json_templa
 int32_t surge_replay_encode_protobuf_state(surge_replay_handle* h, const surge_json_template* payload_tmpl,
                                            const uint8_t* d_keys_utf8, const int64_t* d_key_off, uint8_t* d_out,
                                            int64_t out_capacity, int64_t* d_out_off, int64_t* total_bytes_out);
+
+/* ---- serialized state, read back ------------------------------------------------------------------
+ * The inverse of the encoders above: state-topic record VALUES (the compact play-json text a surge_json_template
+ * describes, fields in case-class order) -> fixed 64-byte states, for a store that resumes from the compacted state
+ * topic (SurgeStateStoreConsumer.scala:57-76; records written by SurgeModel.scala:57-65) instead of replaying every
+ * event.  The template's parts are matched in order: LITERAL bytes exactly; KEY a JSON string whose unescaped bytes
+ * must be the aggregate's id when a key table is given; STR a JSON string that is validated and whose still-escaped
+ * span is reported; I32 / U32 / I64 the integer rule of surge_event_json_decode (-?[0-9]+, no fraction or exponent)
+ * with a value outside the field's range REPORTED, never wrapped; F64 any JSON number, correctly rounded
+ * (surge_parse_f64_json's algorithm).  String escapes: \" \\ \/ \b \f \n \r \t and \uXXXX outside the surrogate range.
+ * Nothing may follow the last part.  Bytes of the state the template does not name are zero; flags becomes
+ * SURGE_STATE_PRESENT.  NOT restored, because the text does not carry them: fields the template does not name,
+ * SURGE_STATE_POISONED (a poisoned aggregate is never written), and the sign of -0.0 (written as 0, read as +0.0). */
+#define SURGE_STATE_DECODE_OK           0
+#define SURGE_STATE_DECODE_LITERAL      1 /* a literal of the template does not match (or the text ends inside it)  */
+#define SURGE_STATE_DECODE_STRING       2 /* no opening quote, a raw control character, or the text ends in a string */
+#define SURGE_STATE_DECODE_ESCAPE       3 /* an escape that is none of the accepted ones                              */
+#define SURGE_STATE_DECODE_KEY_MISMATCH 4 /* the KEY string is not this aggregate's id                                */
+#define SURGE_STATE_DECODE_INT          5 /* not an integer literal                                                   */
+#define SURGE_STATE_DECODE_RANGE        6 /* an integer outside the field's range                                     */
+#define SURGE_STATE_DECODE_NUMBER       7 /* not a JSON number                                                        */
+#define SURGE_STATE_DECODE_TRAILING     8 /* bytes behind the last part                                               */
+#define SURGE_STATE_DECODE_AMBIGUOUS    9 /* device only, transient: a Double the fast algorithm cannot decide        */
+#define SURGE_STATE_DECODE_SURROGATE   10 /* a \uD800 .. \uDFFF escape                                                */
+#define SURGE_STATE_DECODE_SKIPPED    255 /* d_status_out only: a later record names the same aggregate; not parsed   */
+
+/* One value on the host (thread-safe; needs no device): 0 or a SURGE_STATE_DECODE_* status (> 0), SURGE_E_INVALID for a
+ * NULL argument or a template that is not consistent.  key_len = -1: the id is not compared.  state64_out is written
+ * only when the result is 0.  str_span_out (nullable): 2 x SURGE_JSON_STRING_COLUMNS entries, {offset into value, length}
+ * of each STR column's still-escaped bytes.  A Double the fast algorithm cannot decide is settled here with strtod, as
+ * surge_parse_f64_json does. */
+int32_t surge_decode_json_state(const surge_json_template* tmpl, const uint8_t* value, int64_t len, const uint8_t* key,
+                                int64_t key_len, void* state64_out, int64_t* str_span_out);
+
+/* n_records values on the device, in offset order: record r's text is d_values[d_value_off[r] .. d_value_off[r+1]) and
+ * names aggregate d_agg_idx[r] (d_agg_idx NULL: record r is aggregate r, n_records <= n_agg).  Per aggregate the LAST
+ * record that names it wins, as a KTable restore applies them: an empty value is a tombstone — the row becomes the
+ * canonical None (64 zero bytes); a value that decodes writes the row; a value that does not leaves the row untouched
+ * and is counted.  Rows no record names are untouched; records that lose are never parsed (status SKIPPED).
+ * d_keys_utf8 / d_key_off (n_agg + 1 entries; both NULL: no comparison): the ids the KEY strings must equal.
+ * d_states64: n_agg rows of 64 bytes, 16-byte aligned (the handle's own resident state, surge_replay_device_state, or
+ * any other buffer).  d_status_out (nullable): n_records bytes.  d_str_span_out (nullable): per record
+ * 2 x SURGE_JSON_STRING_COLUMNS int64 as above, defined where the status is 0.
+ * counts_out = {rows written, tombstones, winners refused, Doubles re-parsed on the host}.  The rare Double the device
+ * cannot decide is copied back, parsed by surge_decode_json_state and patched in before the call returns.
+ * Returns SURGE_E_CORRUPT after decoding everything else when a winner was refused (last_error: how many, and the first
+ * such record); SURGE_E_INVALID, with nothing written, when a d_agg_idx entry is outside [0, n_agg).  The work is
+ * enqueued on the handle's stream; the call returns when it is done.  ABI v1 handles (a v2 slot schema keeps its
+ * presence word elsewhere: SURGE_E_UNSUPPORTED). */
+int32_t surge_replay_decode_json_states(surge_replay_handle* h, const surge_json_template* tmpl, const uint8_t* d_values,
+                                        const int64_t* d_value_off, int64_t n_records, const uint8_t* d_keys_utf8,
+                                        const int64_t* d_key_off, const int64_t* d_agg_idx, int64_t n_agg, void* d_states64,
+                                        uint8_t* d_status_out, int64_t* d_str_span_out, int64_t counts_out[4]);
+
+/* What the bytes the template does NOT name hold in a row surge_replay_decode_json_states writes: state64's (NULL: zeros,
+ * the default).  The named fields and the flags word always come from the text.  A store that resumes from the state topic
+ * passes its schema's default_state: a fold materialises an aggregate from those defaults (min_arg / max_arg are not zero),
+ * so only then does a restored row equal, byte for byte, the row a fold of the aggregate's events produces — as the host
+ * path's state_to_fixed does.  Tombstones stay 64 zero bytes. */
+int32_t surge_replay_set_decode_base(surge_replay_handle* h, const void* state64);
 
 /* ---- snapshot publishing (SURVEY §8f N2 x N3) ---------------------------------------------------------------
  * What the state topic needs after a replay / a run of micro-batches, relative to the last COMMITTED snapshot of this

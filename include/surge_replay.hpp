@@ -16,6 +16,7 @@
 #ifndef SURGE_REPLAY_HPP
 #define SURGE_REPLAY_HPP
 
+#include <array>
 #include <cstdint>
 #include <cstring>
 #include <map>
@@ -198,6 +199,18 @@ class AggregateStateStore {
       throw AggregateInitializationException("replay of aggregate " + aggregateId + " hit an event whose handler throws");
     if (!present) return std::nullopt;
     return model_->stateFromFixed(aggregateId, st);
+  }
+
+  // Serialized state values on the device -> d_states64 (surge_replay_decode_json_states: last record per aggregate wins,
+  // an empty value deletes; arguments as in surge_replay.h).  Returns {rows written, tombstones, refused, re-parsed};
+  // throws when the call fails — SURGE_E_CORRUPT after everything else was decoded when a winner was refused.
+  std::array<int64_t, 4> decodeJsonStates(const surge_json_template& tmpl, const uint8_t* d_values, const int64_t* d_value_off, int64_t n_records,
+                                          const uint8_t* d_keys_utf8, const int64_t* d_key_off, const int64_t* d_agg_idx, int64_t n_agg,
+                                          void* d_states64, uint8_t* d_status_out = nullptr, int64_t* d_str_span_out = nullptr) {
+    std::array<int64_t, 4> counts{};
+    check(surge_replay_decode_json_states(h_, &tmpl, d_values, d_value_off, n_records, d_keys_utf8, d_key_off, d_agg_idx, n_agg, d_states64,
+                                          d_status_out, d_str_span_out, counts.data()));
+    return counts;
   }
 
   surge_replay_handle* handle() const { return h_; }

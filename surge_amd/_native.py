@@ -69,6 +69,8 @@ EXPORTS = (
     "surge_format_f64_json_many",
     "surge_replay_encode_json",
     "surge_replay_encode_protobuf_state",
+    "surge_replay_decode_json_states",
+    "surge_replay_set_decode_base",
     "surge_replay_pack_states",
     "surge_replay_unpack_states",
     "surge_replay_partition_hash",
@@ -174,6 +176,9 @@ SNAPSHOT_EXPORTS = (
     "surge_device_framer_next_offsets",
     "surge_device_framer_uncompressed_bytes",
 )
+
+#: the host half of the state decoder (declared in ``include/surge_replay.h``; needs no handle and no device)
+STATE_EXPORTS = ("surge_decode_json_state",)
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -307,6 +312,9 @@ def load() -> ctypes.CDLL:
         "surge_format_f64_json_many": ([vp, i64, vp, i64, vp], i64),
         "surge_replay_encode_json": ([vp, vp, vp, vp, vp, i64, vp, ctypes.POINTER(i64)], i32),
         "surge_replay_encode_protobuf_state": ([vp, vp, vp, vp, vp, i64, vp, ctypes.POINTER(i64)], i32),
+        "surge_replay_decode_json_states": ([vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, ctypes.POINTER(i64 * 4)], i32),
+        "surge_replay_set_decode_base": ([vp, vp], i32),
+        "surge_decode_json_state": ([vp, vp, i64, vp, i64, vp, vp], i32),
         "surge_replay_pack_states": ([vp, vp, i64, vp, vp], i32),
         "surge_replay_unpack_states": ([vp, vp, i64, vp, vp], i32),
         "surge_replay_partition_hash": ([vp, vp, i64, i32, vp], i32),
@@ -409,7 +417,7 @@ def load() -> ctypes.CDLL:
         "surge_device_framer_next_offsets": ([vp, vp], i32),
         "surge_device_framer_uncompressed_bytes": ([vp], i64),
     })
-    for name in EXPORTS + INGEST_EXPORTS + SNAPSHOT_EXPORTS:
+    for name in EXPORTS + INGEST_EXPORTS + SNAPSHOT_EXPORTS + STATE_EXPORTS:
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -14,6 +14,7 @@
 
 #include "replay_internal.h"
 #include "f64_text.h"
+#include "state_parse.h"
 
 using namespace surge;
 
@@ -155,6 +156,8 @@ struct surge_replay_handle {
   const uint8_t* encode_filter = nullptr;  // surge_replay_set_encode_filter
   JsonSide json_side{};                  // Double-text tables (device copy, made on first use), side string columns
   DevBuf f64_tables, nan_count;
+  alignas(16) uint8_t decode_base[64] = {};       // surge_replay_set_decode_base: what a decoded row's unnamed bytes hold
+  DevBuf sd_ptab, sd_counts, sd_last, sd_status;  // surge_replay_decode_json_states: parse table, counters, last record per aggregate, statuses
 
   CommState* comm = nullptr;  // the snapshot exchange (comm.hip), created by surge_replay_comm_init
   DevBuf gathered[2];         // handle-owned output of allgather_snapshot(d_out = NULL), per slot
@@ -625,7 +628,7 @@ int32_t surge_replay_destroy(surge_replay_handle* h) {
   h->host_flags = nullptr;
   h->cidx.release();
   h->tidx.release();
-  DevBuf* bufs[] = {&h->gb_temp, &h->gb_u32, &h->gb_flags, &h->gb_agg_idx, &h->gb_events, &h->published, &h->gathered[0], &h->gathered[1], &h->f64_tables, &h->nan_count, &h->ix_arena, &h->ix_cnt, &h->stage_keys, &h->stage_events, &h->t_tiles, &h->t_gsub, &h->perm, &h->counter, &h->own_seg_off, &h->own_events, &h->own_init, &h->own_state, &h->d_analysis, &h->nz_off,
+  DevBuf* bufs[] = {&h->gb_temp, &h->gb_u32, &h->gb_flags, &h->gb_agg_idx, &h->gb_events, &h->published, &h->gathered[0], &h->gathered[1], &h->f64_tables, &h->nan_count, &h->sd_ptab, &h->sd_counts, &h->sd_last, &h->sd_status, &h->ix_arena, &h->ix_cnt, &h->stage_keys, &h->stage_events, &h->t_tiles, &h->t_gsub, &h->perm, &h->counter, &h->own_seg_off, &h->own_events, &h->own_init, &h->own_state, &h->d_analysis, &h->nz_off,
                     &h->nz_map, &h->block_counts, &h->plan, &h->batch_group_agg, &h->batch_group_off,
                     &h->batch_events, &h->poison_count, &h->gather_idx, &h->gather_out, &h->scan_totals};
   for (DevBuf* b : bufs) b->release();
@@ -1757,6 +1760,128 @@ int32_t surge_replay_encode_protobuf_state(surge_replay_handle* h, const surge_j
                                            const uint8_t* d_keys_utf8, const int64_t* d_key_off, uint8_t* d_out,
                                            int64_t out_capacity, int64_t* d_out_off, int64_t* total_bytes_out) {
   return encode_states(h, payload_tmpl, d_keys_utf8, d_key_off, d_out, out_capacity, d_out_off, total_bytes_out, 1u);
+}
+
+int32_t surge_replay_set_decode_base(surge_replay_handle* h, const void* state64) {
+  if (!h) return fail(nullptr, SURGE_E_INVALID, "handle is NULL");
+  if (state64) std::memcpy(h->decode_base, state64, 64); else std::memset(h->decode_base, 0, 64);
+  return SURGE_OK;
+}
+
+int32_t surge_replay_decode_json_states(surge_replay_handle* h, const surge_json_template* tmpl, const uint8_t* d_values,
+                                        const int64_t* d_value_off, int64_t n_records, const uint8_t* d_keys_utf8,
+                                        const int64_t* d_key_off, const int64_t* d_agg_idx, int64_t n_agg, void* d_states64,
+                                        uint8_t* d_status_out, int64_t* d_str_span_out, int64_t counts_out[4]) {
+  if (!h) return fail(nullptr, SURGE_E_INVALID, "handle is NULL");
+  if (h->v2) return fail(h, SURGE_E_UNSUPPORTED, "decode_json_states serves ABI v1 handles (a slot schema keeps its presence word elsewhere)");
+  if (const char* why = state_template_problem(tmpl)) return fail(h, SURGE_E_INVALID, why);
+  if (!counts_out) return fail(h, SURGE_E_INVALID, "counts_out is NULL");
+  counts_out[0] = counts_out[1] = counts_out[2] = counts_out[3] = 0;
+  if (n_records < 0 || n_agg < 0) return fail(h, SURGE_E_INVALID, "negative size");
+  if (!d_agg_idx && n_records > n_agg) return fail(h, SURGE_E_INVALID, "more records than aggregates and no d_agg_idx");
+  if ((d_keys_utf8 && !d_key_off)) return fail(h, SURGE_E_INVALID, "d_keys_utf8 without d_key_off");
+  if (n_records == 0) return SURGE_OK;
+  if (!d_value_off || !d_states64) return fail(h, SURGE_E_INVALID, "NULL argument");
+  if ((uintptr_t)d_states64 & 15u) return fail(h, SURGE_E_INVALID, "d_states64 is not 16-byte aligned");
+  DeviceGuard g(h->device);
+  if (!h->sd_ptab.ptr) {  // the Eisel-Lemire table of the Double parser: one 10.4 KB copy per handle
+    HIPCHK(h, h->sd_ptab.reserve(sizeof(F64ParseTable)));
+    HIPCHK(h, hipMemcpy(h->sd_ptab.ptr, f64_parse_table_host(), sizeof(F64ParseTable), hipMemcpyHostToDevice));
+  }
+  HIPCHK(h, h->sd_counts.reserve(SD_N_COUNTS * 8));
+  if (d_agg_idx) HIPCHK(h, h->sd_last.reserve_roomy((size_t)n_agg * 8));
+  if (!d_status_out) HIPCHK(h, h->sd_status.reserve_roomy((size_t)n_records));  // (the re-parse below finds its records by status)
+  StateDecodeParams p{};
+  p.values = d_values; p.value_off = d_value_off; p.n_records = n_records;
+  p.keys = d_keys_utf8; p.key_off = d_key_off;
+  p.agg_idx = d_agg_idx; p.last1 = (unsigned long long*)h->sd_last.ptr; p.n_agg = n_agg;
+  p.states = (uint4*)d_states64;
+  p.status = d_status_out ? d_status_out : (uint8_t*)h->sd_status.ptr;
+  p.spans = d_str_span_out;
+  p.ptab = (const F64ParseTable*)h->sd_ptab.ptr;
+  p.counts = (unsigned long long*)h->sd_counts.ptr;
+  // the base row, without the bytes the template names and the flags word: the kernel ORs it into the parsed row
+  alignas(16) uint8_t base[64];
+  std::memcpy(base, h->decode_base, 64);
+  std::memset(base + 36, 0, 4);
+  for (uint32_t i = 0; i < tmpl->n_parts; ++i) {
+    const uint32_t k = tmpl->part[i].kind;
+    if (k >= SURGE_JP_I32 && k <= SURGE_JP_F64) std::memset(base + tmpl->part[i].field_offset, 0, (k == SURGE_JP_I64 || k == SURGE_JP_F64) ? 8 : 4);
+  }
+  std::memcpy(p.base, base, 64);
+  // rows of the handle's own resident state change: what the host mirror holds is no longer the current fold epoch's
+  const uint4* s0 = (const uint4*)d_states64;
+  const bool resident = h->d_state && s0 < h->d_state + h->n_agg * 4 && h->d_state < s0 + n_agg * 4;
+  std::unique_lock<std::shared_mutex> lk(h->mu, std::defer_lock);
+  if (resident) lk.lock();
+  HIPCHK(h, launch_state_decode(*tmpl, p, h->stream));
+  unsigned long long c[SD_N_COUNTS] = {0};
+  HIPCHK(h, hipMemcpyAsync(c, p.counts, sizeof(c), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (c[SD_BAD_INDEX])
+    return fail(h, SURGE_E_INVALID, std::to_string(c[SD_BAD_INDEX]) + " d_agg_idx entr(y/ies) outside [0, n_agg): nothing was written");
+  if (resident) h->fold_epoch.fetch_add(1);
+  int64_t refused = (int64_t)c[SD_REFUSED], first_refused = refused ? (int64_t)c[SD_FIRST_REFUSED] : -1, written = (int64_t)c[SD_WRITTEN];
+  int32_t first_status = 0;
+  if (c[SD_AMBIGUOUS]) {
+    // the rare Double the Eisel-Lemire product cannot decide (or one of more than 19 digits): those records come back and
+    // go through the host export (strtod), as the device decoder of events hands its undecided records back
+    std::vector<uint8_t> status((size_t)n_records);
+    std::vector<int64_t> off((size_t)n_records + 1), agg;
+    HIPCHK(h, hipMemcpyAsync(status.data(), p.status, (size_t)n_records, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(off.data(), d_value_off, ((size_t)n_records + 1) * 8, hipMemcpyDeviceToHost, h->stream));
+    if (d_agg_idx) {
+      agg.resize((size_t)n_records);
+      HIPCHK(h, hipMemcpyAsync(agg.data(), d_agg_idx, (size_t)n_records * 8, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::vector<uint8_t> text, key;
+    for (int64_t r = 0; r < n_records; ++r) {
+      if (status[(size_t)r] != SURGE_STATE_DECODE_AMBIGUOUS) continue;
+      const int64_t a = d_agg_idx ? agg[(size_t)r] : r;
+      text.resize((size_t)(off[(size_t)r + 1] - off[(size_t)r]));
+      HIPCHK(h, hipMemcpyAsync(text.data(), d_values + off[(size_t)r], text.size(), hipMemcpyDeviceToHost, h->stream));
+      int64_t key_len = -1;
+      if (d_key_off) {
+        int64_t ko[2];
+        HIPCHK(h, hipMemcpyAsync(ko, d_key_off + a, 16, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        key_len = ko[1] - ko[0];
+        key.resize((size_t)key_len);
+        if (key_len > 0) HIPCHK(h, hipMemcpyAsync(key.data(), d_keys_utf8 + ko[0], (size_t)key_len, hipMemcpyDeviceToHost, h->stream));
+      }
+      HIPCHK(h, hipStreamSynchronize(h->stream));
+      alignas(16) uint8_t row[64];
+      int64_t span[2 * SURGE_JSON_STRING_COLUMNS];
+      const int32_t rc = surge_decode_json_state(tmpl, text.data(), (int64_t)text.size(), key.data(), key_len, row, span);
+      const uint8_t st = (uint8_t)(rc < 0 ? SURGE_STATE_DECODE_NUMBER : rc);
+      if (rc == SURGE_STATE_DECODE_OK) {
+        for (int b = 0; b < 64; ++b) row[b] |= base[b];
+        HIPCHK(h, hipMemcpyAsync((uint8_t*)d_states64 + a * 64, row, 64, hipMemcpyHostToDevice, h->stream));
+        if (d_str_span_out) HIPCHK(h, hipMemcpyAsync(d_str_span_out + r * (2 * SURGE_JSON_STRING_COLUMNS), span, sizeof(span), hipMemcpyHostToDevice, h->stream));
+        ++written;
+      } else {
+        ++refused;
+        if (first_refused < 0 || r < first_refused) first_refused = r;
+      }
+      HIPCHK(h, hipMemcpyAsync(p.status + r, &st, 1, hipMemcpyHostToDevice, h->stream));
+      HIPCHK(h, hipStreamSynchronize(h->stream));  // (row / span / st are this iteration's)
+    }
+  }
+  counts_out[0] = written;
+  counts_out[1] = (int64_t)c[SD_TOMBSTONES];
+  counts_out[2] = refused;
+  counts_out[3] = (int64_t)c[SD_AMBIGUOUS];
+  if (refused) {
+    uint8_t st = 0;
+    HIPCHK(h, hipMemcpyAsync(&st, p.status + first_refused, 1, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    first_status = st;
+    return fail(h, SURGE_E_CORRUPT, std::to_string(refused) + " state value(s) were refused (their rows are untouched), the first at record " +
+                                    std::to_string(first_refused) + " with status " + std::to_string(first_status) +
+                                    " (SURGE_STATE_DECODE_*); everything else was decoded");
+  }
+  return SURGE_OK;
 }
 
 int32_t surge_replay_snapshot_delta(surge_replay_handle* h, uint8_t* d_kind_out, int64_t* n_values_out, int64_t* n_tombstones_out,

@@ -110,6 +110,26 @@ struct JsonSide {
 hipError_t launch_json_encode(const surge_json_template& tmpl, const uint4* states, int64_t n, const uint8_t* keys,
                               const int64_t* key_off, int64_t* d_len_off, int64_t* d_totals, uint8_t* out, bool write_pass,
                               uint32_t envelope, const uint8_t* filter, const JsonSide& side, hipStream_t stream);
+// ---- state_decode.hip: serialized state values -> 64-byte states (surge_replay_decode_json_states) ------------------
+struct F64ParseTable;
+enum { SD_WRITTEN = 0, SD_TOMBSTONES = 1, SD_REFUSED = 2, SD_AMBIGUOUS = 3, SD_FIRST_REFUSED = 4, SD_BAD_INDEX = 5, SD_N_COUNTS = 6 };
+struct StateDecodeParams {
+  const uint8_t* values;        // record r's text: values[value_off[r] .. value_off[r + 1])
+  const int64_t* value_off;
+  int64_t n_records;
+  const uint8_t* keys;          // nullable pair: the ids the KEY strings must equal
+  const int64_t* key_off;
+  const int64_t* agg_idx;       // nullable: record r is aggregate r
+  unsigned long long* last1;    // agg_idx only: n_agg entries of scratch (1 + the last record that names the aggregate)
+  int64_t n_agg;
+  uint4* states;
+  uint4 base[4];                // ORed into every decoded row: zero wherever the template (or the flags word) writes
+  uint8_t* status;              // nullable
+  int64_t* spans;               // nullable
+  const F64ParseTable* ptab;    // device copy of the Eisel-Lemire table (f64_parse.h)
+  unsigned long long* counts;   // SD_N_COUNTS entries
+};
+hipError_t launch_state_decode(const surge_json_template& tmpl, const StateDecodeParams& p, hipStream_t stream);
 // kind[a] in SURGE_SNAP_*; d_counts: two u64 {values, tombstones}; commit: published := states where kind != SKIP
 hipError_t launch_snapshot_invalidate(uint4* published, int64_t n, const uint8_t* kind, hipStream_t stream);
 hipError_t launch_snapshot_commit(const uint4* states, uint4* published, int64_t n, const uint8_t* kind, hipStream_t stream);

@@ -1,0 +1,19 @@
+// state_decode_host.cpp — surge_decode_json_state: one serialized state value -> the fixed 64-byte state on the host, with
+// the parser the device kernel runs (state_parse.h).  Plain C++ (no HIP): point reads of a state-topic record, the
+// device decoder's re-parse of a Double it cannot decide, and the reference the device kernel is held to in the tests.
+#include <cstring>
+
+#include "state_parse.h"
+
+extern "C" int32_t surge_decode_json_state(const surge_json_template* tmpl, const uint8_t* value, int64_t len, const uint8_t* key,
+                                           int64_t key_len, void* state64_out, int64_t* str_span_out) {
+  if (!state64_out || len < 0 || (!value && len > 0) || (!key && key_len > 0)) return SURGE_E_INVALID;
+  if (surge::state_template_problem(tmpl)) return SURGE_E_INVALID;
+  alignas(16) uint8_t row[64];
+  int64_t span[2 * SURGE_JSON_STRING_COLUMNS] = {0};
+  const int rc = surge::state_parse_json<true>(*tmpl, value, len, key, key_len < 0 ? -1 : key_len, surge::f64_parse_table_host(), row, span);
+  if (rc != SURGE_STATE_DECODE_OK) return rc;
+  std::memcpy(state64_out, row, 64);
+  if (str_span_out) std::memcpy(str_span_out, span, sizeof(span));
+  return SURGE_STATE_DECODE_OK;
+}

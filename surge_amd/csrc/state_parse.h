@@ -1,0 +1,201 @@
+// state_parse.h — one serialized state value (the text the state encoders write, include/surge_replay.h) -> the fixed
+// 64-byte state, on the host and on the device (same code): the inverse of json_encode_kernel (state_kernels.hip).
+//
+// What is parsed: compact play-json, `Json.toJson(state).toString()` over a `Json.format` case-class format
+// (TestBoundedContext.scala:127-129, BankAccountSurgeModel.scala:26-28) — the fields in case-class order with nothing
+// between the tokens, exactly the text a surge_json_template describes.  The parser walks the template's parts in order;
+// anything else is refused with a status that names the part kind that did not match, never guessed at:
+//   LITERAL            the bytes must match
+//   KEY                a JSON string; with a key given, its unescaped bytes must be the aggregate's id
+//   STR                a JSON string; validated, its still-escaped span (offset, length between the quotes) reported
+//   I32 / U32 / I64    -?[0-9]+ and nothing of a decimal after it (the event decoder's integer rule, event_decode.cpp),
+//                      inside the field's range — a value outside it is reported, never wrapped
+//   F64                f64_parse_json_number (f64_parse.h): correctly rounded, or AMBIGUOUS for the caller to settle
+// Strings: every byte below 0x20 must be escaped (Jackson writes them as \u00XX and refuses them raw); the escapes are
+// \" \\ \/ \b \f \n \r \t and \uXXXX for a code point outside the surrogate range, unescaped to UTF-8.  Bytes from 0x80
+// on are taken as they are (the id is compared byte for byte).
+// The parser never reads at or beyond value + len, and writes nothing but row[0 .. 64) and span[0 .. 8).
+#pragma once
+#include <stdint.h>
+
+#include "../../include/surge_replay.h"
+#include "f64_parse.h"
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+extern "C" int32_t surge_parse_f64_json(const uint8_t* text, int64_t len, uint64_t* bits_out);  // f64_text.cpp: Eisel-Lemire, strtod where that cannot decide
+#endif
+
+namespace surge {
+
+// the template's own consistency (what the encoders check before they launch); 0 = usable, else a message
+inline const char* state_template_problem(const surge_json_template* t) {
+  if (!t) return "template is NULL";
+  if (t->n_parts == 0 || t->n_parts > SURGE_JSON_MAX_PARTS) return "template.n_parts out of range";
+  for (uint32_t i = 0; i < t->n_parts; ++i) {
+    const auto& pt = t->part[i];
+    if (pt.kind > SURGE_JP_STR) return "unknown template part kind";
+    if (pt.kind == SURGE_JP_LITERAL && (pt.lit_off > 256 || pt.lit_len > 256 - pt.lit_off)) return "literal out of range";
+    if (pt.kind == SURGE_JP_STR) {
+      if (pt.field_offset >= SURGE_JSON_STRING_COLUMNS) return "SURGE_JP_STR names a string column out of range";
+    } else if (pt.kind >= SURGE_JP_I32) {
+      const uint32_t width = (pt.kind == SURGE_JP_I64 || pt.kind == SURGE_JP_F64) ? 8u : 4u;
+      if (pt.field_offset > 64u - width || pt.field_offset % width) return "field outside the 64-byte state or misaligned";
+      if (pt.field_offset < 40u && pt.field_offset + width > 36u) return "field overlaps the flags word";
+    }
+  }
+  return nullptr;
+}
+
+SURGE_HD int sp_hex(uint8_t c) {
+  if (c >= '0' && c <= '9') return c - '0';
+  if (c >= 'a' && c <= 'f') return c - 'a' + 10;
+  if (c >= 'A' && c <= 'F') return c - 'A' + 10;
+  return -1;
+}
+
+// A JSON string whose opening quote is v[*pos].  key_len >= 0: the unescaped bytes must equal key[0 .. key_len).
+// *pos ends behind the closing quote; the raw span between the quotes goes to *raw_off / *raw_len.
+SURGE_HD int sp_string(const uint8_t* v, int64_t len, int64_t* pos, const uint8_t* key, int64_t key_len, int64_t* raw_off,
+                       int64_t* raw_len) {
+  int64_t i = *pos;
+  if (i >= len || v[i] != '"') return SURGE_STATE_DECODE_STRING;
+  ++i;
+  *raw_off = i;
+  int64_t k = 0;       // unescaped bytes so far
+  bool same = true;    // ... and they equal the key's
+  while (true) {
+    if (i >= len) return SURGE_STATE_DECODE_STRING;  // unterminated
+    uint32_t c = v[i++];
+    if (c == '"') break;
+    if (c < 0x20u) return SURGE_STATE_DECODE_STRING;  // a control character is always escaped
+    uint32_t n_out = 1;
+    if (c == '\\') {
+      if (i >= len) return SURGE_STATE_DECODE_STRING;
+      const uint8_t e = v[i++];
+      switch (e) {
+        case '"': c = '"'; break;
+        case '\\': c = '\\'; break;
+        case '/': c = '/'; break;
+        case 'b': c = '\b'; break;
+        case 'f': c = '\f'; break;
+        case 'n': c = '\n'; break;
+        case 'r': c = '\r'; break;
+        case 't': c = '\t'; break;
+        case 'u': {
+          if (len - i < 4) return SURGE_STATE_DECODE_STRING;  // the text ends inside the escape
+          c = 0;
+          for (int d = 0; d < 4; ++d) {
+            const int h = sp_hex(v[i + d]);
+            if (h < 0) return SURGE_STATE_DECODE_ESCAPE;
+            c = (c << 4) | (uint32_t)h;
+          }
+          i += 4;
+          if (c >= 0xD800u && c <= 0xDFFFu) return SURGE_STATE_DECODE_SURROGATE;
+          n_out = c < 0x80u ? 1u : c < 0x800u ? 2u : 3u;
+          break;
+        }
+        default: return SURGE_STATE_DECODE_ESCAPE;
+      }
+    }
+    if (key_len >= 0) {
+      // the code point as UTF-8, byte by byte against the key
+      for (uint32_t b = 0; b < n_out; ++b) {
+        uint32_t byte;
+        if (n_out == 1) byte = c;
+        else if (n_out == 2) byte = b == 0 ? (0xC0u | (c >> 6)) : (0x80u | (c & 0x3Fu));
+        else byte = b == 0 ? (0xE0u | (c >> 12)) : b == 1 ? (0x80u | ((c >> 6) & 0x3Fu)) : (0x80u | (c & 0x3Fu));
+        same = same && k < key_len && key[k] == (uint8_t)byte;
+        ++k;
+      }
+    }
+  }
+  *raw_len = i - 1 - *raw_off;
+  *pos = i;
+  if (key_len >= 0 && !(same && k == key_len)) return SURGE_STATE_DECODE_KEY_MISMATCH;
+  return SURGE_STATE_DECODE_OK;
+}
+
+// -?[0-9]+ not followed by a fraction, an exponent or a sign -> magnitude and sign; `over`: beyond 64 bits
+SURGE_HD int sp_integer(const uint8_t* v, int64_t len, int64_t* pos, bool* neg, uint64_t* mag, bool* over) {
+  int64_t i = *pos;
+  *neg = false;
+  if (i < len && v[i] == '-') { *neg = true; ++i; }
+  uint64_t m = 0;
+  bool any = false, ov = false;
+  while (i < len && v[i] >= '0' && v[i] <= '9') {
+    const uint64_t d = (uint64_t)(v[i] - '0');
+    if (m > (0xFFFFFFFFFFFFFFFFull - d) / 10ull) ov = true; else m = m * 10ull + d;
+    any = true;
+    ++i;
+  }
+  if (!any) return SURGE_STATE_DECODE_INT;
+  if (i < len && (v[i] == '.' || v[i] == 'e' || v[i] == 'E' || v[i] == '+' || v[i] == '-')) return SURGE_STATE_DECODE_INT;
+  *mag = m;
+  *over = ov;
+  *pos = i;
+  return SURGE_STATE_DECODE_OK;
+}
+
+// One value -> row[0 .. 64) (16-byte aligned; complete only when the result is OK) and, for STR parts, span[2 c] /
+// span[2 c + 1] = offset / length of column c's still-escaped bytes (span nullable).  key_len < 0: the id is not compared.
+// RESOLVE (host only): a Double the fast algorithm cannot decide is settled by surge_parse_f64_json's strtod path; without
+// it the value is reported as SURGE_STATE_DECODE_AMBIGUOUS.
+template <bool RESOLVE>
+SURGE_HD int state_parse_json(const surge_json_template& t, const uint8_t* v, int64_t len, const uint8_t* key, int64_t key_len,
+                              const F64ParseTable* tb, uint8_t* row, int64_t* span) {
+  uint64_t* row8 = (uint64_t*)row;
+  for (int q = 0; q < 8; ++q) row8[q] = 0;
+  int64_t i = 0;
+  for (uint32_t p = 0; p < t.n_parts; ++p) {
+    const uint32_t kind = t.part[p].kind, off = t.part[p].field_offset;
+    if (kind == SURGE_JP_LITERAL) {
+      const uint32_t lo = t.part[p].lit_off, ll = t.part[p].lit_len;
+      if (len - i < (int64_t)ll) return SURGE_STATE_DECODE_LITERAL;
+      for (uint32_t b = 0; b < ll; ++b)
+        if (v[i + b] != t.literals[lo + b]) return SURGE_STATE_DECODE_LITERAL;
+      i += ll;
+    } else if (kind == SURGE_JP_KEY || kind == SURGE_JP_STR) {
+      int64_t ro = 0, rl = 0;
+      const int rc = sp_string(v, len, &i, key, kind == SURGE_JP_KEY ? key_len : -1, &ro, &rl);
+      if (rc != SURGE_STATE_DECODE_OK) return rc;
+      if (kind == SURGE_JP_STR && span && off < SURGE_JSON_STRING_COLUMNS) { span[2 * off] = ro; span[2 * off + 1] = rl; }
+    } else if (kind == SURGE_JP_F64) {
+      int64_t e = i;
+      while (e < len && e - i < 400 && ((v[e] >= '0' && v[e] <= '9') || v[e] == '-' || v[e] == '+' || v[e] == '.' || v[e] == 'e' || v[e] == 'E')) ++e;
+      if (e - i >= 400) return SURGE_STATE_DECODE_NUMBER;
+      uint64_t bits = 0;
+      const int rc = f64_parse_json_number(v + i, (int)(e - i), tb, &bits);
+      if (rc == F64_PARSE_MALFORMED) return SURGE_STATE_DECODE_NUMBER;
+      if (rc == F64_PARSE_AMBIGUOUS) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+        if (RESOLVE) {
+          if (surge_parse_f64_json(v + i, e - i, &bits) < 0) return SURGE_STATE_DECODE_NUMBER;
+        } else
+#endif
+          return SURGE_STATE_DECODE_AMBIGUOUS;
+      }
+      *(uint64_t*)(row + off) = bits;
+      i = e;
+    } else {
+      bool neg = false, over = false;
+      uint64_t mag = 0;
+      const int rc = sp_integer(v, len, &i, &neg, &mag, &over);
+      if (rc != SURGE_STATE_DECODE_OK) return rc;
+      if (kind == SURGE_JP_I32) {
+        if (over || mag > (neg ? 0x80000000ull : 0x7FFFFFFFull)) return SURGE_STATE_DECODE_RANGE;
+        *(uint32_t*)(row + off) = neg ? (uint32_t)0 - (uint32_t)mag : (uint32_t)mag;
+      } else if (kind == SURGE_JP_U32) {
+        if (over || mag > (neg ? 0ull : 0xFFFFFFFFull)) return SURGE_STATE_DECODE_RANGE;
+        *(uint32_t*)(row + off) = (uint32_t)mag;
+      } else {
+        if (over || mag > (neg ? 0x8000000000000000ull : 0x7FFFFFFFFFFFFFFFull)) return SURGE_STATE_DECODE_RANGE;
+        *(uint64_t*)(row + off) = neg ? (uint64_t)0 - mag : mag;
+      }
+    }
+  }
+  if (i != len) return SURGE_STATE_DECODE_TRAILING;
+  *(uint32_t*)(row + 36) = SURGE_STATE_PRESENT;
+  return SURGE_STATE_DECODE_OK;
+}
+
+}  // namespace surge

@@ -132,3 +132,78 @@ def encode_states(engine: ReplayEngine, template: JsonTemplate, d_keys_utf8, d_k
         msg = lib.surge_replay_last_error(engine._h)
         raise ReplayError(rc, msg.decode() if msg else "")
     raise RuntimeError("encode_states: unreachable")
+
+
+# ---- the way back: serialized state values -> fixed 64-byte states -----------------------------------------------------
+#: ``SURGE_STATE_DECODE_*`` (``include/surge_replay.h``)
+DECODE_STATUS = {0: "OK", 1: "LITERAL", 2: "STRING", 3: "ESCAPE", 4: "KEY_MISMATCH", 5: "INT", 6: "RANGE", 7: "NUMBER", 8: "TRAILING",
+                 9: "AMBIGUOUS", 10: "SURROGATE", 255: "SKIPPED"}
+DECODE_OK, DECODE_LITERAL, DECODE_STRING, DECODE_ESCAPE, DECODE_KEY_MISMATCH, DECODE_INT, DECODE_RANGE = 0, 1, 2, 3, 4, 5, 6
+DECODE_NUMBER, DECODE_TRAILING, DECODE_AMBIGUOUS, DECODE_SURROGATE, DECODE_SKIPPED = 7, 8, 9, 10, 255
+
+
+class DecodedStates(tuple):
+    """``(states, status, counts)`` of ``decode_states``; ``.spans`` holds the STR parts' raw spans, ``.refused`` the
+    message of the call when winners were refused (``None`` otherwise)."""
+
+    spans = None
+    refused = None
+
+
+def decode_state_host(template: JsonTemplate, value: bytes, key=None):
+    """One serialized state value on the host (``surge_decode_json_state``: the parser the device kernel runs).  Returns
+    ``(status, state, spans)``: a ``SURGE_STATE_DECODE_*`` status, the state (a one-element ``STATE_DTYPE`` array, zeros
+    unless the status is 0) and ``spans[c] = (offset, length)`` of STR column ``c``'s still-escaped bytes.  ``key``
+    (``str`` or UTF-8 ``bytes``): the id the KEY string must equal; ``None``: not compared."""
+    from .schema import STATE_DTYPE
+
+    t = template.to_c()
+    value = bytes(value)
+    kb = None if key is None else (key.encode("utf-8") if isinstance(key, str) else bytes(key))
+    state = np.zeros(1, dtype=STATE_DTYPE)
+    span = (ctypes.c_int64 * (2 * STRING_COLUMNS))()
+    rc = _native.load().surge_decode_json_state(ctypes.byref(t), value, len(value), kb, -1 if kb is None else len(kb),
+                                                state.ctypes.data_as(ctypes.c_void_p), span)
+    if rc < 0:
+        raise ValueError("surge_decode_json_state: bad argument or inconsistent template")
+    return rc, state, [(span[2 * c], span[2 * c + 1]) for c in range(STRING_COLUMNS)]
+
+
+def decode_states(engine: ReplayEngine, template: JsonTemplate, d_values, d_value_off, d_keys_utf8=None, d_key_off=None, d_agg_idx=None,
+                  out=None, want_spans: bool = False, raise_on_refused: bool = False):
+    """Decode state-topic record values on the device (``surge_replay_decode_json_states``): record ``r``'s text is
+    ``d_values[d_value_off[r]:d_value_off[r+1]]`` (empty = tombstone) and names aggregate ``d_agg_idx[r]`` (``None``: aggregate
+    ``r``); per aggregate the last record wins.  ``out``: the ``n_agg x 64`` byte CUDA tensor the rows go to (rows nothing
+    names, and rows whose winner does not decode, keep what they hold) — ``None``: a fresh all-None tensor of one row per
+    record (identity) or per key.  Returns ``(states, status, counts)``: the tensor, one ``SURGE_STATE_DECODE_*`` byte per
+    record (CUDA) and ``counts = (rows written, tombstones, winners refused, Doubles re-parsed on the host)``; ``.spans`` of
+    the result is the ``n_records x 4 x 2`` int64 CUDA tensor of STR spans when ``want_spans``.  Winners that do not decode
+    are reported in ``counts`` (and ``.refused``), or raised as ``ReplayError`` (CORRUPT) with ``raise_on_refused``; any
+    other failure raises."""
+    import torch
+
+    lib = _native.load()
+    n = int(d_value_off.numel()) - 1
+    dev = d_value_off.device
+    if out is None:
+        n_agg = n if d_agg_idx is None else (int(d_key_off.numel()) - 1 if d_key_off is not None else None)
+        if n_agg is None:
+            raise ValueError("decode_states: with d_agg_idx and no key table, pass `out` (it defines the aggregate count)")
+        out = torch.zeros((n_agg, 64), dtype=torch.uint8, device=dev)
+    n_agg = int(out.numel()) // 64
+    status = torch.empty(n, dtype=torch.uint8, device=dev)
+    spans = torch.zeros((n, STRING_COLUMNS, 2), dtype=torch.int64, device=dev) if want_spans else None
+    counts = (ctypes.c_int64 * 4)()
+    t = template.to_c()
+    ptr = lambda x: ctypes.c_void_p(x.data_ptr()) if x is not None and x.numel() else None  # noqa: E731
+    rc = lib.surge_replay_decode_json_states(
+        engine._h, ctypes.byref(t), ptr(d_values), ctypes.c_void_p(d_value_off.data_ptr()), n, ptr(d_keys_utf8),
+        ctypes.c_void_p(d_key_off.data_ptr()) if d_key_off is not None else None, ptr(d_agg_idx), n_agg, ctypes.c_void_p(out.data_ptr()),
+        ptr(status), ptr(spans), ctypes.byref(counts))
+    res = DecodedStates((out, status, tuple(int(c) for c in counts)))
+    res.spans = spans
+    if rc == -7 and not raise_on_refused:  # SURGE_E_CORRUPT: everything else was decoded; counts[2] says how many were not
+        res.refused = (lib.surge_replay_last_error(engine._h) or b"").decode()
+        return res
+    engine._check(rc)
+    return res

@@ -262,6 +262,65 @@ class GpuReplayStateStore:
         self._restored = True
         return counters
 
+    def restore_from_state_records(self, records, events_tail: Sequence = (), template=None) -> dict:
+        """Resume from the compacted *state* topic instead of replaying every event — what the reference's restore does
+        (``SurgeStateStoreConsumer.scala:57-76``, records written by ``SurgeModel.scala:57-65``).  ``records``: ``(key,
+        value_or_None)`` pairs or ``snapshot.StateRecord`` objects in offset order; per key the last record wins and
+        ``None`` deletes.  The values are decoded on the device (``encode.decode_states``; ``template``: the model's
+        serialized state, default ``JsonTemplate.counter()``) straight into the engine's resident state, the loaded states
+        become the snapshot baseline (a publish right after the load has nothing to say), then ``events_tail`` — the
+        events behind the snapshot — is folded on top.  Fields the template does not name take the algebra's defaults,
+        as ``state_to_fixed`` gives them on the ``restore(prior=...)`` path; the POISONED flag and the sign of ``-0.0``
+        are not in the text and are not restored.  A winning value that does not decode raises ``ReplayError`` (CORRUPT).
+        Returns the decoder's counts."""
+        import ctypes
+
+        import torch
+
+        from . import _native
+        from .encode import JsonTemplate, decode_states, key_table_utf8
+        from .schema import EVENT_DTYPE
+
+        template = template or JsonTemplate.counter()
+        agg_idx, values, lens = [], [], []
+        for rec in records:
+            key, value = (rec.key, rec.value) if hasattr(rec, "key") else rec
+            agg_idx.append(self.keys.intern(key))
+            value = b"" if value is None else bytes(value)
+            values.append(value)
+            lens.append(len(value))
+        n_agg, n_rec = len(self.keys), len(agg_idx)
+        eng, lib = self.engine, _native.load()
+        eng.load_csr(np.zeros(1, dtype=np.int64), np.zeros(0, dtype=EVENT_DTYPE))
+        eng.fold()  # no aggregate yet ...
+        eng.grow(n_agg)  # ... then every interned id, None
+        counts = (0, 0, 0, 0)
+        dev = torch.device("cuda", eng.device)
+        if n_rec:
+            off = np.zeros(n_rec + 1, dtype=np.int64)
+            np.cumsum(lens, out=off[1:])
+            data, key_off = key_table_utf8(self.keys.keys)
+            to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+            d_values = to_dev(np.frombuffer(b"".join(values), dtype=np.uint8).copy()) if off[-1] else torch.zeros(0, dtype=torch.uint8, device=dev)
+            defaults = self.model.event_algebra().to_c().default_state
+            eng._check(lib.surge_replay_set_decode_base(eng._h, ctypes.byref(defaults)))
+            try:
+                res = decode_states(eng, template, d_values, to_dev(off), to_dev(data), to_dev(key_off), to_dev(np.asarray(agg_idx, dtype=np.int64)),
+                                    out=eng.device_state(), raise_on_refused=True)
+            finally:
+                eng._check(lib.surge_replay_set_decode_base(eng._h, None))
+            counts = res[2]
+        if n_agg:
+            d_kind = torch.zeros(n_agg, dtype=torch.uint8, device=dev)
+            nv, nt = ctypes.c_int64(), ctypes.c_int64()
+            eng._check(lib.surge_replay_snapshot_delta(eng._h, ctypes.c_void_p(d_kind.data_ptr()), ctypes.byref(nv), ctypes.byref(nt), 1))
+        self._restored = True
+        if len(events_tail):
+            self.apply_events(events_tail)  # grows for new ids, group-by + fold on the device, refreshes the mirror
+        else:
+            eng.snapshot()
+        return {"rows_written": counts[0], "tombstones": counts[1], "refused": counts[2], "reparsed_on_host": counts[3]}
+
     def restore_log(self, log: EventLog, init_state: Optional[np.ndarray] = None, algo: int = ALGO_AUTO) -> None:
         self.keys = log.keys
         self.engine.load_csr(log.seg_off, log.events, init_state)
