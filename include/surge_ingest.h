@@ -230,6 +230,21 @@ typedef struct surge_device_decoder surge_device_decoder;
  * template with surge_event_json_decode's rules (Doubles correctly rounded on the device — f64_parse.h — the rare value
  * its fast path cannot decide is re-parsed on the host).  hip_stream: the stream the decoder works on (NULL = default). */
 int32_t surge_device_decoder_create(int32_t device_id, void* hip_stream, const surge_event_json_template* tmpl, surge_device_decoder** out);
+/* STATE MODE: a decoder for the compacted STATE topic (what SurgeStateStoreConsumer.scala:57-76 reads, records written by
+ * SurgeModel.scala:57-65).  Every other entry point works on it unchanged — push, push_async / push_parts_async,
+ * push_finish[_async], push_records, reserve, keys, key_table, counters, stats, clear — with these differences per record:
+ *   - the aggregate id is the WHOLE key (the state topic's key is the id itself; "a:b" and "a" are two ids);
+ *   - a null value is a TOMBSTONE and is delivered (value length 0); a null key fails the push; so does an empty, non-null
+ *     value under a non-empty key (writeState never writes one, and the loader could not tell it from a tombstone) —
+ *     SURGE_E_CORRUPT naming the record's offset, nothing of the push delivered, like every bad record;
+ *   - empty key AND empty value is still the producer's flush record (KafkaProducerActorImpl.scala:322-329 writes it on the
+ *     state topic): skipped and counted; record headers (stateHeaders) are skipped;
+ *   - no value is decoded: the delivered records' value bytes are gathered, in delivery order, into one device buffer behind
+ *     what earlier pushes delivered (a push's staged bytes are reused by the next push, so the values move);
+ *   - push_records: an EMPTY value is the tombstone (ConsumerRecord.value() == null: a JVM caller maps null to empty).
+ * The result is read with surge_device_decoder_state_result and handed over with surge_device_decoder_load_states;
+ * surge_device_decoder_result, surge_replay_append_decoded[_async] and surge_replay_stage_decoded return SURGE_E_STATE. */
+int32_t surge_device_decoder_create_states(int32_t device_id, void* hip_stream, surge_device_decoder** out);
 int32_t surge_device_decoder_destroy(surge_device_decoder* d);
 const char* surge_device_decoder_last_error(const surge_device_decoder* d);
 /* Decodes the sections (spans of `bytes`, a HOST buffer) and APPENDS their records to the device-resident result.  A
@@ -274,6 +289,12 @@ int32_t surge_device_decoder_push_records(surge_device_decoder* d, const uint8_t
 /* Everything appended since the last clear: device arrays of n_records entries (valid until the next push / clear). */
 int32_t surge_device_decoder_result(surge_device_decoder* d, int64_t* n_records, const int64_t** d_agg_idx, const void** d_events16,
                                     const int64_t** d_offsets, int64_t* n_keys);
+/* The same of a state decoder (SURGE_E_STATE on any other): record r names aggregate d_agg_idx[r], its value is
+ * d_values[d_value_off[r] .. d_value_off[r+1]) (empty: a tombstone), its Kafka offset d_offsets[r] (log compaction leaves
+ * gaps); d_value_off has n_records + 1 entries, d_value_off[0] = 0.  The values buffer ends at least 64 bytes behind its last
+ * value.  Valid until the next push_finish / clear / load_states. */
+int32_t surge_device_decoder_state_result(surge_device_decoder* d, int64_t* n_records, const int64_t** d_agg_idx, const uint8_t** d_values,
+                                          const int64_t** d_value_off, const int64_t** d_offsets, int64_t* n_keys);
 int32_t surge_device_decoder_clear(surge_device_decoder* d); /* drops the records, keeps the key table */
 /* Folds everything decoded since the last clear onto the replay handle's resident state and clears it: grows the
  * state for aggregate ids seen for the first time (surge_replay_grow), device group-by + fold
@@ -294,6 +315,22 @@ int32_t surge_replay_append_decoded_async(struct surge_replay_handle* h, surge_d
  * and the decoder is cleared.  No host wait: the hand-over is ordered by events exactly like append_decoded_async's.
  * When the topic ends: surge_replay_pack_staged(h, <the decoder's key count>) and one surge_replay_fold. */
 int32_t surge_replay_stage_decoded(struct surge_replay_handle* h, surge_device_decoder* d, int64_t* n_events_out, int64_t* n_keys_out);
+/* A state decoder's hand-over (SURGE_E_STATE on an events decoder): everything delivered since the last clear goes into the
+ * handle's resident state, as a KTable restore applies the records it is handed (SurgeStateStoreConsumer.scala:69).  The
+ * state grows for ids seen for the first time (as in surge_replay_append_decoded: the handle must hold a bound / restored
+ * state), the handle's stream waits (event) for the decoder's, and surge_replay_decode_json_states (surge_replay.h) runs over
+ * the decoder's own arrays WITH its key table — a value's KEY string must be the interned id — writing
+ * surge_replay_device_state: per aggregate the last record wins, a tombstone makes the row 64 zero bytes.  tmpl: the model's
+ * serialized state (struct surge_json_template).  counts_out: that decode's four counts for this call {rows written,
+ * tombstones, winners refused, Doubles re-parsed on the host}.
+ * The call returns when the rows are written, so the next push_finish may write the result arrays again (stage 1 of later
+ * pushes overlaps on its own streams all the while).  The decoder's records are cleared whether or not a winner was refused:
+ * then SURGE_E_CORRUPT is returned after everything else was loaded, and the message gives the TOPIC offset of the first
+ * refused record.  Keep-last ACROSS calls follows from calling in delivery order: a later call overwrites or zeroes what an
+ * earlier one wrote.  What the bytes the template does not name hold stays the caller's business
+ * (surge_replay_set_decode_base).  ABI v2 handles: SURGE_E_UNSUPPORTED (the decode's; nothing is cleared). */
+struct surge_json_template;
+int32_t surge_device_decoder_load_states(surge_device_decoder* d, struct surge_replay_handle* h, const struct surge_json_template* tmpl, int64_t counts_out[4]);
 /* The key table (aggregate ids in first-delivered order): to the host (NULL / NULL = size query), or where it lives on
  * the device (n_keys + 1 offsets; what the GPU state encoders and K4 take). */
 int32_t surge_device_decoder_keys(surge_device_decoder* d, uint8_t* utf8_out, int64_t utf8_capacity, int64_t* key_off_out, int64_t* n_keys_out,

@@ -123,6 +123,7 @@ INGEST_EXPORTS = (
     "surge_ingest_set_allocator",
     "surge_ingest_use_pinned_arena",
     "surge_device_decoder_create",
+    "surge_device_decoder_create_states",
     "surge_device_decoder_destroy",
     "surge_device_decoder_last_error",
     "surge_device_decoder_push",
@@ -134,7 +135,9 @@ INGEST_EXPORTS = (
     "surge_device_decoder_pending",
     "surge_device_decoder_reserve",
     "surge_device_decoder_result",
+    "surge_device_decoder_state_result",
     "surge_device_decoder_clear",
+    "surge_device_decoder_load_states",
     "surge_replay_append_decoded",
     "surge_replay_append_decoded_async",
     "surge_replay_stage_decoded",
@@ -366,6 +369,7 @@ def load() -> ctypes.CDLL:
         "surge_ingest_set_allocator": ([vp, vp, vp], i32),
         "surge_ingest_use_pinned_arena": ([vp], i32),
         "surge_device_decoder_create": ([i32, vp, vp, ctypes.POINTER(vp)], i32),
+        "surge_device_decoder_create_states": ([i32, vp, ctypes.POINTER(vp)], i32),
         "surge_device_decoder_destroy": ([vp], i32),
         "surge_device_decoder_last_error": ([vp], ctypes.c_char_p),
         "surge_device_decoder_push": ([vp, vp, vp, i64], i32),
@@ -377,7 +381,10 @@ def load() -> ctypes.CDLL:
         "surge_device_decoder_pending": ([vp], i32),
         "surge_device_decoder_reserve": ([vp, i64, i64], i32),
         "surge_device_decoder_result": ([vp, ctypes.POINTER(i64), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64)], i32),
+        "surge_device_decoder_state_result": ([vp, ctypes.POINTER(i64), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                               ctypes.POINTER(i64)], i32),
         "surge_device_decoder_clear": ([vp], i32),
+        "surge_device_decoder_load_states": ([vp, vp, vp, ctypes.POINTER(i64 * 4)], i32),
         "surge_replay_append_decoded": ([vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "surge_replay_append_decoded_async": ([vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "surge_replay_stage_decoded": ([vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),

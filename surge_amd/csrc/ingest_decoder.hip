@@ -12,6 +12,9 @@
 // decodes the event values (16-byte events as they are, or the reference's play-json text through the event template,
 // surge_amd/csrc/event_decode.cpp's rules) and compacts away the producer's flush records.  The host decoder spends
 // ≈ 90 ns (fixed-16) / 640 ns (JSON) per record and thread on exactly these steps.
+// State mode (surge_device_decoder_create_states) reads the compacted STATE topic with the same stages: the id is the whole key,
+// a null value is a delivered tombstone, no value is decoded — stage 2 gathers the delivered records' value bytes into one
+// buffer behind value_off, and surge_device_decoder_load_states hands them to surge_replay_decode_json_states.
 #include <sys/prctl.h>
 #include <time.h>
 
@@ -92,6 +95,7 @@ struct surge_device_decoder {
   int device = 0;
   hipStream_t stream = nullptr;
   bool json = false;
+  bool states = false;  // state mode (surge_device_decoder_create_states): values are kept (r_val / r_val_off), not decoded into events
   // Two host threads may drive one decoder: one enqueues stage 1 (push_async / push_parts_async), the other finishes pushes
   // (push_finish*, result, clear, append_decoded*).  `mu` covers what both touch: the slot queue and the error text.
   std::mutex mu;
@@ -115,6 +119,7 @@ struct surge_device_decoder {
   std::atomic<int> n_pending{0};  // slots [head, head + n_pending) hold pushes whose stage 1 is enqueued (changes under `mu`)
   // stage 2 scratch
   Buf first, first_scan, keep, keep_pos, temp;
+  Buf vlen, vscan, val_src, long_runs, st_status;  // state mode: the value scan and gather's scratch; load_states' per-record statuses
   // hash table + key table
   Buf t_slots, arena, key_off, key_hash;
   uint64_t t_cap = 0;
@@ -122,6 +127,8 @@ struct surge_device_decoder {
   int64_t n_keys = 0, arena_bytes = 0;
   // result
   Buf r_agg, r_ev, r_off;
+  Buf r_val, r_val_off;   // state mode: the delivered records' value bytes, one after the other, and n_records + 1 offsets into them
+  int64_t val_bytes = 0;  // ... bytes of r_val in use
   int64_t n_records = 0;
   // hand-over of the result arrays to a consumer on another stream (surge_replay_append_decoded_async): `consumed` is
   // recorded on the consumer's stream behind its last read, the next stage 2 waits for it before it writes the arrays
@@ -204,7 +211,7 @@ const char* surge_device_decoder_last_error(const surge_device_decoder* d) {
   return g_dec_err.c_str();
 }
 
-int32_t surge_device_decoder_create(int32_t device_id, void* hip_stream, const surge_event_json_template* tmpl, surge_device_decoder** out) {
+static int32_t decoder_create(int32_t device_id, void* hip_stream, const surge_event_json_template* tmpl, bool states, surge_device_decoder** out) {
   if (!out) return dfail(nullptr, E_INVALID, "out is NULL");
   *out = nullptr;
   if (tmpl && surge_event_json_validate(tmpl) != 0) return dfail(nullptr, E_INVALID, std::string("event template: ") + surge_event_json_last_error());
@@ -216,6 +223,7 @@ int32_t surge_device_decoder_create(int32_t device_id, void* hip_stream, const s
   d->device = device_id;
   d->stream = (hipStream_t)hip_stream;
   d->json = tmpl != nullptr;
+  d->states = states;
   if (const char* v = std::getenv("SURGE_INGEST_DEBUG_WEAK_HASH"))
     if (v[0] == '1') d->seed = 1ull << 63;  // test hook: the table's first hash function keeps 8 bits, so keys collide and the re-seed runs
   int prev = 0;
@@ -324,6 +332,14 @@ int32_t surge_device_decoder_create(int32_t device_id, void* hip_stream, const s
   return OK;
 }
 
+int32_t surge_device_decoder_create(int32_t device_id, void* hip_stream, const surge_event_json_template* tmpl, surge_device_decoder** out) {
+  return decoder_create(device_id, hip_stream, tmpl, false, out);
+}
+
+int32_t surge_device_decoder_create_states(int32_t device_id, void* hip_stream, surge_device_decoder** out) {
+  return decoder_create(device_id, hip_stream, nullptr, true, out);
+}
+
 int32_t surge_device_decoder_destroy(surge_device_decoder* d) {
   if (!d) return OK;
 #ifdef SURGE_EXPERIMENTS
@@ -347,7 +363,8 @@ int32_t surge_device_decoder_destroy(surge_device_decoder* d) {
     if (s.pinned) (void)hipHostFree(s.pinned);
   }
   Buf* bufs[] = {&d->d_tmpl, &d->d_ptab, &d->first, &d->first_scan, &d->keep, &d->keep_pos, &d->temp, &d->t_slots,
-                 &d->arena, &d->key_off, &d->key_hash, &d->r_agg, &d->r_ev, &d->r_off};
+                 &d->arena, &d->key_off, &d->key_hash, &d->r_agg, &d->r_ev, &d->r_off, &d->vlen, &d->vscan, &d->val_src,
+                 &d->long_runs, &d->st_status, &d->r_val, &d->r_val_off};
   for (Buf* b : bufs) b->release();
   if (d->ready) (void)hipEventDestroy(d->ready);
   if (d->consumed) (void)hipEventDestroy(d->consumed);
@@ -365,8 +382,9 @@ const char* why_bad(uint32_t status) {
   static const char* why[] = {"", "", "has a null key or value (not an event)", "is malformed (a length runs past its record or batch)",
                               "is not the JSON object the event template describes", "names an event type the template does not know",
                               "lacks a field the template names, or the field is not the number it should be", "is not a 16-byte fixed event", "",
-                              "collides with another key on its 64-bit hash"};
-  return status < 10 ? why[status] : "is bad";
+                              "collides with another key on its 64-bit hash",
+                              "has an empty, non-null value under a key (a state record carries a value or the null of a tombstone)"};
+  return status < 11 ? why[status] : "is bad";
 }
 
 struct DeviceScope {  // the calling thread's device, restored on the way out
@@ -403,8 +421,8 @@ int32_t await_release(surge_device_decoder* d, PushSlot& s) {
 int32_t slot_scratch(surge_device_decoder* d, PushSlot& s, int64_t n_rec) {
   const size_t R = (size_t)n_rec;
   DCHK(d, s.meta.reserve(R * sizeof(RecMeta), false, s.stream));
-  DCHK(d, s.ev_tmp.reserve(R * 16, false, s.stream));
-  DCHK(d, s.f64_list.reserve(R * 4, false, s.stream));
+  if (!d->states) DCHK(d, s.ev_tmp.reserve(R * 16, false, s.stream));
+  if (!d->states) DCHK(d, s.f64_list.reserve(R * 4, false, s.stream));
   static const ErrorCell kZero{~0ull, 0u, 0u, ~0u, ~0u};  // (the source of an asynchronous copy: it must outlive the call)
   DCHK(d, hipMemcpyAsync(s.d_err.p, &kZero, sizeof(kZero), hipMemcpyHostToDevice, s.stream));
   return OK;
@@ -582,8 +600,9 @@ SlotNeeds slot_needs(const PushSlot& s, const uint8_t* const* bytes, WireLayout&
 }
 
 int32_t size_slot(surge_device_decoder* d, PushSlot& t, const SlotNeeds& n) {
-  const std::pair<Buf*, size_t> device[] = {{&t.d_bytes, n.bytes}, {&t.d_sections, n.sections}, {&t.meta, (size_t)n.n_rec * sizeof(RecMeta)}, {&t.ev_tmp, (size_t)n.n_rec * 16},
-                                            {&t.f64_list, (size_t)n.n_rec * 4}, {&t.crc_spans, n.crc_spans}, {&t.lz4_blocks, n.lz4.blocks}, {&t.lz4_sizes, n.lz4.state},
+  const size_t per_event = d->states ? 0 : (size_t)n.n_rec;  // (a state decoder decodes no value)
+  const std::pair<Buf*, size_t> device[] = {{&t.d_bytes, n.bytes}, {&t.d_sections, n.sections}, {&t.meta, (size_t)n.n_rec * sizeof(RecMeta)}, {&t.ev_tmp, per_event * 16},
+                                            {&t.f64_list, per_event * 4}, {&t.crc_spans, n.crc_spans}, {&t.lz4_blocks, n.lz4.blocks}, {&t.lz4_sizes, n.lz4.state},
                                             {&t.lz4_nseq, n.lz4.n_seq}, {&t.lz4_seq, n.lz4.seq}, {&t.lz4_cls, n.lz4.cls}};
   for (const auto& b : device) DCHK(d, b.first->reserve(b.second, false, t.stream));
   return slot_pinned(d, t, n.pinned);
@@ -668,7 +687,7 @@ int32_t stage1_wire(surge_device_decoder* d, PushSlot& s, int32_t n_parts, const
   Lz4Work w{dbg_decode() / 10, (int32_t*)s.lz4_sizes.p, (int32_t*)s.lz4_nseq.p, (uint2*)s.lz4_seq.p, (int32_t*)s.lz4_cls.p, nullptr};
   DCHK(d, launch_lz4(s.lz4, dby, (uint8_t*)s.d_bytes.p + L.area_base(), (const Lz4Block*)s.lz4_blocks.p, w, dsec, derr, st));
   laps.lap("lz4 launches");
-  JsonCtx jc{d->json ? (const EvjDevice*)d->d_tmpl.p : nullptr, (const surge::F64ParseTable*)d->d_ptab.p, dbg_decode() % 10};
+  JsonCtx jc{d->json ? (const EvjDevice*)d->d_tmpl.p : nullptr, (const surge::F64ParseTable*)d->d_ptab.p, dbg_decode() % 10, d->states ? 1 : 0};
   DCHK(d, launch_sections(dby, dsec, L.total_sections, L.max_recs, seed, jc, (RecMeta*)s.meta.p, (uint4*)s.ev_tmp.p, (uint32_t*)s.f64_list.p, derr, st));
   laps.lap("section launches");
   s.n_rec = L.n_rec;
@@ -714,7 +733,7 @@ int32_t stage1_records(surge_device_decoder* d, PushSlot& s, const uint8_t* keys
   DCHK(d, hipMemcpyAsync(s.rec_b.p, p_vo, off_bytes, hipMemcpyHostToDevice, st));
   if (offsets) DCHK(d, hipMemcpyAsync(s.rec_c.p, p_of, (size_t)n * 8, hipMemcpyHostToDevice, st));
   DCHK(d, launch_records((const uint8_t*)s.d_bytes.p, (const int64_t*)s.rec_a.p, (const int64_t*)s.rec_b.p, offsets ? (const int64_t*)s.rec_c.p : nullptr, kb, n, seed,
-                         JsonCtx{d->json ? (const EvjDevice*)d->d_tmpl.p : nullptr, (const surge::F64ParseTable*)d->d_ptab.p}, (RecMeta*)s.meta.p,
+                         JsonCtx{d->json ? (const EvjDevice*)d->d_tmpl.p : nullptr, (const surge::F64ParseTable*)d->d_ptab.p, 0, d->states ? 1 : 0}, (RecMeta*)s.meta.p,
                          (uint4*)s.ev_tmp.p, (uint32_t*)s.f64_list.p, (ErrorCell*)s.d_err.p, st));
   s.n_rec = n;
   s.seed = seed;
@@ -773,6 +792,10 @@ int32_t stage2(surge_device_decoder* d, PushSlot& s, bool wait) {
     size_t temp_bytes = 0;
     DCHK(d, intern_temp_bytes(n_rec, &temp_bytes, st));
     DCHK(d, d->temp.reserve(temp_bytes, false, st));
+    if (d->states) {
+      DCHK(d, d->vlen.reserve((R + 1) * 8, false, st));
+      DCHK(d, d->vscan.reserve((R + 1) * 8, false, st));
+    }
     const int32_t rc = ensure_table(d, n_rec);
     if (rc != OK) return rc;
   }
@@ -780,10 +803,15 @@ int32_t stage2(surge_device_decoder* d, PushSlot& s, bool wait) {
   PCHK(hipStreamWaitEvent(st, s.done, 0));
   if (s.seed != d->seed) launch_rekey_records(dmeta, n_rec, dby, d->seed, st);  // the table was re-seeded after this push's stage 1 hashed its keys
   ErrorCell ec;
-  unsigned long long first_total = 0;
+  unsigned long long first_total = 0, val_total = 0;
   uint32_t kept = 0;
+  StateScratch values{(unsigned long long*)d->vlen.p, (unsigned long long*)d->vscan.p, nullptr, nullptr};
   for (int attempt = 0;; ++attempt) {
     PCHK(launch_intern_probe(dmeta, n_rec, dby, keys_of(d), scratch, derr, st));
+    if (d->states) {  // the delivered records' value lengths, scanned: where each value goes, and how many bytes the push adds
+      PCHK(launch_value_scan(dmeta, n_rec, scratch, values, st));
+      PCHK(hipMemcpyAsync(&val_total, values.vscan + R, 8, hipMemcpyDeviceToHost, st));
+    }
     PCHK(hipMemcpyAsync(&ec, derr, sizeof(ec), hipMemcpyDeviceToHost, st));
     PCHK(hipMemcpyAsync(&first_total, (unsigned long long*)d->first_scan.p + R, 8, hipMemcpyDeviceToHost, st));
     PCHK(hipMemcpyAsync(&kept, (uint32_t*)d->keep_pos.p + R, 4, hipMemcpyDeviceToHost, st));
@@ -816,6 +844,39 @@ int32_t stage2(surge_device_decoder* d, PushSlot& s, bool wait) {
     const uint32_t status = (uint32_t)(ec.first_bad & 0xff);
     RecMeta m;
     PCHK(hipMemcpy(&m, dmeta + rec, sizeof(m), hipMemcpyDeviceToHost));
+    if (status == RS_MALFORMED && s.wire) {
+      // the record stage gives up on such a record before it keeps its offset: read it here, from the section's bytes as the
+      // device has them (an LZ4 section exists decompressed there only) — the length varints up to the record, then its head
+      size_t si = 0;
+      while (si + 1 < s.h_secs.size() && s.h_secs[si + 1].rec_first <= rec) ++si;
+      Section sec;
+      std::vector<uint8_t> sb;
+      if (si < s.h_secs.size() && hipMemcpy(&sec, (const Section*)s.d_sections.p + si, sizeof(sec), hipMemcpyDeviceToHost) == hipSuccess && sec.byte_len > 0 &&
+          sec.byte_len < (1ll << 31)) {
+        try { sb.resize((size_t)sec.byte_len); } catch (const std::bad_alloc&) { sb.clear(); }
+        if (!sb.empty() && hipMemcpy(sb.data(), dby + sec.byte_off, sb.size(), hipMemcpyDeviceToHost) == hipSuccess) {
+          size_t pos = 0;
+          auto varlong = [&](int64_t* v) -> bool {
+            uint64_t u = 0;
+            for (int shift = 0; shift <= 63; shift += 7) {
+              if (pos >= sb.size()) return false;
+              const uint8_t b = sb[pos++];
+              u |= (uint64_t)(b & 0x7f) << shift;
+              if (!(b & 0x80)) { *v = (int64_t)(u >> 1) ^ -(int64_t)(u & 1); return true; }
+            }
+            return false;
+          };
+          int64_t len = 0, ts = 0, delta = 0;
+          bool ok = true;
+          for (int64_t k = sec.rec_first; ok && k < rec; ++k) {
+            ok = varlong(&len) && len >= 0 && (uint64_t)len <= sb.size() - pos;
+            if (ok) pos += (size_t)len;
+          }
+          if (ok && varlong(&len) && pos < sb.size() && (++pos, varlong(&ts)) && varlong(&delta)) m.offset = sec.base_offset + delta;
+        }
+      }
+      (void)hipGetLastError();
+    }
     return fail(status == RS_COLLISION ? E_UNSUPPORTED : SURGE_E_CORRUPT, "record " + std::to_string(rec) + " of the push (offset " + std::to_string(m.offset) + ") " +
                                                                              why_bad(status) + (status == RS_COLLISION ? " under four hash functions in a row" : ""));
   }
@@ -829,7 +890,14 @@ int32_t stage2(surge_device_decoder* d, PushSlot& s, bool wait) {
       if (e == hipSuccess) e = d->arena.reserve((size_t)(d->arena_bytes + new_bytes) + 16, true, st);
     }
     if (e == hipSuccess) e = d->r_agg.reserve((size_t)(d->n_records + kept) * 8 + 16, true, st);
-    if (e == hipSuccess) e = d->r_ev.reserve((size_t)(d->n_records + kept) * 16 + 16, true, st);
+    if (e == hipSuccess && !d->states) e = d->r_ev.reserve((size_t)(d->n_records + kept) * 16 + 16, true, st);
+    if (d->states) {  // (the values buffer ends at least 64 bytes behind its last value)
+      const size_t n_runs = ((size_t)kept + kGatherRecs - 1) / kGatherRecs;
+      if (e == hipSuccess) e = d->r_val_off.reserve((size_t)(d->n_records + kept + 1) * 8 + 16, true, st);
+      if (e == hipSuccess) e = d->r_val.reserve((size_t)(d->val_bytes + (int64_t)val_total) + 64, true, st);
+      if (e == hipSuccess) e = d->val_src.reserve((size_t)kept * 8 + 16, false, st);
+      if (e == hipSuccess) e = d->long_runs.reserve((n_runs + 1) * 4, false, st);
+    }
     if (e == hipSuccess) e = d->r_off.reserve((size_t)(d->n_records + kept) * 8 + 16, true, st);
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? E_NOMEM : E_DEVICE, std::string("growing the key table / result arrays: ") + hipGetErrorString(e));
   }
@@ -837,8 +905,15 @@ int32_t stage2(surge_device_decoder* d, PushSlot& s, bool wait) {
     PCHK(hipStreamWaitEvent(st, d->consumed, 0));
     d->consumed_valid = false;
   }
-  launch_intern_commit(dmeta, n_rec, dby, keys_of(d), scratch, n_new, (const uint4*)s.ev_tmp.p, d->n_records, (int64_t*)d->r_agg.p, (uint4*)d->r_ev.p, (int64_t*)d->r_off.p, st);
+  launch_intern_commit(dmeta, n_rec, dby, keys_of(d), scratch, n_new, (const uint4*)s.ev_tmp.p, d->n_records, (int64_t*)d->r_agg.p, d->states ? nullptr : (uint4*)d->r_ev.p,
+                       (int64_t*)d->r_off.p, st);
   PCHK(hipGetLastError());
+  if (d->states) {  // the values leave the slot's bytes (its next push writes those again) for the result's own buffer
+    values.val_src = (int64_t*)d->val_src.p;
+    values.long_runs = (uint32_t*)d->long_runs.p;
+    PCHK(launch_value_gather(dmeta, n_rec, dby, scratch, values, kept, d->n_records, d->val_bytes, (int64_t*)d->r_val_off.p, (uint8_t*)d->r_val.p, st));
+    d->val_bytes += (int64_t)val_total;
+  }
   d->n_keys += n_new;
   d->arena_bytes += new_bytes;
   if (ec.n_f64_host > 0) {
@@ -925,6 +1000,7 @@ int32_t grow_for_keys(surge_replay_handle* h, surge_device_decoder* d) {
 // overlaps the fold of fetch i on the device.
 int32_t hand_over_async(surge_replay_handle* h, surge_device_decoder* d, int64_t* n_events_out, int64_t* n_keys_out, bool fold) {
   if (!h || !d) return dfail(d, E_INVALID, "NULL argument");
+  if (d->states) return dfail(d, SURGE_E_STATE, "a state decoder holds state values, not events: hand them over with surge_device_decoder_load_states");
   if (n_events_out) *n_events_out = d->n_records;
   if (n_keys_out) *n_keys_out = d->n_keys;
   int32_t rc = fold ? grow_for_keys(h, d) : OK;
@@ -1047,6 +1123,7 @@ int32_t surge_device_decoder_push_records(surge_device_decoder* d, const uint8_t
 int32_t surge_device_decoder_result(surge_device_decoder* d, int64_t* n_records, const int64_t** d_agg_idx, const void** d_events16,
                                     const int64_t** d_offsets, int64_t* n_keys) {
   if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (d->states) return dfail(d, SURGE_E_STATE, "a state decoder has no events: see surge_device_decoder_state_result");
   if (n_records) *n_records = d->n_records;
   if (d_agg_idx) *d_agg_idx = (const int64_t*)d->r_agg.p;
   if (d_events16) *d_events16 = d->r_ev.p;
@@ -1055,10 +1132,70 @@ int32_t surge_device_decoder_result(surge_device_decoder* d, int64_t* n_records,
   return OK;
 }
 
+int32_t surge_device_decoder_state_result(surge_device_decoder* d, int64_t* n_records, const int64_t** d_agg_idx, const uint8_t** d_values,
+                                          const int64_t** d_value_off, const int64_t** d_offsets, int64_t* n_keys) {
+  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (!d->states) return dfail(d, SURGE_E_STATE, "not a state decoder (surge_device_decoder_create_states): see surge_device_decoder_result");
+  if (n_records) *n_records = d->n_records;
+  if (d_agg_idx) *d_agg_idx = (const int64_t*)d->r_agg.p;
+  if (d_values) *d_values = (const uint8_t*)d->r_val.p;
+  if (d_value_off) *d_value_off = (const int64_t*)d->r_val_off.p;
+  if (d_offsets) *d_offsets = (const int64_t*)d->r_off.p;
+  if (n_keys) *n_keys = d->n_keys;
+  return OK;
+}
+
+// state values -> resident state: what a KTable restore of the state topic does with the records it is handed
+// (SurgeStateStoreConsumer.scala:69), behind one call
+int32_t surge_device_decoder_load_states(surge_device_decoder* d, surge_replay_handle* h, const surge_json_template* tmpl, int64_t counts_out[4]) {
+  if (!h || !d || !counts_out) return dfail(d, E_INVALID, "NULL argument");
+  counts_out[0] = counts_out[1] = counts_out[2] = counts_out[3] = 0;
+  if (!d->states) return dfail(d, SURGE_E_STATE, "not a state decoder (surge_device_decoder_create_states): an events decoder hands over with surge_replay_append_decoded");
+  int32_t rc = grow_for_keys(h, d);
+  if (rc != OK) return rc;
+  if (d->n_records == 0) return OK;
+  void* hs = nullptr;
+  rc = surge_replay_get_stream(h, &hs);
+  if (rc != OK) return dfail(d, rc, surge_replay_last_error(h));
+  void* d_states = nullptr;
+  int64_t n_agg = 0;
+  rc = surge_replay_device_state(h, &d_states, &n_agg);
+  if (rc != OK) return dfail(d, rc, surge_replay_last_error(h));
+  DeviceScope scope(d->device);
+  DCHK(d, d->st_status.reserve((size_t)d->n_records, false, d->stream));
+  // the arrays are written on the decoder's stream and read on the handle's
+  DCHK(d, hipEventRecord(d->ready, d->stream));
+  DCHK(d, hipStreamWaitEvent((hipStream_t)hs, d->ready, 0));
+  // (rows [0, n_keys): every aggregate index of the result is below the decoder's key count, and its key table has that many ids)
+  rc = surge_replay_decode_json_states(h, tmpl, (const uint8_t*)d->r_val.p, (const int64_t*)d->r_val_off.p, d->n_records, (const uint8_t*)d->arena.p,
+                                       (const int64_t*)d->key_off.p, (const int64_t*)d->r_agg.p, d->n_keys, d_states, (uint8_t*)d->st_status.p, nullptr, counts_out);
+  if (rc != OK && rc != SURGE_E_CORRUPT) return dfail(d, rc, surge_replay_last_error(h));  // nothing was loaded: the records stay
+  std::string refused;
+  if (rc == SURGE_E_CORRUPT) {  // everything else is loaded; name the first refused record by its TOPIC offset
+    refused = surge_replay_last_error(h);
+    std::vector<uint8_t> status((size_t)d->n_records);
+    if (hipMemcpy(status.data(), d->st_status.p, status.size(), hipMemcpyDeviceToHost) == hipSuccess) {
+      for (int64_t r = 0; r < d->n_records; ++r) {
+        if (status[(size_t)r] == SURGE_STATE_DECODE_OK || status[(size_t)r] == SURGE_STATE_DECODE_SKIPPED) continue;
+        int64_t offset = -1;
+        if (hipMemcpy(&offset, (const int64_t*)d->r_off.p + r, 8, hipMemcpyDeviceToHost) == hipSuccess)
+          refused = std::to_string(counts_out[2]) + " state value(s) were refused (their rows are untouched), the first at topic offset " + std::to_string(offset) +
+                    " (record " + std::to_string(r) + " of this load) with status " + std::to_string((int)status[(size_t)r]) + " (SURGE_STATE_DECODE_*); everything else was loaded";
+        break;
+      }
+    }
+    (void)hipGetLastError();
+  }
+  d->n_records = 0;  // (cleared whether or not a winner was refused: the call returns when the rows are written)
+  d->val_bytes = 0;
+  return rc == OK ? OK : dfail(d, rc, refused);
+}
+
 // result -> resident state: the composition a host would otherwise spell out (grow for the new keys, device group-by +
 // fold, clear), behind one call so a JVM needs a single JNI crossing per poll
 int32_t surge_replay_append_decoded(surge_replay_handle* h, surge_device_decoder* d, int64_t* n_events_out, int64_t* n_keys_out) {
   if (!h || !d) return dfail(d, E_INVALID, "NULL argument");
+  if (d->states) return dfail(d, SURGE_E_STATE, "a state decoder holds state values, not events: hand them over with surge_device_decoder_load_states");
   if (n_events_out) *n_events_out = d->n_records;
   if (n_keys_out) *n_keys_out = d->n_keys;
   int32_t rc = grow_for_keys(h, d);
@@ -1099,6 +1236,7 @@ int32_t surge_replay_stage_decoded(surge_replay_handle* h, surge_device_decoder*
 int32_t surge_device_decoder_clear(surge_device_decoder* d) {
   if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
   d->n_records = 0;
+  d->val_bytes = 0;
   return OK;
 }
 

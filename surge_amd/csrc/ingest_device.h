@@ -27,6 +27,7 @@ enum : uint32_t {
   RS_SIZE = 7,          // fixed-16 topic: value is not 16 bytes
   RS_F64_HOST = 8,      // a Double the fast parser cannot decide: the host re-parses this value exactly
   RS_COLLISION = 9,     // two different keys with the same 64-bit hash
+  RS_EMPTY_VALUE = 10,  // state mode: an empty, non-null value under a key (writeState never writes one; the loader reads empty as a tombstone)
 };
 
 struct RecMeta {
@@ -164,6 +165,7 @@ struct JsonCtx {  // what the value decoder needs besides the value
   const EvjDevice* tmpl;  // nullptr: 16-byte fixed events
   const surge::F64ParseTable* ptab;
   int32_t dbg = 0;  // SURGE_DBG_DECODE (timing experiments only, results are NOT the topic's): 1 = sections are staged, nothing else; 2 = staged and chained, no record decoded
+  int32_t states = 0;  // state mode (surge_device_decoder_create_states): the id is the whole key, a null value is a tombstone, no value is decoded
 #ifdef SURGE_EXPERIMENTS
   unsigned long long* ticks = nullptr;  // per workgroup: wall clock (10 ns) at start, after staging, after the chain, at the end
 #endif
@@ -230,6 +232,20 @@ void launch_intern_reseed(RecMeta* meta, int64_t n_rec, const uint8_t* bytes, co
 void launch_intern_commit(const RecMeta* meta, int64_t n_rec, const uint8_t* bytes, const KeyTable& k, const InternScratch& sc, int64_t n_new,
                           const uint4* ev_tmp, int64_t out_base, int64_t* agg_out, uint4* ev_out, int64_t* off_out, hipStream_t st);
 void launch_intern_rollback(const RecMeta* meta, int64_t n_rec, const Table& t, hipStream_t st);  // a failed push takes the keys it probed out again
+
+// ---- state mode (ingest_intern.hip): the kept records' VALUES move out of the push's staged bytes -------------------------------
+constexpr int kGatherRecs = 256;          // kept records per workgroup of the value gather
+constexpr int64_t kGatherOwn = 64 << 10;  // bytes of its run's span a workgroup copies itself; what lies beyond is split over a second, grid-wide launch
+struct StateScratch {  // per push: vlen / vscan (n_rec + 1) entries, val_src one per delivered record, long_runs 1 + one per workgroup of the gather
+  unsigned long long *vlen, *vscan;
+  int64_t* val_src;
+  uint32_t* long_runs;  // [0] = how many runs are listed behind it
+};
+// behind launch_intern_probe: vscan[i] = value bytes of the delivered records in front of record i (vscan[n_rec]: of all of them)
+hipError_t launch_value_scan(const RecMeta* meta, int64_t n_rec, const InternScratch& sc, const StateScratch& ss, hipStream_t st);
+// behind launch_intern_commit: value_off[out_base + k] (and the closing entry) = val_base + ..., the values' bytes to values[val_base ..)
+hipError_t launch_value_gather(const RecMeta* meta, int64_t n_rec, const uint8_t* bytes, const InternScratch& sc, const StateScratch& ss, int64_t kept, int64_t out_base,
+                               int64_t val_base, int64_t* value_off, uint8_t* values, hipStream_t st);
 
 }  // namespace ingest
 }  // namespace surge

@@ -7,6 +7,7 @@
 //              delivered records' positions in the result arrays
 //   assign     the new keys' bytes to the device key arena, their ids into their slots
 //   finalize   one thread per delivered record: aggregate index from its slot, event and offset to the result arrays
+//   (state mode) value scan + value gather: the delivered records' value bytes out of the push's bytes into one buffer
 // The control flow around these — the retry after a collision, what is checked before anything is committed, the commit order —
 // is stage 2 of the decoder (ingest_decoder.hip); this unit launches what it is told to.
 #include <rocprim/device/device_radix_sort.hpp>
@@ -121,7 +122,7 @@ __global__ void finalize_kernel(const RecMeta* __restrict__ meta, int64_t n_rec,
   if (i >= n_rec || !keep[i]) return;
   const int64_t o = out_base + pos[i];
   agg_out[o] = (int64_t)t.s[meta[i].slot].key_id;
-  ev_out[o] = ev_tmp[i];
+  if (ev_out) ev_out[o] = ev_tmp[i];  // (state mode has no events: the values follow by value_gather_kernel)
   off_out[o] = meta[i].offset;
 }
 
@@ -159,6 +160,125 @@ __global__ void rekey_records_kernel(RecMeta* __restrict__ meta, int64_t n_rec, 
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_rec || meta[i].status != RS_OK) return;
   meta[i].hash = hash_key(bytes + meta[i].key_off, meta[i].key_len, seed);
+}
+
+// ---- state mode: the delivered records' values -> one contiguous buffer --------------------------------------------------------
+// A push's staged / decompressed bytes are written again by the slot's next push, so the values a state decoder keeps have to
+// move: behind what earlier pushes delivered, one after the other in delivery order, value_off in front of each.
+
+// vlen[i] = the bytes record i adds to the values (0 for a record that is not delivered, and for the closing entry n_rec)
+__global__ void value_len_kernel(const RecMeta* __restrict__ meta, int64_t n_rec, const uint32_t* __restrict__ keep, unsigned long long* __restrict__ vlen) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n_rec) return;
+  vlen[i] = (i < n_rec && keep[i]) ? (unsigned long long)(uint32_t)meta[i].val_len : 0ull;
+}
+
+// per delivered record: where its value goes (value_off, absolute) and where it lies in the push's bytes (val_src, by position in the push)
+__global__ void value_off_kernel(const RecMeta* __restrict__ meta, int64_t n_rec, const uint32_t* __restrict__ keep, const uint32_t* __restrict__ pos,
+                                 const unsigned long long* __restrict__ vscan, int64_t out_base, int64_t val_base, int64_t* __restrict__ value_off,
+                                 int64_t* __restrict__ val_src) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > n_rec) return;
+  if (i == n_rec) { value_off[out_base + pos[n_rec]] = val_base + (int64_t)vscan[n_rec]; return; }  // (pos[n_rec] = records delivered)
+  if (!keep[i]) return;
+  value_off[out_base + pos[i]] = val_base + (int64_t)vscan[i];
+  val_src[pos[i]] = meta[i].val_off;
+}
+
+// The gather.  The work is split by OUTPUT bytes: a workgroup owns a run of kGatherRecs consecutive delivered records — their
+// output span [D0, D1) is contiguous — and its lanes take the span's aligned 16-byte pieces, not the records: a lane finds the
+// record(s) its piece comes from in the run's offsets (LDS, binary search), puts the bytes together with load4 and stores one
+// aligned uint4; values of 30 bytes and one value of a megabyte keep every lane equally busy.  What lies in front of the first
+// and behind the last aligned piece (< 16 bytes each) is stored byte by byte: nothing outside [D0, D1) is written.
+struct GatherRun {
+  int64_t dst[kGatherRecs + 1];  // value_off of the run's records and the closing entry (absolute, in the values buffer)
+  int64_t src[kGatherRecs];      // where each value lies in the push's bytes
+  int32_t n;
+};
+
+__device__ __forceinline__ void gather_run_load(GatherRun& run, int64_t first, int64_t kept, const int64_t* __restrict__ value_off, const int64_t* __restrict__ val_src) {
+  const int64_t left = kept - first;
+  const int32_t n = left < kGatherRecs ? (int32_t)left : kGatherRecs;
+  for (int32_t k = threadIdx.x; k <= n; k += blockDim.x) {
+    run.dst[k] = value_off[first + k];
+    if (k < n) run.src[k] = val_src[first + k];
+  }
+  if (threadIdx.x == 0) run.n = n;
+}
+
+// the record of the run that holds output byte p (D0 <= p < D1): the first whose end lies behind p (records without bytes never qualify)
+__device__ __forceinline__ int32_t gather_find(const GatherRun& run, int64_t p) {
+  int32_t lo = 0, hi = run.n - 1;
+  while (lo < hi) {
+    const int32_t mid = (lo + hi) >> 1;
+    if (run.dst[mid + 1] > p) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ uint32_t gather_byte(const GatherRun& run, const uint8_t* __restrict__ bytes, int64_t p, int32_t& r) {
+  while (run.dst[r + 1] <= p) ++r;  // (p < D1 = dst[n]: ends at a record with bytes)
+  return bytes[run.src[r] + (p - run.dst[r])];
+}
+
+// the aligned piece [p, p + 16) of the run's span
+__device__ __forceinline__ void gather_piece(const GatherRun& run, const uint8_t* __restrict__ bytes, int64_t p, uint8_t* __restrict__ values) {
+  int32_t r = gather_find(run, p);
+  uint32_t w[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int64_t q = p + 4 * k;
+    while (run.dst[r + 1] <= q) ++r;
+    if (q + 4 <= run.dst[r + 1]) {  // the dword lies in one value: one unaligned load (reads at most 7 bytes behind it: the staged bytes' slack)
+      w[k] = load4(bytes + run.src[r] + (q - run.dst[r]));
+    } else {                        // it straddles values: byte by byte
+      int32_t rr = r;
+      uint32_t v = 0u;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) v |= gather_byte(run, bytes, q + b, rr) << (8 * b);
+      w[k] = v;
+    }
+  }
+  *(uint4*)(values + p) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// One workgroup per run.  It copies the head and tail bytes and the first kGatherOwn bytes' worth of pieces; a run whose span is
+// longer (one value of a megabyte among short ones) lists itself for value_gather_long_kernel, which splits the rest over a whole
+// grid: the decision is the workgroup's, not a lane's, and no lane ever copies a long value alone.
+__global__ void __launch_bounds__(256) value_gather_kernel(const uint8_t* __restrict__ bytes, const int64_t* __restrict__ value_off, const int64_t* __restrict__ val_src,
+                                                          int64_t kept, uint8_t* __restrict__ values, uint32_t* __restrict__ long_runs) {
+  __shared__ GatherRun run;
+  gather_run_load(run, (int64_t)blockIdx.x * kGatherRecs, kept, value_off, val_src);
+  __syncthreads();
+  const int64_t d0 = run.dst[0], d1 = run.dst[run.n];
+  if (d1 <= d0) return;  // tombstones only
+  const int64_t a0 = (d0 + 15) & ~15ll;                    // the first aligned piece starts here (if it fits)
+  const int64_t n_pieces = a0 < d1 ? (d1 - a0) >> 4 : 0;
+  const int64_t own = n_pieces < (kGatherOwn >> 4) ? n_pieces : (kGatherOwn >> 4);
+  for (int64_t j = threadIdx.x; j < own; j += blockDim.x) gather_piece(run, bytes, a0 + 16 * j, values);
+  // head [d0, min(a0, d1)) and tail [a0 + 16 n_pieces, d1): lanes of the last wave, one byte each
+  const int64_t head_end = a0 < d1 ? a0 : d1, tail = a0 < d1 ? a0 + 16 * n_pieces : d1;
+  const int t = (int)threadIdx.x - 192;
+  if (t >= 0 && t < 16 && d0 + t < head_end) { int32_t r = gather_find(run, d0 + t); values[d0 + t] = (uint8_t)gather_byte(run, bytes, d0 + t, r); }
+  if (t >= 16 && t < 32 && tail + (t - 16) < d1) { int32_t r = gather_find(run, tail + (t - 16)); values[tail + (t - 16)] = (uint8_t)gather_byte(run, bytes, tail + (t - 16), r); }
+  if (threadIdx.x == 0 && n_pieces > own) long_runs[1 + atomicAdd(&long_runs[0], 1u)] = blockIdx.x;  // (at most one entry per workgroup: the list holds them all)
+}
+
+// the pieces behind the first kGatherOwn bytes of the listed runs, every run split over the whole grid
+__global__ void __launch_bounds__(256) value_gather_long_kernel(const uint8_t* __restrict__ bytes, const int64_t* __restrict__ value_off, const int64_t* __restrict__ val_src,
+                                                               int64_t kept, uint8_t* __restrict__ values, const uint32_t* __restrict__ long_runs) {
+  __shared__ GatherRun run;
+  const uint32_t n_long = long_runs[0];
+  for (uint32_t k = 0; k < n_long; ++k) {  // (uniform: every workgroup walks the same list)
+    __syncthreads();  // the last run's readers are through
+    gather_run_load(run, (int64_t)long_runs[1 + k] * kGatherRecs, kept, value_off, val_src);
+    __syncthreads();
+    const int64_t d0 = run.dst[0], d1 = run.dst[run.n];
+    const int64_t a0 = (d0 + 15) & ~15ll;
+    const int64_t n_pieces = a0 < d1 ? (d1 - a0) >> 4 : 0;
+    for (int64_t j = (kGatherOwn >> 4) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_pieces; j += (int64_t)gridDim.x * blockDim.x)
+      gather_piece(run, bytes, a0 + 16 * j, values);
+  }
 }
 
 // one thread per item, 256 to a workgroup
@@ -213,6 +333,27 @@ void launch_intern_commit(const RecMeta* meta, int64_t n_rec, const uint8_t* byt
 }
 
 void launch_intern_rollback(const RecMeta* meta, int64_t n_rec, const Table& t, hipStream_t st) { LAUNCH_1D(rollback_kernel, n_rec, st, meta, n_rec, t); }
+
+hipError_t launch_value_scan(const RecMeta* meta, int64_t n_rec, const InternScratch& sc, const StateScratch& ss, hipStream_t st) {
+  LAUNCH_1D(value_len_kernel, n_rec + 1, st, meta, n_rec, (const uint32_t*)sc.keep, ss.vlen);
+  size_t tb = sc.temp_bytes;
+  return rocprim::exclusive_scan(sc.temp, tb, (const unsigned long long*)ss.vlen, ss.vscan, 0ull, (size_t)n_rec + 1, rocprim::plus<unsigned long long>(), st);
+}
+
+hipError_t launch_value_gather(const RecMeta* meta, int64_t n_rec, const uint8_t* bytes, const InternScratch& sc, const StateScratch& ss, int64_t kept, int64_t out_base,
+                               int64_t val_base, int64_t* value_off, uint8_t* values, hipStream_t st) {
+  LAUNCH_1D(value_off_kernel, n_rec + 1, st, meta, n_rec, (const uint32_t*)sc.keep, (const uint32_t*)sc.keep_pos, (const unsigned long long*)ss.vscan, out_base, val_base,
+            value_off, ss.val_src);
+  if (kept <= 0) return hipGetLastError();
+  const hipError_t e = hipMemsetAsync(ss.long_runs, 0, 4, st);
+  if (e != hipSuccess) return e;
+  const unsigned n_runs = (unsigned)((kept + kGatherRecs - 1) / kGatherRecs);
+  hipLaunchKernelGGL(value_gather_kernel, dim3(n_runs), dim3(256), 0, st, bytes, (const int64_t*)(value_off + out_base), (const int64_t*)ss.val_src, kept, values, ss.long_runs);
+  // (1024 workgroups: four per CU; with no run listed each reads one word and ends)
+  hipLaunchKernelGGL(value_gather_long_kernel, dim3(1024), dim3(256), 0, st, bytes, (const int64_t*)(value_off + out_base), (const int64_t*)ss.val_src, kept, values,
+                     (const uint32_t*)ss.long_runs);
+  return hipGetLastError();
+}
 
 }  // namespace ingest
 }  // namespace surge

@@ -1,7 +1,8 @@
 // ingest_records.hip — the device decoder's record stage: the varint-framed records of every batch found (chain), parsed
 // (key span, value span, offset; 64-bit hash of the key up to ':') and their values decoded (16-byte events as they are, or
-// the reference's play-json text through the event template, surge_amd/csrc/event_decode.cpp's rules).  Nothing here reads or
-// writes the key table.
+// the reference's play-json text through the event template, surge_amd/csrc/event_decode.cpp's rules).  In state mode
+// (JsonCtx::states, the state topic) the id is the whole key, a null value is a delivered tombstone and no value is decoded: the
+// value spans stay in RecMeta for stage 2's gather.  Nothing here reads or writes the key table.
 #include <cstdio>
 #include <cstdlib>
 
@@ -353,6 +354,56 @@ __device__ __forceinline__ void decode_record(P base, int64_t sec_off, int64_t b
   ev_tmp[gi] = e;
 }
 
+// The same record in STATE mode (JsonCtx::states: the compacted state topic).  The id is the WHOLE key — the state topic's key is the
+// id itself, "a:b" and "a" are two ids; a null value is a tombstone and is delivered, with no bytes; a null key, and an empty
+// non-null value under a key (writeState never writes one, the loader would read it as a tombstone), are refused; the flush record
+// is skipped as above; headers are skipped (the chain knows where the record ends); no value is decoded — its span stays in
+// RecMeta for stage 2's gather.  A function of its own behind a uniform branch: the events path keeps its instructions and registers.
+template <typename P>
+__device__ __forceinline__ void decode_state_record(P base, int64_t sec_off, int64_t base_offset, bool valid, int32_t body, int32_t end, int64_t gi, uint64_t seed,
+                                                    RecMeta* __restrict__ meta, ErrorCell* err) {
+  if (!valid) return;
+  RecMeta m;
+  m.key_off = m.val_off = m.offset = 0; m.hash = 0; m.key_len = m.val_len = 0; m.slot = 0; m.status = RS_MALFORMED;
+  if (body >= 0) {
+    ReaderT<P> q{base + body, base + end, true};
+    if (q.p < q.end) ++q.p; else q.ok = false;  // attributes
+    (void)q.varlong();                            // timestampDelta
+    const int64_t offset_delta = q.varlong();
+    const int64_t klen = q.varlong();
+    P key = q.p;
+    if (q.ok && klen > 0) { if (q.end - q.p >= klen) q.p += klen; else q.ok = false; }
+    const int64_t vlen = q.ok ? q.varlong() : 0;
+    P val = q.p;
+    if (q.ok && vlen > 0) { if (q.end - q.p >= vlen) q.p += vlen; else q.ok = false; }
+    if (q.ok && klen >= -1 && vlen >= -1 && klen < (1ll << 31) && vlen < (1ll << 31)) {
+      m.offset = base_offset + offset_delta;
+      if (klen == 0 && vlen == 0) {
+        m.status = RS_SKIP;  // KafkaProducerActorImpl.scala:322-329: the producer flushes on the state topic
+      } else if (klen < 0) {
+        m.status = RS_NULL;
+      } else if (vlen == 0) {
+        m.status = RS_EMPTY_VALUE;
+      } else {
+        uint64_t hk = hash_key_begin(seed);
+        for (int n = 0; n < (int)klen; n += 4) {
+          uint32_t w4 = load4(key + n);
+          const int take = (int)klen - n < 4 ? (int)klen - n : 4;
+          for (int b = 0; b < take; ++b, w4 >>= 8) hk = (hk ^ (w4 & 0xffu)) * 0x100000001B3ull;
+        }
+        m.key_off = sec_off + (key - base);
+        m.key_len = (int32_t)klen;
+        m.val_off = sec_off + (val - base);
+        m.val_len = vlen < 0 ? 0 : (int32_t)vlen;
+        m.hash = hash_key_end(hk, (int)klen, seed);
+        m.status = RS_OK;
+      }
+    }
+  }
+  if (m.status >= RS_NULL) report(err, gi, m.status);
+  meta[gi] = m;
+}
+
 // Workgroup sizes of section_kernel.  The decode walks are latency-bound: what counts is how many batches a CU has in
 // flight, and a workgroup's lanes beyond its batch's records only take registers away from other batches.  A 16 KiB batch of
 // the reference's publisher holds ~140 play-json events: 192 lanes decode it in one round where 256 idled 45 % of theirs — and
@@ -537,7 +588,11 @@ __device__ bool chain_records_parallel(lds_ptr_t base, int32_t len, int32_t cnt,
 }
 
 // A workgroup takes its section when lo_excl < byte_len and (byte_len <= cap or take_rest); byte_len <= cap is staged.
-template <int kSecThreads>
+// kStates: the state-mode instantiation.  The mode travels in JsonCtx::states and is the same for every record of a launch, so the
+// branch is taken where it is cheapest, at the launch: as a branch INSIDE the one kernel it cost the events path its register
+// budget (80 VGPRs hold the kernel only because ~170 scalar registers already live in spare vector lanes; a second record path
+// pushed those into scratch memory).
+template <int kSecThreads, bool kStates>
 __global__ void __launch_bounds__(kSecThreads) __attribute__((amdgpu_waves_per_eu(kSecThreads == 256 ? 5 : 6)))  // (four waves at 80 VGPRs spill)
 section_kernel(const uint8_t* __restrict__ bytes, const Section* __restrict__ sections, int64_t n_sections, int64_t lo_excl, int64_t cap, int32_t take_rest,
                uint64_t seed, JsonCtx jc, RecMeta* __restrict__ meta, uint4* __restrict__ ev_tmp, uint32_t* __restrict__ f64_host_list, ErrorCell* err) {
@@ -569,12 +624,14 @@ section_kernel(const uint8_t* __restrict__ bytes, const Section* __restrict__ se
   if (jc.dbg) {  // timing experiments: every record of the batch is "skipped"
     RecMeta m;
     m.key_off = m.val_off = m.offset = 0; m.hash = 0; m.key_len = m.val_len = 0; m.slot = 0; m.status = RS_SKIP;
-    for (int32_t i = threadIdx.x; i < sec.n_records; i += kSecThreads) { meta[sec.rec_first + i] = m; ev_tmp[sec.rec_first + i] = make_uint4(0, 0, 0, 0); }
+    for (int32_t i = threadIdx.x; i < sec.n_records; i += kSecThreads) { meta[sec.rec_first + i] = m; if constexpr (!kStates) ev_tmp[sec.rec_first + i] = make_uint4(0, 0, 0, 0); }
     if (jc.dbg == 1) return;
   }
   if (len >= (1ll << 31)) {  // a section of 2 GiB: nothing writes one (a batch's length is an int32)
-    for (int32_t i0 = 0; i0 < sec.n_records; i0 += kSecThreads)
-      decode_record(bytes, 0, 0, i0 + (int32_t)threadIdx.x < sec.n_records, -1, -1, sec.rec_first + i0 + threadIdx.x, seed, jc, meta, ev_tmp, f64_host_list, err);
+    for (int32_t i0 = 0; i0 < sec.n_records; i0 += kSecThreads) {
+      if constexpr (kStates) decode_state_record(bytes, 0, 0, i0 + (int32_t)threadIdx.x < sec.n_records, -1, -1, sec.rec_first + i0 + threadIdx.x, seed, meta, err);
+      else decode_record(bytes, 0, 0, i0 + (int32_t)threadIdx.x < sec.n_records, -1, -1, sec.rec_first + i0 + threadIdx.x, seed, jc, meta, ev_tmp, f64_host_list, err);
+    }
     return;
   }
   const lds_ptr_t lbase = (lds_ptr_t)sec_smem + skew;
@@ -611,10 +668,14 @@ section_kernel(const uint8_t* __restrict__ bytes, const Section* __restrict__ se
       const int32_t i = i0 + (int32_t)threadIdx.x;
       const bool valid = i < cnt;
       const int32_t body = valid ? rec_body[i] : -1, end = body >= 0 ? rec_end[i] : -1;
-      if (staged)
+      if constexpr (kStates) {
+        if (staged) decode_state_record(lbase, sec.byte_off, sec.base_offset, valid, body, end, sec.rec_first + r0 + i, seed, meta, err);
+        else decode_state_record(gbase, sec.byte_off, sec.base_offset, valid, body, end, sec.rec_first + r0 + i, seed, meta, err);
+      } else if (staged) {
         decode_record(lbase, sec.byte_off, sec.base_offset, valid, body, end, sec.rec_first + r0 + i, seed, jc, meta, ev_tmp, f64_host_list, err);
-      else
+      } else {
         decode_record(gbase, sec.byte_off, sec.base_offset, valid, body, end, sec.rec_first + r0 + i, seed, jc, meta, ev_tmp, f64_host_list, err);
+      }
     }
     __syncthreads();
     SURGE_TICK(3);
@@ -642,11 +703,13 @@ __global__ void __launch_bounds__(256) records_kernel(const uint8_t* __restrict_
     } else {
       const uint8_t* key = bytes + k0;
       int n = 0;
-      while (n < (int)(k1 - k0) && key[n] != (uint8_t)':') ++n;
+      if (jc.states) n = (int)(k1 - k0);  // the id is the whole key; an empty value is the tombstone
+      else while (n < (int)(k1 - k0) && key[n] != (uint8_t)':') ++n;
       m.key_len = n;
       m.val_len = (int32_t)(v1 - v0);
       m.hash = hash_key(key, n, seed);
-      has_value = true;
+      has_value = !jc.states;
+      if (jc.states) m.status = RS_OK;
     }
   }
   if (!valid) return;
@@ -660,7 +723,7 @@ __global__ void __launch_bounds__(256) records_kernel(const uint8_t* __restrict_
   }
   if (m.status >= RS_NULL) report(err, i, m.status);
   meta[i] = m;
-  ev_tmp[i] = e;
+  if (!jc.states) ev_tmp[i] = e;
 }
 
 }  // namespace
@@ -690,13 +753,18 @@ hipError_t launch_sections(const uint8_t* bytes, const Section* sections, int64_
     const size_t lds = (size_t)((caps[c] + 47) & ~15ll) + 2 * (size_t)kSecRecs * 4;
     const int64_t lo_excl = c == 0 ? -1 : caps[c - 1];
     const int32_t rest = c == n_caps - 1 ? 1 : 0;
-#define SURGE_SECTION_LAUNCH(T)                                                                                                                    \
-  hipLaunchKernelGGL(section_kernel<T>, dim3((unsigned)n_sections), dim3(T), lds, st, bytes, sections, n_sections, lo_excl, caps[c], rest, seed, jc, meta, \
+#define SURGE_SECTION_LAUNCH(T, S)                                                                                                                  \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(section_kernel<T, S>), dim3((unsigned)n_sections), dim3(T), lds, st, bytes, sections, n_sections, lo_excl, caps[c], rest, seed, jc, meta, \
                      ev_tmp, f64_host_list, err)
-    if (max_recs <= 64) SURGE_SECTION_LAUNCH(64);
-    else if (max_recs <= 128) SURGE_SECTION_LAUNCH(128);
-    else if (max_recs <= 192) SURGE_SECTION_LAUNCH(192);
-    else SURGE_SECTION_LAUNCH(256);
+#define SURGE_SECTION_WIDTH(S)                     \
+  do {                                             \
+    if (max_recs <= 64) SURGE_SECTION_LAUNCH(64, S);        \
+    else if (max_recs <= 128) SURGE_SECTION_LAUNCH(128, S); \
+    else if (max_recs <= 192) SURGE_SECTION_LAUNCH(192, S); \
+    else SURGE_SECTION_LAUNCH(256, S);                      \
+  } while (0)
+    if (jc.states) SURGE_SECTION_WIDTH(true); else SURGE_SECTION_WIDTH(false);
+#undef SURGE_SECTION_WIDTH
 #undef SURGE_SECTION_LAUNCH
 #ifdef SURGE_EXPERIMENTS
     if (jc.ticks) {  // (blocks: experiment runs only)

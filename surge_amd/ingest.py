@@ -526,15 +526,25 @@ class PushPipeline:
 
 class DeviceDecoder:
     """``surge_device_decoder``: records sections (host bytes) -> device-resident ``(agg_idx, events, offsets)`` and a
-    device key table.  ``template=None``: record values are 16-byte events; otherwise the model's ``EventJsonTemplate``."""
+    device key table.  ``template=None``: record values are 16-byte events; otherwise the model's ``EventJsonTemplate``.
+    ``states=True`` (instead of a template): a decoder for the compacted *state* topic
+    (``surge_device_decoder_create_states``) — the id is the whole key, a null value is a delivered tombstone, the values
+    are kept as bytes (``state_result()``) and handed to the engine with ``load_states_into``; ``result`` / ``fold_into`` /
+    ``stage_into`` are an events decoder's and fail on it (STATE)."""
 
-    def __init__(self, template: Optional[EventJsonTemplate] = None, device: int = 0, stream=None):
+    def __init__(self, template: Optional[EventJsonTemplate] = None, device: int = 0, stream=None, states: bool = False):
+        if states and template is not None:
+            raise ValueError("DeviceDecoder: states=True is the alternative to an event template")
         self._lib = _native.load()
         self._h = ctypes.c_void_p()
         self.device = device
+        self.states = bool(states)
         self._inflight = []
         c = template.to_c() if template is not None else None
-        rc = self._lib.surge_device_decoder_create(device, stream, ctypes.byref(c) if c is not None else None, ctypes.byref(self._h))
+        if states:
+            rc = self._lib.surge_device_decoder_create_states(device, stream, ctypes.byref(self._h))
+        else:
+            rc = self._lib.surge_device_decoder_create(device, stream, ctypes.byref(c) if c is not None else None, ctypes.byref(self._h))
         if rc != 0:
             raise IngestError(rc, (self._lib.surge_device_decoder_last_error(None) or b"").decode())
 
@@ -606,7 +616,10 @@ class DeviceDecoder:
     @property
     def n_keys(self) -> int:
         n = ctypes.c_int64()
-        self._check(self._lib.surge_device_decoder_result(self._h, None, None, None, None, ctypes.byref(n)))
+        if self.states:
+            self._check(self._lib.surge_device_decoder_state_result(self._h, None, None, None, None, None, ctypes.byref(n)))
+        else:
+            self._check(self._lib.surge_device_decoder_result(self._h, None, None, None, None, ctypes.byref(n)))
         return int(n.value)
 
     def reserve(self, n_keys: int, key_bytes: int) -> None:
@@ -659,6 +672,46 @@ class DeviceDecoder:
             return torch.as_tensor(holder, device=dev)
 
         return view(pa, n.value, 1), view(pe, n.value, 2), view(po, n.value, 1), nk.value
+
+    def state_result(self):
+        """A state decoder's records since the last clear: ``(agg_idx, values, value_off, offsets, n_keys)`` — CUDA tensors
+        viewing the decoder's arrays (valid until the next ``finish`` / ``clear`` / ``load_states_into``): record ``r`` names
+        aggregate ``agg_idx[r]``, its value is ``values[value_off[r]:value_off[r+1]]`` (empty: a tombstone) and its Kafka
+        offset ``offsets[r]``."""
+        import torch
+
+        n, nk = ctypes.c_int64(), ctypes.c_int64()
+        pa, pv, pvo, po = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self._lib.surge_device_decoder_state_result(self._h, ctypes.byref(n), ctypes.byref(pa), ctypes.byref(pv), ctypes.byref(pvo), ctypes.byref(po),
+                                                                ctypes.byref(nk)))
+        dev = torch.device("cuda", self.device)
+        z = torch.zeros(0, dtype=torch.int64, device=dev)
+        if n.value == 0:
+            return z, torch.zeros(0, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int64, device=dev), z.clone(), nk.value
+
+        def view(ptr, count, typestr):
+            iface = {"shape": (count,), "typestr": typestr, "data": (ptr.value, False), "version": 2}
+            return torch.as_tensor(type("_Span", (), {"__cuda_array_interface__": iface})(), device=dev)
+
+        torch.cuda.synchronize(dev)  # (a finish(wait=False) leaves the arrays complete in stream order only)
+        value_off = view(pvo, n.value + 1, "<i8")
+        total = int(value_off[-1].item())
+        values = view(pv, total, "|u1") if total else torch.zeros(0, dtype=torch.uint8, device=dev)
+        return view(pa, n.value, "<i8"), values, value_off, view(po, n.value, "<i8"), nk.value
+
+    def load_states_into(self, engine, template):
+        """A state decoder's hand-over (``surge_device_decoder_load_states``): everything delivered since the last clear is
+        decoded through ``template`` (the model's serialized state, ``encode.JsonTemplate``) into ``engine``'s resident state
+        — grown first for ids seen for the first time; per aggregate the last record wins, a tombstone zeroes the row — and
+        the decoder is cleared.  Returns the decode's counts ``(rows written, tombstones, winners refused, Doubles re-parsed
+        on the host)``; a refused winner raises ``IngestError`` (CORRUPT, naming the record's topic offset) after everything
+        else was loaded."""
+        counts = (ctypes.c_int64 * 4)()
+        t = template.to_c()
+        rc = self._lib.surge_device_decoder_load_states(self._h, engine._h, ctypes.byref(t), ctypes.byref(counts))
+        engine.n_agg = max(engine.n_agg, self.n_keys)  # (grown inside the call)
+        self._check(rc)
+        return tuple(int(c) for c in counts)
 
     def clear(self) -> None:
         self._check(self._lib.surge_device_decoder_clear(self._h))

@@ -321,6 +321,93 @@ class GpuReplayStateStore:
             eng.snapshot()
         return {"rows_written": counts[0], "tombstones": counts[1], "refused": counts[2], "reparsed_on_host": counts[3]}
 
+    def restore_from_state_topic(self, fetches, n_partitions: int = 0, template=None, events_tail: Sequence = (), framing_threads: int = 4,
+                                 device_crc: bool = True, in_place: bool = True) -> dict:
+        """``restore_from_state_records`` from what a consumer of the state topic actually receives: ``fetches`` yields the
+        topic's bytes — message-format-v2 record batches, LZ4 or uncompressed, transactional, with the producer's flush
+        records, tombstones as null values and the offset gaps log compaction leaves — one ``bytes`` per fetch, or with
+        ``n_partitions`` a sequence of that many per fetch (``None`` for a partition without bytes).  Framing is
+        ``restore_from_fetches``' (``FramedFetches`` / ``PartitionedFramedFetches``, ``read_committed``); a state-mode
+        ``DeviceDecoder`` finds the records and interns the ids on the device (up to four pushes in flight; the oldest is
+        finished, then loaded: ``load_states_into``) — no per-record work in Python.  The loaded states become the snapshot
+        baseline, then ``events_tail`` is folded on top, exactly as ``restore_from_state_records`` does.  Returns the
+        framer's and the decoder's counters plus the summed decode counts."""
+        import ctypes
+
+        import torch
+
+        from . import _native
+        from .encode import JsonTemplate
+        from .ingest import DeviceDecoder, FramedFetches, PartitionedFramedFetches
+        from .log import KeyTable
+        from .schema import EVENT_DTYPE
+
+        template = template or JsonTemplate.counter()
+        eng, lib = self.engine, _native.load()
+        eng.load_csr(np.zeros(1, dtype=np.int64), np.zeros(0, dtype=EVENT_DTYPE))
+        eng.fold()  # no aggregate yet: the loads grow the state for the ids they meet
+        depth = 4
+        totals = [0, 0, 0, 0]
+        d = DeviceDecoder(states=True, device=eng.device)
+        defaults = self.model.event_algebra().to_c().default_state
+        try:
+            eng._check(lib.surge_replay_set_decode_base(eng._h, ctypes.byref(defaults)))
+
+            def finish_one():
+                d.finish()
+                for i, c in enumerate(d.load_states_into(eng, template)):
+                    totals[i] += c
+
+            framer = (PartitionedFramedFetches(fetches, n_partitions, threads=framing_threads, hold=depth, overlap=True, device_crc=device_crc, in_place=in_place)
+                      if n_partitions
+                      else FramedFetches(fetches, overlap=True, hold=depth, device_crc=device_crc))
+            with framer as framed:
+                try:
+                    pending = 0
+                    fetch_iter = iter(framed)
+                    while True:
+                        if pending == depth:  # the oldest push is finished BEFORE the next fetch is asked for (its slab is framed into again)
+                            finish_one()
+                            pending -= 1
+                        item = next(fetch_iter, None)
+                        if item is None:
+                            break
+                        parts = item if isinstance(item, list) else [item]
+                        parts = [(sec, arena) for sec, arena in parts if sec.shape[0]]
+                        if parts:
+                            d.push_async(parts)
+                            pending += 1
+                    while pending:
+                        finish_one()
+                        pending -= 1
+                finally:
+                    while d.pending:  # (an error path: pushes that are enqueued read the framer's slabs until they are finished)
+                        try:
+                            d.finish()
+                        except Exception:
+                            pass
+                counters = framed.counters()
+            keys = KeyTable()
+            for k in d.keys():
+                keys.intern(k)
+            counters.update(d.counters())
+            self.keys = keys
+        finally:
+            eng._check(lib.surge_replay_set_decode_base(eng._h, None))
+            d.close()
+        n_agg = len(self.keys)
+        if n_agg:
+            d_kind = torch.zeros(n_agg, dtype=torch.uint8, device=torch.device("cuda", eng.device))
+            nv, nt = ctypes.c_int64(), ctypes.c_int64()
+            eng._check(lib.surge_replay_snapshot_delta(eng._h, ctypes.c_void_p(d_kind.data_ptr()), ctypes.byref(nv), ctypes.byref(nt), 1))
+        self._restored = True
+        if len(events_tail):
+            self.apply_events(events_tail)
+        else:
+            eng.snapshot()
+        counters.update({"rows_written": totals[0], "tombstones": totals[1], "refused": totals[2], "reparsed_on_host": totals[3]})
+        return counters
+
     def restore_log(self, log: EventLog, init_state: Optional[np.ndarray] = None, algo: int = ALGO_AUTO) -> None:
         self.keys = log.keys
         self.engine.load_csr(log.seg_off, log.events, init_state)
