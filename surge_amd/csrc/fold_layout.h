@@ -65,6 +65,9 @@ constexpr int kTableWalkWords = 14;
 constexpr int kTargetTasks = 8192;                        // enough tasks to fill the chip (2048 resident waves) four times over; 16384
                                                           // cost 3-13 % on logs below 1 GB: per-task start-up (plan, offsets, op table, first tile)
 
+constexpr int kDrawTiles = 8;                             // SORTED / CHUNKED: a draw at the ticket dispenser takes about this many tiles' worth of
+                                                          // groups (chunk_walk, fold_lane_device.h)
+
 struct FoldParams {
   const uint4* events;      // 16 B records
   int64_t n_events;         // length of the events buffer (loads are clamped to it)
