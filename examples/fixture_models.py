@@ -419,6 +419,11 @@ class BankAccountCommandModel(ReplayableCommandModel[BankAccount, object, object
         owner, code = self.static_fields.get(aggregate_id, ("", ""))
         return BankAccount(uuid.UUID(aggregate_id), owner, code, float(fixed["balance"]))
 
+    def restore_static_strings(self, aggregate_id: str, strings) -> None:
+        """The owner and security code a resume from the state topic read back (string columns 0 and 1 of ``JsonTemplate.bank_account()``)."""
+        if aggregate_id not in self.static_fields and strings[0] is not None and strings[1] is not None:
+            self.static_fields[aggregate_id] = (strings[0].decode("utf-8"), strings[1].decode("utf-8"))
+
     def state_to_fixed(self, aggregate: BankAccount) -> np.ndarray:
         s = np.zeros(1, dtype=STATE_DTYPE)
         a = self.event_algebra()
@@ -471,6 +476,31 @@ class BankAccountEventFormat:
         else:
             raise TypeError(f"not a BankAccount event: {evt!r}")
         return SerializedMessage(str(evt.accountNumber), text.encode("utf-8"))
+
+
+class BankAccountBusinessLogic(SurgeCommandBusinessLogic[BankAccount, object, object]):
+    """``BankAccountSurgeModel`` (``.../docs/command/BankAccountSurgeModel.scala:14-32``)."""
+
+    aggregate_name = "bank-account"
+    state_topic = KafkaTopic("bank-account-state")
+    events_topic = KafkaTopic("bank-account-events")
+
+    def __init__(self):
+        self._model = BankAccountCommandModel()
+        self._agg_format = BankAccountFormat()
+        self._evt_format = BankAccountEventFormat()
+
+    def command_model(self):
+        return self._model
+
+    def aggregate_read_formatting(self):
+        return self._agg_format
+
+    def aggregate_write_formatting(self):
+        return self._agg_format
+
+    def event_write_formatting(self):
+        return self._evt_format
 
 
 # ======================================================================================================

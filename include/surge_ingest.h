@@ -331,6 +331,19 @@ int32_t surge_replay_stage_decoded(struct surge_replay_handle* h, surge_device_d
  * (surge_replay_set_decode_base).  ABI v2 handles: SURGE_E_UNSUPPORTED (the decode's; nothing is cleared). */
 struct surge_json_template;
 int32_t surge_device_decoder_load_states(surge_device_decoder* d, struct surge_replay_handle* h, const struct surge_json_template* tmpl, int64_t counts_out[4]);
+/* The STR fields of the loaded states, kept on the device (off by default: load_states then behaves exactly as described
+ * above).  surge_device_decoder_keep_strings(d, 1) — state decoders only (SURGE_E_STATE otherwise), before the first
+ * load_states — makes every load_states also reserve a span buffer for the decode and, for every column a SURGE_JP_STR part
+ * of tmpl names, run surge_replay_merge_state_strings (surge_replay.h) over the load's records with the decoder's own
+ * previous column, n_agg = the decoder's key count: the column of a decoder that has loaded the whole topic holds, per
+ * aggregate, the string of the record that won — empty for a tombstoned id, the earlier string where a later winner was
+ * refused (a load that returns SURGE_E_CORRUPT has merged everything else).  The decoder owns the buffers (two per column,
+ * used in turn; they grow with room to spare), the merges run on the handle's stream behind the decode.
+ * surge_device_decoder_state_strings: column's CSR column (n_agg + 1 offsets) — the form surge_replay_set_encode_strings
+ * takes — valid until the next load_states, clear or destroy; *d_off == NULL (and *n_agg == 0) for a column no load has
+ * named. */
+int32_t surge_device_decoder_keep_strings(surge_device_decoder* d, int32_t on);
+int32_t surge_device_decoder_state_strings(surge_device_decoder* d, int32_t column, const uint8_t** d_utf8, const int64_t** d_off, int64_t* n_agg);
 /* The key table (aggregate ids in first-delivered order): to the host (NULL / NULL = size query), or where it lives on
  * the device (n_keys + 1 offsets; what the GPU state encoders and K4 take). */
 int32_t surge_device_decoder_keys(surge_device_decoder* d, uint8_t* utf8_out, int64_t utf8_capacity, int64_t* key_off_out, int64_t* n_keys_out,

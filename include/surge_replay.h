@@ -498,7 +498,8 @@ int32_t surge_replay_encode_protobuf_state(surge_replay_handle* h, const surge_j
  * topic (SurgeStateStoreConsumer.scala:57-76; records written by SurgeModel.scala:57-65) instead of replaying every
  * event.  The template's parts are matched in order: LITERAL bytes exactly; KEY a JSON string whose unescaped bytes
  * must be the aggregate's id when a key table is given; STR a JSON string that is validated and whose still-escaped
- * span is reported; I32 / U32 / I64 the integer rule of surge_event_json_decode (-?[0-9]+, no fraction or exponent)
+ * span is reported — surge_replay_merge_state_strings (below) unescapes the spans of a load into the side string column
+ * the encoders read, so a STR field is restored too; I32 / U32 / I64 the integer rule of surge_event_json_decode (-?[0-9]+, no fraction or exponent)
  * with a value outside the field's range REPORTED, never wrapped; F64 any JSON number, correctly rounded
  * (surge_parse_f64_json's algorithm).  String escapes: \" \\ \/ \b \f \n \r \t and \uXXXX outside the surrogate range.
  * Nothing may follow the last part.  Bytes of the state the template does not name are zero; flags becomes
@@ -544,6 +545,33 @@ int32_t surge_replay_decode_json_states(surge_replay_handle* h, const surge_json
                                         const int64_t* d_value_off, int64_t n_records, const uint8_t* d_keys_utf8,
                                         const int64_t* d_key_off, const int64_t* d_agg_idx, int64_t n_agg, void* d_states64,
                                         uint8_t* d_status_out, int64_t* d_str_span_out, int64_t counts_out[4]);
+
+/* A STR span (the bytes between the quotes, as reported above) -> the string, on the host, by the routine the device runs:
+ * the escapes above, \uXXXX as 1 - 3 bytes of UTF-8, bytes from 0x80 on as they are.  Returns the unescaped length — the
+ * bytes are written to out only when capacity >= that length — or -(SURGE_STATE_DECODE_* status): a raw byte below 0x20, a
+ * bare quote or a text that ends inside an escape (STRING), an unknown escape (ESCAPE), a surrogate (SURROGATE).  Never reads
+ * at or beyond raw + raw_len. */
+int64_t surge_unescape_json_string(const uint8_t* raw, int64_t raw_len, uint8_t* out, int64_t capacity);
+
+/* The STR parts of a load, kept: merges the strings of `column` that n_records decoded values carry into a side string
+ * column over n_agg aggregates — a fresh CSR column (d_out_utf8, d_out_off: n_agg + 1 offsets) in exactly the form
+ * surge_replay_set_encode_strings takes.  d_values / d_value_off / d_agg_idx are the arrays surge_replay_decode_json_states
+ * was given, d_status / d_str_span what it left.  Aggregate a's string:
+ *   - a record with status SURGE_STATE_DECODE_OK names a (the highest, should there be several): empty when its value is
+ *     empty (a tombstone), else the unescaped bytes of its span for `column`;
+ *   - otherwise, with a < n_prev: its string in the column so far (d_prev_utf8 / d_prev_off, n_prev + 1 offsets; NULL / 0:
+ *     none), byte for byte — SKIPPED losers and refused winners contribute nothing, so a refused winner's string stays as
+ *     its row does;
+ *   - otherwise empty.
+ * n_records = 0 extends a column to n_agg aggregates (after surge_replay_grow).  Two passes around a scan, as
+ * surge_replay_encode_json: *total_bytes_out always receives the total; when it exceeds out_capacity nothing is written to
+ * d_out_utf8 and SURGE_E_RANGE is returned.  SURGE_E_INVALID for a column outside [0, SURGE_JSON_STRING_COLUMNS),
+ * n_agg < n_prev, NULL where data is needed, and — with nothing written — a d_agg_idx entry outside [0, n_agg).  The output
+ * must not overlap the previous column.  Enqueued on the handle's stream; returns when it is done. */
+int32_t surge_replay_merge_state_strings(surge_replay_handle* h, int32_t column, const uint8_t* d_values, const int64_t* d_value_off,
+                                         int64_t n_records, const int64_t* d_agg_idx, const uint8_t* d_status, const int64_t* d_str_span,
+                                         const uint8_t* d_prev_utf8, const int64_t* d_prev_off, int64_t n_prev, int64_t n_agg,
+                                         uint8_t* d_out_utf8, int64_t out_capacity, int64_t* d_out_off, int64_t* total_bytes_out);
 
 /* What the bytes the template does NOT name hold in a row surge_replay_decode_json_states writes: state64's (NULL: zeros,
  * the default).  The named fields and the flags word always come from the text.  A store that resumes from the state topic

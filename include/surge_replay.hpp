@@ -213,6 +213,19 @@ class AggregateStateStore {
     return counts;
   }
 
+  // The STR spans that decode left -> string column `column` over n_agg aggregates (surge_replay_merge_state_strings; arguments
+  // as in surge_replay.h).  Returns the column's bytes; a buffer that is too small is not an error here: the total is
+  // returned (> out_capacity), nothing was written to d_out_utf8, call again with room.  Throws on any other failure.
+  int64_t mergeStateStrings(int32_t column, const uint8_t* d_values, const int64_t* d_value_off, int64_t n_records, const int64_t* d_agg_idx,
+                            const uint8_t* d_status, const int64_t* d_str_span, const uint8_t* d_prev_utf8, const int64_t* d_prev_off, int64_t n_prev,
+                            int64_t n_agg, uint8_t* d_out_utf8, int64_t out_capacity, int64_t* d_out_off) {
+    int64_t total = 0;
+    const int32_t rc = surge_replay_merge_state_strings(h_, column, d_values, d_value_off, n_records, d_agg_idx, d_status, d_str_span, d_prev_utf8,
+                                                        d_prev_off, n_prev, n_agg, d_out_utf8, out_capacity, d_out_off, &total);
+    if (!(rc == SURGE_E_RANGE && total > out_capacity)) check(rc);
+    return total;
+  }
+
   surge_replay_handle* handle() const { return h_; }
 
  private:

@@ -70,6 +70,7 @@ EXPORTS = (
     "surge_replay_encode_json",
     "surge_replay_encode_protobuf_state",
     "surge_replay_decode_json_states",
+    "surge_replay_merge_state_strings",
     "surge_replay_set_decode_base",
     "surge_replay_pack_states",
     "surge_replay_unpack_states",
@@ -138,6 +139,8 @@ INGEST_EXPORTS = (
     "surge_device_decoder_state_result",
     "surge_device_decoder_clear",
     "surge_device_decoder_load_states",
+    "surge_device_decoder_keep_strings",
+    "surge_device_decoder_state_strings",
     "surge_replay_append_decoded",
     "surge_replay_append_decoded_async",
     "surge_replay_stage_decoded",
@@ -181,7 +184,7 @@ SNAPSHOT_EXPORTS = (
 )
 
 #: the host half of the state decoder (declared in ``include/surge_replay.h``; needs no handle and no device)
-STATE_EXPORTS = ("surge_decode_json_state",)
+STATE_EXPORTS = ("surge_decode_json_state", "surge_unescape_json_string")
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -318,6 +321,8 @@ def load() -> ctypes.CDLL:
         "surge_replay_decode_json_states": ([vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, ctypes.POINTER(i64 * 4)], i32),
         "surge_replay_set_decode_base": ([vp, vp], i32),
         "surge_decode_json_state": ([vp, vp, i64, vp, i64, vp, vp], i32),
+        "surge_unescape_json_string": ([vp, i64, vp, i64], i64),
+        "surge_replay_merge_state_strings": ([vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, i64, vp, ctypes.POINTER(i64)], i32),
         "surge_replay_pack_states": ([vp, vp, i64, vp, vp], i32),
         "surge_replay_unpack_states": ([vp, vp, i64, vp, vp], i32),
         "surge_replay_partition_hash": ([vp, vp, i64, i32, vp], i32),
@@ -385,6 +390,8 @@ def load() -> ctypes.CDLL:
                                                ctypes.POINTER(i64)], i32),
         "surge_device_decoder_clear": ([vp], i32),
         "surge_device_decoder_load_states": ([vp, vp, vp, ctypes.POINTER(i64 * 4)], i32),
+        "surge_device_decoder_keep_strings": ([vp, i32], i32),
+        "surge_device_decoder_state_strings": ([vp, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64)], i32),
         "surge_replay_append_decoded": ([vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "surge_replay_append_decoded_async": ([vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "surge_replay_stage_decoded": ([vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),

@@ -1884,6 +1884,58 @@ int32_t surge_replay_decode_json_states(surge_replay_handle* h, const surge_json
   return SURGE_OK;
 }
 
+int32_t surge_replay_merge_state_strings(surge_replay_handle* h, int32_t column, const uint8_t* d_values, const int64_t* d_value_off, int64_t n_records,
+                                         const int64_t* d_agg_idx, const uint8_t* d_status, const int64_t* d_str_span, const uint8_t* d_prev_utf8,
+                                         const int64_t* d_prev_off, int64_t n_prev, int64_t n_agg, uint8_t* d_out_utf8, int64_t out_capacity,
+                                         int64_t* d_out_off, int64_t* total_bytes_out) {
+  if (!h) return fail(nullptr, SURGE_E_INVALID, "handle is NULL");
+  if (column < 0 || column >= SURGE_JSON_STRING_COLUMNS) return fail(h, SURGE_E_INVALID, "string column out of range");
+  if (n_records < 0 || n_prev < 0 || out_capacity < 0) return fail(h, SURGE_E_INVALID, "negative size");
+  if (n_agg < n_prev) return fail(h, SURGE_E_INVALID, "n_agg is below n_prev: a column never shrinks");
+  if (!d_out_off || !total_bytes_out) return fail(h, SURGE_E_INVALID, "NULL argument");
+  if (n_prev > 0 && !d_prev_off) return fail(h, SURGE_E_INVALID, "d_prev_off is NULL");
+  if (n_records > 0 && (!d_value_off || !d_status || !d_str_span)) return fail(h, SURGE_E_INVALID, "NULL argument");
+  if (!d_agg_idx && n_records > n_agg) return fail(h, SURGE_E_INVALID, "more records than aggregates and no d_agg_idx");
+  *total_bytes_out = 0;
+  DeviceGuard g(h->device);
+  StateStringsParams p{};
+  p.values = d_values; p.value_off = d_value_off; p.n_records = n_records;
+  p.agg_idx = d_agg_idx; p.status = d_status; p.spans = d_str_span; p.column = column;
+  p.n_agg = n_agg;
+  p.prev = d_prev_utf8; p.prev_off = d_prev_off; p.n_prev = n_prev;
+  p.out = d_out_utf8; p.out_off = d_out_off;
+  if (n_records > 0) {  // the winners first, and with them the indices: an entry outside [0, n_agg) ends the call before anything is written
+    HIPCHK(h, h->sd_counts.reserve(SD_N_COUNTS * 8));
+    HIPCHK(h, h->sd_last.reserve_roomy((size_t)n_agg * 8));
+    p.win1 = (unsigned long long*)h->sd_last.ptr;
+    unsigned long long* d_bad = (unsigned long long*)h->sd_counts.ptr + SD_BAD_INDEX;
+    unsigned long long bad = 0;
+    HIPCHK(h, launch_state_strings_winners(p, d_bad, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (bad) return fail(h, SURGE_E_INVALID, std::to_string(bad) + " d_agg_idx entr(y/ies) outside [0, n_agg): nothing was written");
+  }
+  const int64_t nb = (n_agg + 1023) / 1024;
+  int64_t total = 0;
+  if (n_agg > 0) {
+    HIPCHK(h, h->scan_totals.reserve((size_t)(nb + 1) * 8));
+    HIPCHK(h, launch_state_strings_pass(p, false, h->stream));
+    HIPCHK(h, launch_scan_lengths_i64(d_out_off, n_agg, (int64_t*)h->scan_totals.ptr, h->stream));
+    HIPCHK(h, hipMemcpyAsync(&total, (int64_t*)h->scan_totals.ptr + nb, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  HIPCHK(h, hipMemcpyAsync(d_out_off + n_agg, &total, 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  *total_bytes_out = total;
+  if (total > out_capacity) return fail(h, SURGE_E_RANGE, "output buffer too small for the string column");
+  if (total > 0 && !d_out_utf8) return fail(h, SURGE_E_INVALID, "d_out_utf8 is NULL");
+  if (total > 0) {
+    HIPCHK(h, launch_state_strings_pass(p, true, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+  }
+  return SURGE_OK;
+}
+
 int32_t surge_replay_snapshot_delta(surge_replay_handle* h, uint8_t* d_kind_out, int64_t* n_values_out, int64_t* n_tombstones_out,
                                     int32_t commit) {
   if (!h) return fail(nullptr, SURGE_E_INVALID, "handle is NULL");

@@ -130,6 +130,17 @@ struct surge_device_decoder {
   Buf r_val, r_val_off;   // state mode: the delivered records' value bytes, one after the other, and n_records + 1 offsets into them
   int64_t val_bytes = 0;  // ... bytes of r_val in use
   int64_t n_records = 0;
+  // state mode, surge_device_decoder_keep_strings: the STR columns of the loaded states (surge_replay_merge_state_strings
+  // writes buffer 1 - cur from buffer cur), and the decode's spans
+  struct StrColumn {
+    Buf utf8[2], off[2];
+    int cur = -1;  // -1: no load has named the column
+    int64_t n = 0, bytes = 0;
+  };
+  StrColumn str_cols[SURGE_JSON_STRING_COLUMNS];
+  Buf st_spans;
+  bool keep_strings = false;
+  int64_t state_loads = 0;
   // hand-over of the result arrays to a consumer on another stream (surge_replay_append_decoded_async): `consumed` is
   // recorded on the consumer's stream behind its last read, the next stage 2 waits for it before it writes the arrays
   hipEvent_t ready = nullptr, consumed = nullptr;
@@ -364,8 +375,10 @@ int32_t surge_device_decoder_destroy(surge_device_decoder* d) {
   }
   Buf* bufs[] = {&d->d_tmpl, &d->d_ptab, &d->first, &d->first_scan, &d->keep, &d->keep_pos, &d->temp, &d->t_slots,
                  &d->arena, &d->key_off, &d->key_hash, &d->r_agg, &d->r_ev, &d->r_off, &d->vlen, &d->vscan, &d->val_src,
-                 &d->long_runs, &d->st_status, &d->r_val, &d->r_val_off};
+                 &d->long_runs, &d->st_status, &d->r_val, &d->r_val_off, &d->st_spans};
   for (Buf* b : bufs) b->release();
+  for (auto& col : d->str_cols)
+    for (int k = 0; k < 2; ++k) { col.utf8[k].release(); col.off[k].release(); }
   if (d->ready) (void)hipEventDestroy(d->ready);
   if (d->consumed) (void)hipEventDestroy(d->consumed);
   if (d->sleeper) (void)hipEventDestroy(d->sleeper);
@@ -1163,13 +1176,16 @@ int32_t surge_device_decoder_load_states(surge_device_decoder* d, surge_replay_h
   if (rc != OK) return dfail(d, rc, surge_replay_last_error(h));
   DeviceScope scope(d->device);
   DCHK(d, d->st_status.reserve((size_t)d->n_records, false, d->stream));
+  if (d->keep_strings) DCHK(d, d->st_spans.reserve((size_t)d->n_records * (2 * SURGE_JSON_STRING_COLUMNS) * 8, false, d->stream));
   // the arrays are written on the decoder's stream and read on the handle's
   DCHK(d, hipEventRecord(d->ready, d->stream));
   DCHK(d, hipStreamWaitEvent((hipStream_t)hs, d->ready, 0));
   // (rows [0, n_keys): every aggregate index of the result is below the decoder's key count, and its key table has that many ids)
   rc = surge_replay_decode_json_states(h, tmpl, (const uint8_t*)d->r_val.p, (const int64_t*)d->r_val_off.p, d->n_records, (const uint8_t*)d->arena.p,
-                                       (const int64_t*)d->key_off.p, (const int64_t*)d->r_agg.p, d->n_keys, d_states, (uint8_t*)d->st_status.p, nullptr, counts_out);
+                                       (const int64_t*)d->key_off.p, (const int64_t*)d->r_agg.p, d->n_keys, d_states, (uint8_t*)d->st_status.p,
+                                       d->keep_strings ? (int64_t*)d->st_spans.p : nullptr, counts_out);
   if (rc != OK && rc != SURGE_E_CORRUPT) return dfail(d, rc, surge_replay_last_error(h));  // nothing was loaded: the records stay
+  ++d->state_loads;
   std::string refused;
   if (rc == SURGE_E_CORRUPT) {  // everything else is loaded; name the first refused record by its TOPIC offset
     refused = surge_replay_last_error(h);
@@ -1186,9 +1202,51 @@ int32_t surge_device_decoder_load_states(surge_device_decoder* d, surge_replay_h
     }
     (void)hipGetLastError();
   }
+  if (d->keep_strings) {  // (a refused winner keeps its earlier string, as it keeps its row: everything else is merged)
+    bool named[SURGE_JSON_STRING_COLUMNS] = {};
+    for (uint32_t i = 0; i < tmpl->n_parts; ++i)
+      if (tmpl->part[i].kind == SURGE_JP_STR && tmpl->part[i].field_offset < SURGE_JSON_STRING_COLUMNS) named[tmpl->part[i].field_offset] = true;
+    for (int c = 0; c < SURGE_JSON_STRING_COLUMNS; ++c) {
+      if (!named[c]) continue;
+      auto& col = d->str_cols[c];
+      const int cur = col.cur, nxt = cur < 0 ? 0 : 1 - cur;
+      // an unescaped string is never longer than its span, and the spans lie inside the load's values: the merge always fits
+      const int64_t cap = col.bytes + d->val_bytes + 16;
+      DCHK(d, col.off[nxt].reserve((size_t)(d->n_keys + 1) * 8, false, d->stream));
+      DCHK(d, col.utf8[nxt].reserve((size_t)cap, false, d->stream));
+      int64_t total = 0;
+      const int32_t mrc = surge_replay_merge_state_strings(h, c, (const uint8_t*)d->r_val.p, (const int64_t*)d->r_val_off.p, d->n_records, (const int64_t*)d->r_agg.p,
+                                                           (const uint8_t*)d->st_status.p, (const int64_t*)d->st_spans.p,
+                                                           cur < 0 ? nullptr : (const uint8_t*)col.utf8[cur].p, cur < 0 ? nullptr : (const int64_t*)col.off[cur].p,
+                                                           cur < 0 ? 0 : col.n, d->n_keys, (uint8_t*)col.utf8[nxt].p, cap, (int64_t*)col.off[nxt].p, &total);
+      if (mrc != OK) return dfail(d, mrc, std::string("keeping string column ") + std::to_string(c) + ": " + surge_replay_last_error(h));
+      col.cur = nxt;
+      col.n = d->n_keys;
+      col.bytes = total;
+    }
+  }
   d->n_records = 0;  // (cleared whether or not a winner was refused: the call returns when the rows are written)
   d->val_bytes = 0;
   return rc == OK ? OK : dfail(d, rc, refused);
+}
+
+int32_t surge_device_decoder_keep_strings(surge_device_decoder* d, int32_t on) {
+  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (!d->states) return dfail(d, SURGE_E_STATE, "not a state decoder (surge_device_decoder_create_states): an events decoder holds no state values");
+  if (d->state_loads != 0) return dfail(d, SURGE_E_STATE, "surge_device_decoder_keep_strings comes before the first surge_device_decoder_load_states");
+  d->keep_strings = on != 0;
+  return OK;
+}
+
+int32_t surge_device_decoder_state_strings(surge_device_decoder* d, int32_t column, const uint8_t** d_utf8, const int64_t** d_off, int64_t* n_agg) {
+  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (!d->states) return dfail(d, SURGE_E_STATE, "not a state decoder (surge_device_decoder_create_states): an events decoder holds no state values");
+  if (column < 0 || column >= SURGE_JSON_STRING_COLUMNS) return dfail(d, E_INVALID, "string column out of range");
+  const auto& col = d->str_cols[column];
+  if (d_utf8) *d_utf8 = col.cur < 0 ? nullptr : (const uint8_t*)col.utf8[col.cur].p;
+  if (d_off) *d_off = col.cur < 0 ? nullptr : (const int64_t*)col.off[col.cur].p;
+  if (n_agg) *n_agg = col.cur < 0 ? 0 : col.n;
+  return OK;
 }
 
 // result -> resident state: the composition a host would otherwise spell out (grow for the new keys, device group-by +

@@ -130,6 +130,28 @@ struct StateDecodeParams {
   unsigned long long* counts;   // SD_N_COUNTS entries
 };
 hipError_t launch_state_decode(const surge_json_template& tmpl, const StateDecodeParams& p, hipStream_t stream);
+// ---- state_strings.hip: the STR spans of decoded state values -> a side string column (surge_replay_merge_state_strings) ----
+struct StateStringsParams {
+  const uint8_t* values;        // record r's text: values[value_off[r] .. value_off[r + 1])  (NULL: every value is empty)
+  const int64_t* value_off;
+  int64_t n_records;
+  const int64_t* agg_idx;       // nullable: record r is aggregate r
+  const uint8_t* status;        // as the decoder left them: only SURGE_STATE_DECODE_OK records contribute
+  const int64_t* spans;         // per record 2 x SURGE_JSON_STRING_COLUMNS {offset into the value, length}
+  int32_t column;
+  unsigned long long* win1;     // n_agg entries of scratch: 1 + the highest OK record that names the aggregate (NULL with no records)
+  int64_t n_agg;
+  const uint8_t* prev;          // the column so far (nullable: every previous string is empty)
+  const int64_t* prev_off;      // n_prev + 1
+  int64_t n_prev;
+  uint8_t* out;
+  int64_t* out_off;             // n_agg + 1: lengths, then (scanned by the caller) offsets
+};
+hipError_t launch_state_strings_winners(const StateStringsParams& p, unsigned long long* bad, hipStream_t stream);
+hipError_t launch_state_strings_pass(const StateStringsParams& p, bool write, hipStream_t stream);
+// state_kernels.hip: the encoders' exclusive scan of v[0 .. n) in place; d_totals: ceil(n / 1024) + 1 entries of scratch, the
+// grand total lands in d_totals[ceil(n / 1024)]
+hipError_t launch_scan_lengths_i64(int64_t* v, int64_t n, int64_t* d_totals, hipStream_t stream);
 // kind[a] in SURGE_SNAP_*; d_counts: two u64 {values, tombstones}; commit: published := states where kind != SKIP
 hipError_t launch_snapshot_invalidate(uint4* published, int64_t n, const uint8_t* kind, hipStream_t stream);
 hipError_t launch_snapshot_commit(const uint4* states, uint4* published, int64_t n, const uint8_t* kind, hipStream_t stream);

@@ -1,5 +1,5 @@
 // state_decode_host.cpp — surge_decode_json_state: one serialized state value -> the fixed 64-byte state on the host, with
-// the parser the device kernel runs (state_parse.h).  Plain C++ (no HIP): point reads of a state-topic record, the
+// the parser the device kernel runs (state_parse.h); surge_unescape_json_string: a STR span -> its string, likewise.  Plain C++ (no HIP): point reads of a state-topic record, the
 // device decoder's re-parse of a Double it cannot decide, and the reference the device kernel is held to in the tests.
 #include <cstring>
 
@@ -16,4 +16,13 @@ extern "C" int32_t surge_decode_json_state(const surge_json_template* tmpl, cons
   std::memcpy(state64_out, row, 64);
   if (str_span_out) std::memcpy(str_span_out, span, sizeof(span));
   return SURGE_STATE_DECODE_OK;
+}
+
+extern "C" int64_t surge_unescape_json_string(const uint8_t* raw, int64_t raw_len, uint8_t* out, int64_t capacity) {
+  if (raw_len < 0 || (!raw && raw_len > 0)) return -(int64_t)SURGE_STATE_DECODE_STRING;
+  int64_t n = 0;
+  const int rc = surge::sp_unescape(raw, raw_len, nullptr, 0, &n);  // the length first: nothing is written unless all of it fits
+  if (rc != SURGE_STATE_DECODE_OK) return -(int64_t)rc;
+  if (out && capacity >= n) (void)surge::sp_unescape(raw, raw_len, out, n, &n);
+  return n;
 }

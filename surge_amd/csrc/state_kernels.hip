@@ -489,6 +489,15 @@ hipError_t launch_stream_probe(const uint4* src, int64_t n_vec, uint32_t* sink, 
   return hipGetLastError();
 }
 
+hipError_t launch_scan_lengths_i64(int64_t* v, int64_t n, int64_t* d_totals, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  const int64_t nb = (n + kScanBlock - 1) / kScanBlock;
+  hipLaunchKernelGGL(scan_block_kernel, dim3((unsigned)nb), dim3(kScanBlock), 0, stream, v, n, d_totals);
+  hipLaunchKernelGGL(scan_totals_kernel, dim3(1), dim3(1024), 0, stream, d_totals, nb);  // exclusive scan of block totals, grand total at [nb]
+  hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)nb), dim3(kScanBlock), 0, stream, v, n, d_totals);
+  return hipGetLastError();
+}
+
 // d_len_off: n + 1 entries; d_totals: ceil(n / 1024) + 1 entries of scratch
 hipError_t launch_json_encode(const surge_json_template& tmpl, const uint4* states, int64_t n, const uint8_t* keys,
                               const int64_t* key_off, int64_t* d_len_off, int64_t* d_totals, uint8_t* out, bool write_pass,
@@ -507,10 +516,7 @@ hipError_t launch_json_encode(const surge_json_template& tmpl, const uint4* stat
   const unsigned blocks = (unsigned)((n + 255) / 256);
   if (!write_pass) {
     hipLaunchKernelGGL(json_encode_kernel<false>, dim3(blocks), dim3(kJsonBlock), 0, stream, t, states, n, keys, key_off, d_len_off, out);
-    const int64_t nb = (n + kScanBlock - 1) / kScanBlock;
-    hipLaunchKernelGGL(scan_block_kernel, dim3((unsigned)nb), dim3(kScanBlock), 0, stream, d_len_off, n, d_totals);
-    hipLaunchKernelGGL(scan_totals_kernel, dim3(1), dim3(1024), 0, stream, d_totals, nb);  // exclusive scan of block totals, grand total at [nb]
-    hipLaunchKernelGGL(scan_add_kernel, dim3((unsigned)nb), dim3(kScanBlock), 0, stream, d_len_off, n, d_totals);
+    return launch_scan_lengths_i64(d_len_off, n, d_totals, stream);
   } else {
     hipLaunchKernelGGL(json_encode_kernel<true>, dim3(blocks), dim3(kJsonBlock), kJsonStageBytes + 16, stream, t, states, n, keys, key_off, d_len_off, out);
   }

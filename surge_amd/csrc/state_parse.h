@@ -7,7 +7,8 @@
 // anything else is refused with a status that names the part kind that did not match, never guessed at:
 //   LITERAL            the bytes must match
 //   KEY                a JSON string; with a key given, its unescaped bytes must be the aggregate's id
-//   STR                a JSON string; validated, its still-escaped span (offset, length between the quotes) reported
+//   STR                a JSON string; validated, its still-escaped span (offset, length between the quotes) reported —
+//                      sp_unescape turns such a span into the string (state_strings.hip keeps them as side columns)
 //   I32 / U32 / I64    -?[0-9]+ and nothing of a decimal after it (the event decoder's integer rule, event_decode.cpp),
 //                      inside the field's range — a value outside it is reported, never wrapped
 //   F64                f64_parse_json_number (f64_parse.h): correctly rounded, or AMBIGUOUS for the caller to settle
@@ -53,6 +54,51 @@ SURGE_HD int sp_hex(uint8_t c) {
   return -1;
 }
 
+// One character of a JSON string's body, the one place that knows the accepted escapes: `c` is the byte just read at
+// v[*i - 1] (not a closing quote); an escape's remaining bytes are read from v[*i ..] and never at or beyond v + len.
+// *cp = the code point (a byte from 0x80 on stands for itself), *n_out = how many UTF-8 bytes it unescapes to (1 .. 3).
+SURGE_HD int sp_string_unit(const uint8_t* v, int64_t len, int64_t* i, uint32_t c, uint32_t* cp, uint32_t* n_out) {
+  *n_out = 1;
+  *cp = c;
+  if (c < 0x20u) return SURGE_STATE_DECODE_STRING;  // a control character is always escaped
+  if (c != '\\') return SURGE_STATE_DECODE_OK;
+  if (*i >= len) return SURGE_STATE_DECODE_STRING;
+  const uint8_t e = v[(*i)++];
+  switch (e) {
+    case '"': *cp = '"'; break;
+    case '\\': *cp = '\\'; break;
+    case '/': *cp = '/'; break;
+    case 'b': *cp = '\b'; break;
+    case 'f': *cp = '\f'; break;
+    case 'n': *cp = '\n'; break;
+    case 'r': *cp = '\r'; break;
+    case 't': *cp = '\t'; break;
+    case 'u': {
+      if (len - *i < 4) return SURGE_STATE_DECODE_STRING;  // the text ends inside the escape
+      uint32_t u = 0;
+      for (int d = 0; d < 4; ++d) {
+        const int h = sp_hex(v[*i + d]);
+        if (h < 0) return SURGE_STATE_DECODE_ESCAPE;
+        u = (u << 4) | (uint32_t)h;
+      }
+      *i += 4;
+      if (u >= 0xD800u && u <= 0xDFFFu) return SURGE_STATE_DECODE_SURROGATE;
+      *cp = u;
+      *n_out = u < 0x80u ? 1u : u < 0x800u ? 2u : 3u;
+      break;
+    }
+    default: return SURGE_STATE_DECODE_ESCAPE;
+  }
+  return SURGE_STATE_DECODE_OK;
+}
+
+// byte b of the n_out UTF-8 bytes of code point c (sp_string_unit's pair)
+SURGE_HD uint32_t sp_utf8_byte(uint32_t c, uint32_t n_out, uint32_t b) {
+  if (n_out == 1) return c;
+  if (n_out == 2) return b == 0 ? (0xC0u | (c >> 6)) : (0x80u | (c & 0x3Fu));
+  return b == 0 ? (0xE0u | (c >> 12)) : b == 1 ? (0x80u | ((c >> 6) & 0x3Fu)) : (0x80u | (c & 0x3Fu));
+}
+
 // A JSON string whose opening quote is v[*pos].  key_len >= 0: the unescaped bytes must equal key[0 .. key_len).
 // *pos ends behind the closing quote; the raw span between the quotes goes to *raw_off / *raw_len.
 SURGE_HD int sp_string(const uint8_t* v, int64_t len, int64_t* pos, const uint8_t* key, int64_t key_len, int64_t* raw_off,
@@ -67,44 +113,13 @@ SURGE_HD int sp_string(const uint8_t* v, int64_t len, int64_t* pos, const uint8_
     if (i >= len) return SURGE_STATE_DECODE_STRING;  // unterminated
     uint32_t c = v[i++];
     if (c == '"') break;
-    if (c < 0x20u) return SURGE_STATE_DECODE_STRING;  // a control character is always escaped
     uint32_t n_out = 1;
-    if (c == '\\') {
-      if (i >= len) return SURGE_STATE_DECODE_STRING;
-      const uint8_t e = v[i++];
-      switch (e) {
-        case '"': c = '"'; break;
-        case '\\': c = '\\'; break;
-        case '/': c = '/'; break;
-        case 'b': c = '\b'; break;
-        case 'f': c = '\f'; break;
-        case 'n': c = '\n'; break;
-        case 'r': c = '\r'; break;
-        case 't': c = '\t'; break;
-        case 'u': {
-          if (len - i < 4) return SURGE_STATE_DECODE_STRING;  // the text ends inside the escape
-          c = 0;
-          for (int d = 0; d < 4; ++d) {
-            const int h = sp_hex(v[i + d]);
-            if (h < 0) return SURGE_STATE_DECODE_ESCAPE;
-            c = (c << 4) | (uint32_t)h;
-          }
-          i += 4;
-          if (c >= 0xD800u && c <= 0xDFFFu) return SURGE_STATE_DECODE_SURROGATE;
-          n_out = c < 0x80u ? 1u : c < 0x800u ? 2u : 3u;
-          break;
-        }
-        default: return SURGE_STATE_DECODE_ESCAPE;
-      }
-    }
+    const int rc = sp_string_unit(v, len, &i, c, &c, &n_out);
+    if (rc != SURGE_STATE_DECODE_OK) return rc;
     if (key_len >= 0) {
       // the code point as UTF-8, byte by byte against the key
       for (uint32_t b = 0; b < n_out; ++b) {
-        uint32_t byte;
-        if (n_out == 1) byte = c;
-        else if (n_out == 2) byte = b == 0 ? (0xC0u | (c >> 6)) : (0x80u | (c & 0x3Fu));
-        else byte = b == 0 ? (0xE0u | (c >> 12)) : b == 1 ? (0x80u | ((c >> 6) & 0x3Fu)) : (0x80u | (c & 0x3Fu));
-        same = same && k < key_len && key[k] == (uint8_t)byte;
+        same = same && k < key_len && key[k] == (uint8_t)sp_utf8_byte(c, n_out, b);
         ++k;
       }
     }
@@ -112,6 +127,28 @@ SURGE_HD int sp_string(const uint8_t* v, int64_t len, int64_t* pos, const uint8_
   *raw_len = i - 1 - *raw_off;
   *pos = i;
   if (key_len >= 0 && !(same && k == key_len)) return SURGE_STATE_DECODE_KEY_MISMATCH;
+  return SURGE_STATE_DECODE_OK;
+}
+
+// The raw span of a JSON string (the bytes between the quotes, as sp_string reports them) -> its unescaped UTF-8.
+// *n_out = the unescaped length; with `out`, bytes [0, min(length, capacity)) are written — never one beyond capacity.
+// The rules are sp_string's (sp_string_unit); a bare quote cannot lie inside a span and is refused as STRING.  Reads
+// raw[0 .. raw_len) only.
+SURGE_HD int sp_unescape(const uint8_t* raw, int64_t raw_len, uint8_t* out, int64_t capacity, int64_t* n_out) {
+  int64_t i = 0, k = 0;
+  *n_out = 0;
+  while (i < raw_len) {
+    uint32_t c = raw[i++];
+    if (c == '"') return SURGE_STATE_DECODE_STRING;
+    uint32_t n = 1;
+    const int rc = sp_string_unit(raw, raw_len, &i, c, &c, &n);
+    if (rc != SURGE_STATE_DECODE_OK) return rc;
+    for (uint32_t b = 0; b < n; ++b) {
+      if (out && k < capacity) out[k] = (uint8_t)sp_utf8_byte(c, n, b);
+      ++k;
+    }
+  }
+  *n_out = k;
   return SURGE_STATE_DECODE_OK;
 }
 

@@ -115,7 +115,7 @@ def encode_states(engine: ReplayEngine, template: JsonTemplate, d_keys_utf8, d_k
             engine._h, c, ctypes.c_void_p(col[0].data_ptr()) if col is not None and col[0].numel() else None,
             ctypes.c_void_p(col[1].data_ptr()) if col is not None else None))
     d_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    cap = int(capacity_hint) if capacity_hint else max(64, 2 * int(d_keys_utf8.numel()) + 64 * n + sum(2 * int(c[0].numel()) for c in strings))
+    cap = int(capacity_hint) if capacity_hint else max(64, 2 * int(d_keys_utf8.numel()) + 64 * n + sum(2 * int(c[0].numel()) for c in strings if c is not None))
     t = template.to_c()
     for _ in range(2):
         d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
@@ -207,3 +207,53 @@ def decode_states(engine: ReplayEngine, template: JsonTemplate, d_values, d_valu
         return res
     engine._check(rc)
     return res
+
+
+# ---- the STR parts of decoded values, kept: spans -> side string columns ------------------------------------------------
+def unescape_json_string(raw: bytes) -> bytes:
+    """The bytes between the quotes of a JSON string -> its UTF-8 (``surge_unescape_json_string``: the routine the device
+    runs on the spans ``decode_states(want_spans=True)`` reports).  Raises ``ValueError`` naming the ``SURGE_STATE_DECODE_*``
+    status for a raw control byte, a bare quote, an unknown escape, a surrogate or a text that ends inside an escape."""
+    raw = bytes(raw)
+    lib = _native.load()
+    n = lib.surge_unescape_json_string(raw, len(raw), None, 0)
+    if n < 0:
+        raise ValueError(f"not the body of a JSON string: {DECODE_STATUS.get(-n, -n)}")
+    out = ctypes.create_string_buffer(max(int(n), 1))
+    lib.surge_unescape_json_string(raw, len(raw), out, n)
+    return out.raw[:n]
+
+
+def merge_state_strings(engine: ReplayEngine, column: int, d_values=None, d_value_off=None, d_agg_idx=None, d_status=None, d_spans=None,
+                        prev=None, n_agg: int = None, capacity_hint: int = 0):
+    """String column ``column`` of the decoded records merged into the column so far (``surge_replay_merge_state_strings``).
+    ``d_values`` / ``d_value_off`` / ``d_agg_idx`` as ``decode_states`` took them, ``d_status`` / ``d_spans`` as it left them
+    (``res[1]``, ``res.spans``); ``prev``: the ``(d_utf8, d_off)`` column so far or ``None``; ``n_agg``: the aggregates the
+    new column covers (default: the engine's).  Per aggregate the winning OK record's unescaped string (empty for a
+    tombstone), else the previous string, else empty.  Without records (``d_value_off=None``) the column is extended to
+    ``n_agg``.  Returns ``(d_utf8, d_off)`` CUDA tensors, ready for ``encode_states(strings=...)``."""
+    import torch
+
+    lib = _native.load()
+    n_agg = engine.n_agg if n_agg is None else int(n_agg)
+    n_rec = 0 if d_value_off is None else int(d_value_off.numel()) - 1
+    n_prev = 0 if prev is None else int(prev[1].numel()) - 1
+    dev = torch.device("cuda", engine.device)
+    ptr = lambda x: ctypes.c_void_p(x.data_ptr()) if x is not None and x.numel() else None  # noqa: E731
+    d_off = torch.empty(n_agg + 1, dtype=torch.int64, device=dev)
+    cap = int(capacity_hint) if capacity_hint else (int(prev[0].numel()) if prev is not None else 0) + (int(d_values.numel()) if d_values is not None else 0)
+    for _ in range(2):
+        d_out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+        total = ctypes.c_int64(0)
+        rc = lib.surge_replay_merge_state_strings(
+            engine._h, int(column), ptr(d_values), ptr(d_value_off) if n_rec else None, n_rec, ptr(d_agg_idx) if n_rec else None,
+            ptr(d_status), ptr(d_spans), ptr(prev[0]) if prev is not None else None, ptr(prev[1]) if prev is not None else None, n_prev, n_agg,
+            ctypes.c_void_p(d_out.data_ptr()), cap, ctypes.c_void_p(d_off.data_ptr()), ctypes.byref(total))
+        if rc == 0:
+            return d_out[: total.value], d_off
+        if rc == -6 and total.value > cap:  # SURGE_E_RANGE: retry with the exact size
+            cap = total.value
+            continue
+        msg = lib.surge_replay_last_error(engine._h)
+        raise ReplayError(rc, msg.decode() if msg else "")
+    raise RuntimeError("merge_state_strings: unreachable")

@@ -532,9 +532,11 @@ class DeviceDecoder:
     are kept as bytes (``state_result()``) and handed to the engine with ``load_states_into``; ``result`` / ``fold_into`` /
     ``stage_into`` are an events decoder's and fail on it (STATE)."""
 
-    def __init__(self, template: Optional[EventJsonTemplate] = None, device: int = 0, stream=None, states: bool = False):
+    def __init__(self, template: Optional[EventJsonTemplate] = None, device: int = 0, stream=None, states: bool = False, keep_strings: bool = False):
         if states and template is not None:
             raise ValueError("DeviceDecoder: states=True is the alternative to an event template")
+        if keep_strings and not states:
+            raise ValueError("DeviceDecoder: keep_strings belongs to a state decoder (states=True)")
         self._lib = _native.load()
         self._h = ctypes.c_void_p()
         self.device = device
@@ -547,6 +549,12 @@ class DeviceDecoder:
             rc = self._lib.surge_device_decoder_create(device, stream, ctypes.byref(c) if c is not None else None, ctypes.byref(self._h))
         if rc != 0:
             raise IngestError(rc, (self._lib.surge_device_decoder_last_error(None) or b"").decode())
+        if keep_strings:  # (before the first load: every load_states_into then merges the STR columns its template names)
+            rc = self._lib.surge_device_decoder_keep_strings(self._h, 1)
+            if rc != 0:
+                msg = (self._lib.surge_device_decoder_last_error(self._h) or b"").decode()
+                self.close()
+                raise IngestError(rc, msg)
 
     def close(self):
         if self._h:
@@ -712,6 +720,33 @@ class DeviceDecoder:
         engine.n_agg = max(engine.n_agg, self.n_keys)  # (grown inside the call)
         self._check(rc)
         return tuple(int(c) for c in counts)
+
+    def state_strings(self):
+        """The STR columns a ``keep_strings=True`` state decoder has kept (``surge_device_decoder_state_strings``): one entry
+        per string column, ``(d_utf8, d_off)`` CUDA tensors viewing the decoder's buffers (valid until the next
+        ``load_states_into`` / ``clear`` / ``close``: clone what has to live longer) — aggregate ``a``'s string is
+        ``d_utf8[d_off[a]:d_off[a+1]]`` — or ``None`` for a column no load has named."""
+        import torch
+
+        from .encode import STRING_COLUMNS
+
+        dev = torch.device("cuda", self.device)
+
+        def view(ptr, count, typestr):
+            iface = {"shape": (count,), "typestr": typestr, "data": (ptr.value, False), "version": 2}
+            return torch.as_tensor(type("_Span", (), {"__cuda_array_interface__": iface})(), device=dev)
+
+        cols = []
+        for c in range(STRING_COLUMNS):
+            pu, po, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
+            self._check(self._lib.surge_device_decoder_state_strings(self._h, c, ctypes.byref(pu), ctypes.byref(po), ctypes.byref(n)))
+            if not po.value:
+                cols.append(None)
+                continue
+            d_off = view(po, n.value + 1, "<i8")
+            total = int(d_off[-1].item())
+            cols.append((view(pu, total, "|u1") if total else torch.zeros(0, dtype=torch.uint8, device=dev), d_off))
+        return cols
 
     def clear(self) -> None:
         self._check(self._lib.surge_device_decoder_clear(self._h))

@@ -228,11 +228,13 @@ class BulkSnapshotPublisher:
     ``keys`` are the aggregate ids in dense-index order; ``template`` declares the model's serialized state."""
 
     def __init__(self, engine, keys: Optional[Sequence[str]], n_partitions: int, template=None, device=None, tables=None,
-                 compression: str = "none", device_framing: bool = True, device_compression: bool = False):
+                 compression: str = "none", device_framing: bool = True, device_compression: bool = False, strings=()):
         """``keys``: aggregate ids in dense-index order; or ``tables = (keys_utf8, key_off, keys_utf16, off16)`` as
         tensors / arrays built without Python strings (large synthetic populations).  ``compression``: "none" or "lz4"
         (the reference producer's ``compression.type``).  ``device_compression``: lz4 batches are framed AND compressed
-        by the ``DeviceFramer`` (needs ``device_framing``); without it they go through the host writer and its compressor."""
+        by the ``DeviceFramer`` (needs ``device_framing``); without it they go through the host writer and its compressor.
+        ``strings``: the side string columns of a template with ``(JP_STR, column)`` parts, as ``encode_states`` takes them
+        (e.g. a resumed store's ``state_string_columns()``); the attribute may be replaced between publishes."""
         import torch
 
         from .encode import JsonTemplate, key_table_utf8
@@ -240,6 +242,7 @@ class BulkSnapshotPublisher:
 
         self.engine, self.n_partitions = engine, n_partitions
         self.template = template or JsonTemplate.counter()
+        self.strings = strings
         self.device = torch.device(device or f"cuda:{engine.device}")
         self.writer = RecordBatchWriter(n_partitions, compression=compression)
         if tables is None:
@@ -293,7 +296,8 @@ class BulkSnapshotPublisher:
         self._pending_kind = None
         eng._check(lib.surge_replay_set_encode_filter(eng._h, ctypes.c_void_p(d_kind.data_ptr())))
         try:
-            d_out, d_off = encode_states(eng, self.template, self.d_keys, self.d_key_off, capacity_hint=max(64, 96 * nv.value + int(self.d_keys.numel())))
+            d_out, d_off = encode_states(eng, self.template, self.d_keys, self.d_key_off, capacity_hint=max(64, 96 * nv.value + int(self.d_keys.numel())) if not self.strings else 0,
+                                          strings=self.strings)
         finally:
             eng._check(lib.surge_replay_set_encode_filter(eng._h, None))
         torch.cuda.synchronize(self.device)
@@ -366,7 +370,8 @@ class BulkSnapshotPublisher:
         eng._check(lib.surge_replay_snapshot_delta(eng._h, ctypes.c_void_p(d_kind.data_ptr()), ctypes.byref(nv), ctypes.byref(nt), 1))
         eng._check(lib.surge_replay_set_encode_filter(eng._h, ctypes.c_void_p(d_kind.data_ptr())))
         try:
-            d_out, d_off = encode_states(eng, self.template, self.d_keys, self.d_key_off, capacity_hint=max(64, 96 * nv.value + int(self.d_keys.numel())))
+            d_out, d_off = encode_states(eng, self.template, self.d_keys, self.d_key_off, capacity_hint=max(64, 96 * nv.value + int(self.d_keys.numel())) if not self.strings else 0,
+                                          strings=self.strings)
         except Exception:
             eng._check(lib.surge_replay_set_encode_filter(eng._h, None))
             eng._check(lib.surge_replay_snapshot_invalidate(eng._h, ctypes.c_void_p(d_kind.data_ptr())))

@@ -46,6 +46,9 @@ class GpuReplayStateStore:
         self.keys = KeyTable()
         self.store_name = f"{business_logic.aggregate_name}AggregateStateStore"  # SurgeStateStoreConsumer.scala:110
         self._restored = False
+        #: the STR columns of the states a resume from the state topic loaded: per string column ``(d_utf8, d_off)`` CUDA
+        #: tensors or ``None`` (``None`` altogether: nothing restored) — see ``state_string_columns``
+        self.state_strings = None
 
     def close(self):
         self.engine.close()
@@ -278,10 +281,12 @@ class GpuReplayStateStore:
         import torch
 
         from . import _native
-        from .encode import JsonTemplate, decode_states, key_table_utf8
+        from .encode import STRING_COLUMNS, JsonTemplate, decode_states, key_table_utf8, merge_state_strings
         from .schema import EVENT_DTYPE
 
         template = template or JsonTemplate.counter()
+        str_columns = _str_columns(template)
+        self.state_strings = None
         agg_idx, values, lens = [], [], []
         for rec in records:
             key, value = (rec.key, rec.value) if hasattr(rec, "key") else rec
@@ -304,12 +309,18 @@ class GpuReplayStateStore:
             d_values = to_dev(np.frombuffer(b"".join(values), dtype=np.uint8).copy()) if off[-1] else torch.zeros(0, dtype=torch.uint8, device=dev)
             defaults = self.model.event_algebra().to_c().default_state
             eng._check(lib.surge_replay_set_decode_base(eng._h, ctypes.byref(defaults)))
+            d_off, d_agg = to_dev(off), to_dev(np.asarray(agg_idx, dtype=np.int64))
             try:
-                res = decode_states(eng, template, d_values, to_dev(off), to_dev(data), to_dev(key_off), to_dev(np.asarray(agg_idx, dtype=np.int64)),
-                                    out=eng.device_state(), raise_on_refused=True)
+                res = decode_states(eng, template, d_values, d_off, to_dev(data), to_dev(key_off), d_agg,
+                                    out=eng.device_state(), want_spans=bool(str_columns), raise_on_refused=True)
             finally:
                 eng._check(lib.surge_replay_set_decode_base(eng._h, None))
             counts = res[2]
+            if str_columns:  # the STR fields the values carry, kept beside the rows
+                self.state_strings = [merge_state_strings(eng, c, d_values, d_off, d_agg, res[1], res.spans, n_agg=n_agg) if c in str_columns else None
+                                      for c in range(STRING_COLUMNS)]
+        if str_columns and self.state_strings is None:
+            self.state_strings = [merge_state_strings(eng, c, n_agg=n_agg) if c in str_columns else None for c in range(STRING_COLUMNS)]
         if n_agg:
             d_kind = torch.zeros(n_agg, dtype=torch.uint8, device=dev)
             nv, nt = ctypes.c_int64(), ctypes.c_int64()
@@ -348,7 +359,9 @@ class GpuReplayStateStore:
         eng.fold()  # no aggregate yet: the loads grow the state for the ids they meet
         depth = 4
         totals = [0, 0, 0, 0]
-        d = DeviceDecoder(states=True, device=eng.device)
+        self.state_strings = None
+        keep = bool(_str_columns(template))  # the STR fields the values carry are kept beside the rows (a template without them pays nothing)
+        d = DeviceDecoder(states=True, device=eng.device, keep_strings=keep)
         defaults = self.model.event_algebra().to_c().default_state
         try:
             eng._check(lib.surge_replay_set_decode_base(eng._h, ctypes.byref(defaults)))
@@ -392,6 +405,8 @@ class GpuReplayStateStore:
                 keys.intern(k)
             counters.update(d.counters())
             self.keys = keys
+            if keep:  # (the decoder's buffers go with it: the columns are cloned out)
+                self.state_strings = [None if col is None else (col[0].clone(), col[1].clone()) for col in d.state_strings()]
         finally:
             eng._check(lib.surge_replay_set_decode_base(eng._h, None))
             d.close()
@@ -407,6 +422,31 @@ class GpuReplayStateStore:
             eng.snapshot()
         counters.update({"rows_written": totals[0], "tombstones": totals[1], "refused": totals[2], "reparsed_on_host": totals[3]})
         return counters
+
+    def state_string_columns(self):
+        """The restored STR columns, extended (``merge_state_strings`` without records: aggregates that appeared after the
+        resume get empty strings — theirs stay the host's) to the engine's current aggregate count: what
+        ``encode.encode_states(strings=...)`` takes.  ``()`` when nothing was restored."""
+        from .encode import merge_state_strings
+
+        if not self.state_strings:
+            return ()
+        n_agg = self.engine.n_agg
+        for c, col in enumerate(self.state_strings):
+            if col is not None and int(col[1].numel()) - 1 < n_agg:
+                self.state_strings[c] = merge_state_strings(self.engine, c, prev=col, n_agg=n_agg)
+        return tuple(self.state_strings)
+
+    def _restored_strings(self, idx: int):
+        """Aggregate ``idx``'s restored strings (one ``bytes`` or ``None`` per column): two slices, no pass over the columns."""
+        out = []
+        for col in self.state_strings:
+            if col is None or idx >= int(col[1].numel()) - 1:
+                out.append(None)
+                continue
+            lo, hi = col[1][idx:idx + 2].tolist()
+            out.append(col[0][lo:hi].cpu().numpy().tobytes())
+        return out
 
     def restore_log(self, log: EventLog, init_state: Optional[np.ndarray] = None, algo: int = ALGO_AUTO) -> None:
         self.keys = log.keys
@@ -449,7 +489,19 @@ class GpuReplayStateStore:
             )
         if not int(raw["flags"]) & STATE_PRESENT:
             return None
+        hook = getattr(self.model, "restore_static_strings", None)
+        if self.state_strings and hook is not None:  # string fields the state topic carried (the model keeps what it already knows)
+            strings = self._restored_strings(idx)
+            if any(x is not None for x in strings):
+                hook(aggregate_id, strings)
         return self.model.state_from_fixed(aggregate_id, raw)
+
+
+def _str_columns(template) -> set:
+    """The string columns a ``JsonTemplate``'s ``(JP_STR, column)`` parts name."""
+    from .encode import JP_STR
+
+    return {int(p[1]) for p in template.parts if isinstance(p, tuple) and int(p[0]) == JP_STR}
 
 
 class GpuReplayKeyValueStore:
