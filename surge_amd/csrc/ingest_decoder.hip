@@ -943,7 +943,7 @@ int32_t stage2(surge_device_decoder* d, PushSlot& s, bool wait) {
       uint8_t ev[16];
       std::vector<uint8_t> value((size_t)m.val_len + 1);
       PCHK(hipMemcpy(value.data(), dby + m.val_off, (size_t)m.val_len, hipMemcpyDeviceToHost));  // (an LZ4 section exists decompressed on the device only)
-      if (surge_event_json_decode(&d->h_tmpl, value.data(), m.val_len, ev) != 0)  // (the device accepted the number's spelling: cannot happen)
+      if (surge_event_json_decode(&d->h_tmpl, value.data(), m.val_len, ev) != 0)  // (the device accepted the number's spelling and its length: cannot happen)
         return poison(dfail(d, SURGE_E_CORRUPT, "record at offset " + std::to_string(m.offset) + ": " + surge_event_json_last_error()));
       PCHK(hipMemcpy((uint8_t*)d->r_ev.p + (size_t)(d->n_records + pos) * 16, ev, 16, hipMemcpyHostToDevice));
     }

@@ -261,6 +261,7 @@ __device__ uint32_t decode_json_event(const EvjDevice* __restrict__ t, const sur
       if (parse_i32(s, l, &a) != 0) return RS_FIELD;
       raw = (uint64_t)(uint32_t)a;
     } else {
+      if (l >= 400) return RS_FIELD;  // surge_parse_f64_json refuses a number of 400 bytes or more before it parses: the host is the rule
       const int rc = surge::f64_parse_json_number((const uint8_t*)s, l, ptab, &raw);  // (a flat pointer: the parser is shared with the host)
       if (rc == surge::F64_PARSE_MALFORMED) return RS_FIELD;
       if (rc == surge::F64_PARSE_AMBIGUOUS) status = RS_F64_HOST;  // type and seq are final; the host fills in the payload
