@@ -1,5 +1,5 @@
 // f64_text.cpp — the power-of-5 tables of f64_text.h, computed once with exact integer arithmetic, and the host entry
-// point of the Double -> JSON text conversion (the device copy of the tables is made by engine.hip).
+// point of the Double -> JSON text conversion (the device copy of the tables is made by engine_states.hip).
 #include "f64_text.h"
 #include "f64_parse.h"
 
