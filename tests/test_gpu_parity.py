@@ -11,6 +11,7 @@ import pytest
 
 from golden_util import NAMES, load_golden
 from oracle import oracle
+from state_out_cases import protobuf_state_class as _protobuf_state_class
 from surge_amd import schema as S
 from surge_amd import synth
 from fixture_models import BANK_ACCOUNT_ALGEBRA, COUNTER_ALGEBRA
@@ -712,21 +713,6 @@ def test_point_reads_tolerate_32_concurrent_readers(publish_mirror):
 
         with ThreadPoolExecutor(max_workers=32) as pool:
             assert sum(pool.map(reader, range(32))) == 0
-
-
-def _protobuf_state_class():
-    """message State { string aggregateId = 1; bytes payload = 2; } (multilanguage-protocol.proto:7-10), built with
-    the real protobuf runtime so the expected bytes come from Google's encoder, not from a restatement."""
-    from google.protobuf import descriptor_pb2, descriptor_pool, message_factory
-
-    fd = descriptor_pb2.FileDescriptorProto(name="surge_multilanguage_state.proto", syntax="proto3")
-    m = fd.message_type.add(name="State")
-    F = descriptor_pb2.FieldDescriptorProto
-    m.field.add(name="aggregateId", number=1, type=F.TYPE_STRING, label=F.LABEL_OPTIONAL)
-    m.field.add(name="payload", number=2, type=F.TYPE_BYTES, label=F.LABEL_OPTIONAL)
-    pool = descriptor_pool.DescriptorPool()
-    pool.Add(fd)
-    return message_factory.GetMessageClass(pool.FindMessageTypeByName("State"))
 
 
 @pytest.mark.gpu
