@@ -1,6 +1,6 @@
 // ingest.cpp — events-topic ingest, host side of libsurge_replay.so.
-// Kafka RecordBatch v2 + LZ4 frame + read_committed, restated from the published formats (kafka-clients
-// 3.2.3 is not vendored under /root/reference: parity unpinned, see include/surge_ingest.h).
+// Kafka RecordBatch v2 + read_committed, restated from the published formats (kafka-clients 3.2.3 is not vendored with the
+// reference: parity unpinned, see include/surge_ingest.h).  The LZ4 frames of compressed batches are read by lz4_frame.cpp.
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -13,7 +13,9 @@
 #include <condition_variable>
 #include <functional>
 #include <mutex>
+#if defined(__x86_64__) || defined(__i386__)
 #include <immintrin.h>
+#endif
 #include <pthread.h>
 #include <thread>
 #include <vector>
@@ -24,6 +26,11 @@ namespace {
 
 constexpr int32_t OK = 0, E_INVALID = -1, E_NOMEM = -4, E_UNSUPPORTED = -5;
 
+// surge_ingest_counters' eight slots, in the order include/surge_ingest.h gives them
+enum Counter { C_BATCHES, C_RECORDS_DECODED, C_RECORDS_DELIVERED, C_RECORDS_ABORTED, C_CONTROL_BATCHES, C_FLUSH_SKIPPED, C_BYTES_DECOMPRESSED,
+               C_OPEN_TRANSACTIONS, C_COUNT };
+static_assert(C_COUNT == 8, "surge_ingest_counters hands out int64_t[8]");
+
 thread_local std::string g_err;
 
 struct Rec {
@@ -33,7 +40,6 @@ struct Rec {
 
 struct Batch {
   int64_t producer_id = -1;
-  bool transactional = false;
   int decided = 1;  // 0 pending (open transaction), 1 committed / non-transactional, 2 aborted
   std::vector<Rec> recs;
   size_t next = 0;  // first record not yet drained
@@ -134,9 +140,6 @@ struct Reader {
     return true;
   }
   uint8_t u8() { return need(1) ? *p++ : 0; }
-  int16_t i16() { if (!need(2)) return 0; int16_t v = (int16_t)((p[0] << 8) | p[1]); p += 2; return v; }
-  int32_t i32() { if (!need(4)) return 0; uint32_t v = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; p += 4; return (int32_t)v; }
-  int64_t i64() { if (!need(8)) return 0; uint64_t v = 0; for (int i = 0; i < 8; ++i) v = (v << 8) | p[i]; p += 8; return (int64_t)v; }
   // zig-zag varint (protobuf style), as Kafka's ByteUtils.readVarlong
   int64_t varlong() {
     uint64_t v = 0;
@@ -152,56 +155,53 @@ struct Reader {
   }
 };
 
-// LZ4 block (sequence) decoder into dst[*op .. cap); matches may reach back into everything already written.
-// LZ4_OK, LZ4_CORRUPT (malformed input) or LZ4_NOSPACE (dst too small: the caller grows it and retries).
-enum { LZ4_OK = 0, LZ4_CORRUPT = 1, LZ4_NOSPACE = 2 };
-int lz4_block(const uint8_t* ip, const uint8_t* iend, uint8_t* dst, int64_t* op_io, int64_t cap) {
-  int64_t op = *op_io;
-  while (ip < iend) {
-    const uint8_t token = *ip++;
-    int64_t lit = token >> 4;
-    if (lit == 15) {
-      uint8_t b;
-      do {
-        if (ip >= iend) return LZ4_CORRUPT;
-        b = *ip++;
-        lit += b;
-      } while (b == 255);
-    }
-    if (iend - ip < lit) return LZ4_CORRUPT;
-    if (cap - op < lit) return LZ4_NOSPACE;
-    std::memcpy(dst + op, ip, (size_t)lit);
-    ip += lit;
-    op += lit;
-    if (ip >= iend) break;  // the last sequence carries literals only
-    if (iend - ip < 2) return LZ4_CORRUPT;
-    const int64_t offset = ip[0] | (ip[1] << 8);
-    ip += 2;
-    if (offset == 0 || offset > op) return LZ4_CORRUPT;
-    int64_t ml = token & 15;
-    if (ml == 15) {
-      uint8_t b;
-      do {
-        if (ip >= iend) return LZ4_CORRUPT;
-        b = *ip++;
-        ml += b;
-      } while (b == 255);
-    }
-    ml += 4;
-    if (cap - op < ml) return LZ4_NOSPACE;
-    if (offset >= ml) {
-      std::memcpy(dst + op, dst + op - offset, (size_t)ml);
-    } else if (offset >= 8) {  // overlapping, but every 8-byte step reads bytes already final
-      int64_t k = 0;
-      for (; k + 8 <= ml; k += 8) std::memcpy(dst + op + k, dst + op + k - offset, 8);
-      for (; k < ml; ++k) dst[op + k] = dst[op + k - offset];
-    } else {
-      for (int64_t k = 0; k < ml; ++k) dst[op + k] = dst[op + k - offset];  // short period: the overlap is the point
-    }
-    op += ml;
-  }
-  *op_io = op;
-  return LZ4_OK;
+// A record batch's header (message format v2: the 61 bytes in front of the records section).
+struct BatchHeader {
+  int64_t base_offset, producer_id;
+  int32_t batch_len, count;  // batch_len: the bytes behind the length field (the batch spans 12 + batch_len)
+  uint32_t crc;
+  int16_t attrs;
+  uint8_t magic;
+  const uint8_t *crc_from, *recs;  // what the CRC-32C covers (attributes .. end of the batch); the records section
+  int64_t crc_len, recs_len;
+  int64_t size() const { return 12 + (int64_t)batch_len; }
+  int codec() const { return attrs & 7; }
+  bool transactional() const { return attrs & 0x10; }
+  bool control() const { return attrs & 0x20; }
+};
+
+// What stands at data + pos: a whole batch; a cut one (fewer than 12 bytes, or fewer than its length says: wait for more); or
+// a length below the v2 header's.  Every walk over a buffer's batches takes its stop rule from here.
+enum class HeaderRead { WHOLE, CUT, SHORT };
+constexpr int32_t kHeaderBehindLength = 49;  // partitionLeaderEpoch .. recordCount
+
+inline uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
+inline uint64_t be64(const uint8_t* p) { return ((uint64_t)be32(p) << 32) | be32(p + 4); }
+
+// ... the length field alone (the first 12 bytes of the header are all it reads)
+inline HeaderRead read_batch_length(const uint8_t* data, int64_t len, int64_t pos, int32_t* batch_len) {
+  if (len - pos < 12) return HeaderRead::CUT;
+  *batch_len = (int32_t)be32(data + pos + 8);
+  if (*batch_len < kHeaderBehindLength) return HeaderRead::SHORT;
+  return len - pos - 12 < *batch_len ? HeaderRead::CUT : HeaderRead::WHOLE;
+}
+
+// ... and the header (of a WHOLE batch every field lies inside it, whatever the magic byte says the layout is)
+inline HeaderRead read_batch_header(const uint8_t* data, int64_t len, int64_t pos, BatchHeader* h) {
+  const HeaderRead got = read_batch_length(data, len, pos, &h->batch_len);
+  if (got != HeaderRead::WHOLE) return got;
+  const uint8_t* p = data + pos;
+  h->base_offset = (int64_t)be64(p);
+  h->magic = p[16];  // behind partitionLeaderEpoch
+  h->crc = be32(p + 17);
+  h->crc_from = p + 21;
+  h->crc_len = (int64_t)h->batch_len - 9;
+  h->attrs = (int16_t)((p[21] << 8) | p[22]);
+  h->producer_id = (int64_t)be64(p + 43);  // behind lastOffsetDelta, baseTimestamp, maxTimestamp
+  h->count = (int32_t)be32(p + 57);        // behind producerEpoch, baseSequence
+  h->recs = p + 61;
+  h->recs_len = (int64_t)h->batch_len - kHeaderBehindLength;
+  return got;
 }
 
 }  // namespace
@@ -220,58 +220,47 @@ struct Arena {
   Arena() = default;
   Arena(const Arena&) = delete;
   Arena& operator=(const Arena&) = delete;
-  ~Arena() { drop(); }
-  void drop() {
+  ~Arena() {
     if (p && !external) (release ? release : std::free)(p);
-    p = nullptr;
-    n = cap = 0;
   }
-  void view(uint8_t* at, size_t bytes) {
-    external = true;
-    p = at;
-    cap = bytes;
-    n = 0;
-  }
-  void reserve(size_t want) {  // an EMPTY arena gets room for `want` bytes in one allocation
-    if (want <= cap) return;
-    size_t c = cap ? cap : (size_t)1 << 16;
-    while (c < want) c += c / 2 + 4096;
-    uint8_t* fresh = (uint8_t*)(alloc ? alloc(c) : std::malloc(c));
-    if (!fresh) throw std::bad_alloc();
-    if (n) std::memcpy(fresh, p, n);
-    if (p) (release ? release : std::free)(p);
-    p = fresh;
-    cap = c;
-  }
-  void reserve_exact(size_t want) {  // an EMPTY arena gets exactly `want` bytes (a group's slabs: page-locked memory is not cheap)
-    if (want <= cap) return;
-    uint8_t* fresh = (uint8_t*)(alloc ? alloc(want) : std::malloc(want));
-    if (!fresh) throw std::bad_alloc();
-    if (p) (release ? release : std::free)(p);
-    p = fresh;
-    n = 0;
-    cap = want;
-  }
+  void view(uint8_t* at, size_t bytes) { external = true; p = at; cap = bytes; n = 0; }
   size_t size() const { return n; }
   const uint8_t* data() const { return p; }
   uint8_t* data() { return p; }
   void clear() { n = 0; }
-  void append(const uint8_t* src, size_t len) {
+  // Three ways to choose a capacity over one re-allocation step (surge_ingest_group_slab_bytes shows the capacities).
+  void reserve(size_t want) {  // room for `want` bytes in one allocation, with half as much again to spare; the contents stay
+    if (want <= cap) return;
+    size_t c = cap ? cap : (size_t)1 << 16;
+    while (c < want) c += c / 2 + 4096;
+    regrow(c, n);
+  }
+  void reserve_exact(size_t want) {  // exactly `want` bytes and EMPTY when it has to grow (a group's slabs: page-locked memory is not cheap)
+    if (want <= cap) return;
+    regrow(want, 0);
+  }
+  void append(const uint8_t* src, size_t len) {  // doubles its way up
     if (n + len > cap) {
       // a group sizes its members' slices for the whole feed; only host-side LZ4 (a group without SURGE_INGEST_DEVICE_LZ4)
       // can outgrow one: surge_ingest_group_feed undoes the feed and runs it again with more room
       if (external) throw SliceOverflow();
-      size_t want = cap ? cap * 2 : (size_t)1 << 16;
-      while (want < n + len) want *= 2;
-      uint8_t* fresh = (uint8_t*)(alloc ? alloc(want) : std::malloc(want));
-      if (!fresh) throw std::bad_alloc();
-      if (n) std::memcpy(fresh, p, n);
-      if (p) (release ? release : std::free)(p);
-      p = fresh;
-      cap = want;
+      size_t c = cap ? cap * 2 : (size_t)1 << 16;
+      while (c < n + len) c *= 2;
+      regrow(c, n);
     }
     if (len) std::memcpy(p + n, src, len);
     n += len;
+  }
+
+ private:
+  void regrow(size_t c, size_t keep) {  // `c` bytes from the allocator; the first `keep` bytes move along
+    uint8_t* fresh = (uint8_t*)(alloc ? alloc(c) : std::malloc(c));
+    if (!fresh) throw std::bad_alloc();
+    if (keep) std::memcpy(fresh, p, keep);
+    if (p) (release ? release : std::free)(p);
+    p = fresh;
+    n = keep;
+    cap = c;
   }
 };
 
@@ -304,7 +293,7 @@ struct surge_ingest {
   std::vector<uint64_t> key_hash;  // their hashes
   std::vector<int64_t> slots;      // open-addressing index over keys (power-of-two size, -1 = empty)
   std::vector<uint8_t> scratch;
-  int64_t counters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int64_t counters[C_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 namespace {
@@ -381,11 +370,12 @@ int64_t ready_count(const surge_ingest* g) {
   return n;
 }
 
-int32_t parse_records(surge_ingest* g, Batch& b, const uint8_t* data, int64_t len, int32_t count, int64_t base_offset,
-                      bool control, int* control_type) {
+// h's records, as they stand at data[0, len), into b (a control batch's: the marker's type into *control_type)
+int32_t parse_records(surge_ingest* g, Batch& b, const BatchHeader& h, const uint8_t* data, int64_t len, int* control_type) {
   Reader r{data, data + len};
-  if (count > 0 && !control) b.recs.reserve((size_t)(count < 65536 ? count : 65536));
-  for (int32_t i = 0; i < count; ++i) {
+  const bool control = h.control();
+  if (h.count > 0 && !control) b.recs.reserve((size_t)(h.count < 65536 ? h.count : 65536));
+  for (int32_t i = 0; i < h.count; ++i) {
     const int64_t rlen = r.varlong();
     if (!r.ok || rlen < 0 || !r.need(rlen)) return fail(g, SURGE_E_CORRUPT, "record length runs past the batch");
     Reader q{r.p, r.p + rlen};
@@ -411,18 +401,18 @@ int32_t parse_records(surge_ingest* g, Batch& b, const uint8_t* data, int64_t le
       if (!q.ok || hv < -1 || (hv > 0 && !q.need(hv))) return fail(g, SURGE_E_CORRUPT, "bad header value");
       if (hv > 0) q.p += hv;
     }
-    g->counters[1] += 1;
+    g->counters[C_RECORDS_DECODED] += 1;
     if (control) {
       // control record key: version int16, type int16 (0 = ABORT, 1 = COMMIT)
       if (klen >= 4) *control_type = (key[2] << 8) | key[3];
       continue;
     }
     if (klen == 0 && vlen == 0) {  // the producer's "flush" record (KafkaProducerActorImpl.scala:322-329)
-      g->counters[5] += 1;
+      g->counters[C_FLUSH_SKIPPED] += 1;
       continue;
     }
     Rec rec;
-    rec.offset = base_offset + offset_delta;
+    rec.offset = h.base_offset + offset_delta;
     rec.key_len = (int32_t)klen;
     rec.value_len = (int32_t)vlen;
     rec.key_off = (int64_t)g->arena_now().size();
@@ -433,6 +423,242 @@ int32_t parse_records(surge_ingest* g, Batch& b, const uint8_t* data, int64_t le
                                         // still-open transactions never enter the key table
     b.recs.push_back(rec);
   }
+  return OK;
+}
+
+// the bytes of the sections a FRAMES framer still holds (open transactions, batches not drained yet)
+int64_t queued_section_bytes(const surge_ingest& g) {
+  int64_t queued = 0;
+  for (const Batch& qb : g.queue) queued += qb.sect_off >= 0 ? qb.sect_len : 0;
+  return queued;
+}
+
+// The records deliverable from the head of the queue, up to `max` of them: the walk stops at an open transaction (nothing
+// behind it is stable yet) and passes aborted batches.  fn(rec, k) gets the k-th of them and answers false to refuse it,
+// which ends the walk with -1; otherwise the count comes back.  kPop: what was visited leaves the queue, and the batches
+// that are exhausted or aborted in front of it go with it; without it the queue stays as it is.
+template <bool kPop, class Fn>
+inline int64_t visit_ready(surge_ingest* g, int64_t max, Fn&& fn) {
+  int64_t n = 0;
+  size_t at = 0;  // (a popping walk only ever looks at the front)
+  while (n < max && at < g->queue.size()) {
+    Batch& b = g->queue[at];
+    if (b.decided == 0) break;
+    if (b.decided == 1) {
+      size_t i = b.next;
+      for (; n < max && i < b.recs.size(); ++i, ++n)
+        if (!fn(b.recs[i], n)) return -1;
+      if (kPop) b.next = i;
+    }
+    if (!kPop) ++at;
+    else if (b.decided == 2 || b.next == b.recs.size()) g->queue.pop_front();
+  }
+  return n;
+}
+
+constexpr const char* kFramesOnly = "this decoder frames batches for a surge_device_decoder (SURGE_INGEST_FRAMES): use surge_ingest_drain_sections";
+
+int32_t delivered(surge_ingest* g, int64_t n, int64_t* n_out) {
+  g->counters[C_RECORDS_DELIVERED] += n;
+  *n_out = n;
+  return OK;
+}
+
+// For each whole batch at the front of data[0, len) whether its CRC-32C holds.  The walk stops where surge_ingest_feed's
+// stops for good — both read their headers with read_batch_header — so verdict k is batch k's.
+void verify_crcs_in_parallel(const uint8_t* data, int64_t len, int n_threads, std::vector<uint8_t>* ok) try {
+  std::vector<BatchHeader> heads;
+  BatchHeader h;
+  for (int64_t pos = 0; read_batch_header(data, len, pos, &h) == HeaderRead::WHOLE && h.magic == 2; pos += h.size()) heads.push_back(h);
+  ok->assign(heads.size(), 0);
+  if (heads.empty()) return;
+  (void)surge_crc32c((const uint8_t*)"", 0);  // initialise the dispatch / tables before threads race for them
+  std::atomic<size_t> next{0};
+  auto work = [&]() {
+    constexpr size_t kGrab = 32;
+    for (size_t b = next.fetch_add(kGrab); b < heads.size(); b = next.fetch_add(kGrab))
+      for (size_t k = b; k < heads.size() && k < b + kGrab; ++k) (*ok)[k] = surge_crc32c(heads[k].crc_from, heads[k].crc_len) == heads[k].crc;
+  };
+  std::vector<std::thread> th;
+  try {
+    for (int t = 1; t < n_threads; ++t) th.emplace_back(work);
+  } catch (...) {  // the threads that did start, and this one, do the work
+  }
+  work();
+  for (std::thread& t : th) t.join();
+} catch (...) {  // no memory for the lists: no verdicts, the walk computes the CRCs itself
+  ok->clear();
+}
+
+// FRAMES, a feed that follows a drain (or any feed of a group's member): on to the next arena.  The sections still queued (open
+// transactions, undrained batches) move along, the ones the last drain handed out stay untouched in the arena this feed leaves
+// behind (valid through the five feeds after it).
+void rotate_arena(surge_ingest* g, int64_t feed_len) {
+  const int to = (g->cur + 1) % surge_ingest::kArenas;
+  Arena& next = g->grouped ? g->ext[to] : g->arenas[to];
+  const Arena& prev = g->arena_now();
+  if (g->grouped) {
+    next.view(g->ext_next, g->ext_next_cap);
+  } else {  // room for the whole feed at once: a page-locked arena that doubles its way up costs an allocation per step
+    next.clear();
+    next.reserve((size_t)queued_section_bytes(*g) + (size_t)feed_len);
+  }
+  for (Batch& qb : g->queue) {
+    if (qb.sect_off < 0) continue;
+    const int64_t at = (int64_t)next.size();
+    next.append(prev.data() + qb.sect_off, (size_t)qb.sect_len);
+    qb.sect_off = at;
+  }
+  g->cur = to;
+  g->handed_out = false;
+}
+
+// An lz4 batch's frame, decompressed on the host into g->scratch: *recs / *recs_len then name the records themselves.
+int32_t host_lz4(surge_ingest* g, const uint8_t** recs, int64_t* recs_len) {
+  // first guess: the frame's content-size field when the producer wrote one, else 8x (Kafka's LZ4 output
+  // stream omits it); a too-small guess comes back as -6 (out of space) and is grown, never as "corrupt"
+  const uint8_t* frame = *recs;
+  const int64_t frame_len = *recs_len;
+  int64_t cap = frame_len * 8 + 1024;
+  if (frame_len >= 15 && (frame[4] & 0x08)) {
+    uint64_t cs = 0;
+    for (int k = 7; k >= 0; --k) cs = (cs << 8) | frame[6 + k];
+    if (cs > 0 && cs <= (1ull << 31)) cap = (int64_t)cs;
+  }
+  int64_t got;
+  while (true) {
+    g->scratch.resize((size_t)cap);
+    got = surge_lz4_frame_decompress(frame, frame_len, g->scratch.data(), cap);
+    if (got != -6) break;
+    cap *= 4;
+    if (cap > (1ll << 31)) return fail(g, SURGE_E_CORRUPT, "LZ4 batch expands beyond 2 GiB");
+  }
+  if (got < 0) return fail(g, SURGE_E_CORRUPT, "bad LZ4 frame in record batch");
+  g->counters[C_BYTES_DECOMPRESSED] += got;
+  *recs = g->scratch.data();
+  *recs_len = got;
+  return OK;
+}
+
+// FRAMES: a data batch's records section travels as it is (the device chains and parses the records): copied into the arena,
+// with defer_crc behind the 8-byte prefix; or, in place, left where the fetch response was received (inside the slab this
+// slice is a view of), with defer_crc together with the 44 bytes in front of it (Batch::crc_prefix).
+void place_section(surge_ingest* g, Batch& b, const BatchHeader& h, const uint8_t* recs, int64_t recs_len, int sect_codec, bool defer_crc) {
+  Arena& arena = g->arena_now();
+  b.base_offset = h.base_offset;
+  b.count = h.count;
+  b.sect_codec = sect_codec;
+  if (g->inplace) {
+    b.crc_prefix = defer_crc ? 44 : 0;
+    b.sect_off = (int64_t)(recs - arena.data()) - b.crc_prefix;
+  } else {
+    b.sect_off = (int64_t)arena.size();
+    if (defer_crc) {
+      const uint32_t pre[2] = {h.crc, ~surge_crc32c(h.crc_from, 40)};  // the register (not finalised) after attributes .. recordCount
+      arena.append((const uint8_t*)pre, 8);
+      b.crc_prefix = 8;
+    }
+    arena.append(recs, (size_t)recs_len);
+  }
+  b.sect_len = recs_len + b.crc_prefix;
+  g->counters[C_RECORDS_DECODED] += h.count;
+}
+
+// An ABORT (0) / COMMIT (1) marker ends its producer's open transaction.  *n_open: the open transactions' batches in the queue
+// — few; the marker looks for its producer's among them from the back and stops at the oldest open one (the first version
+// walked the whole queue per marker: every batch of the feed).
+void apply_marker(surge_ingest* g, int64_t producer_id, int control_type, int64_t* n_open) {
+  int64_t still_to_see = *n_open;
+  for (auto qb = g->queue.rbegin(); qb != g->queue.rend() && still_to_see > 0; ++qb) {
+    if (qb->decided != 0) continue;
+    --still_to_see;
+    if (qb->producer_id != producer_id) continue;
+    qb->decided = control_type == 1 ? 1 : 2;
+    --*n_open;
+    if (control_type == 0) g->counters[C_RECORDS_ABORTED] += qb->sect_off >= 0 ? (int64_t)qb->count : (int64_t)qb->recs.size();
+  }
+}
+
+// One whole batch of a feed: checked, its records parsed (or, FRAMES, its section placed), queued; a marker decides the
+// transactions it ends.  crc_verdict: the batch's CRC-32C verified up front (null: not yet).
+int32_t take_batch(surge_ingest* g, const BatchHeader& h, const uint8_t* crc_verdict, int64_t* n_open) {
+  if (h.magic != 2) return fail(g, E_UNSUPPORTED, "only message format v2 (magic 2) is supported");
+  // SURGE_INGEST_DEVICE_CRC: the CRC of a data batch is only STARTED here — over the 40 header bytes it covers in front of the
+  // records section (place_section) — and finished where the section's bytes go anyway: on the device.  What this thread
+  // still touches of a batch is its header.
+  const bool defer_crc = g->device_crc && !h.control();
+  if (!defer_crc && !(crc_verdict ? *crc_verdict != 0 : surge_crc32c(h.crc_from, h.crc_len) == h.crc))
+    return fail(g, SURGE_E_CORRUPT, "record batch CRC-32C mismatch");
+  if (h.count < 0) return fail(g, SURGE_E_CORRUPT, "truncated batch header");
+  // (a header that is only verified later, on the device, must not drive anything out of bounds before that: a record takes
+  // at least 7 bytes, and LZ4 expands at most 255 x)
+  if (defer_crc && (int64_t)h.count > (h.recs_len / 7 + 1) * (h.codec() ? 255 : 1))
+    return fail(g, SURGE_E_CORRUPT, "recordCount impossible for the batch's size (damaged header)");
+  const uint8_t* recs = h.recs;
+  int64_t recs_len = h.recs_len;
+  int sect_codec = 0;
+  if (h.codec() == 3 && g->device_lz4 && !h.control()) {
+    sect_codec = 3;  // the frame travels as it is: the device decoder walks its blocks and decodes them on the GPU
+  } else if (h.codec() == 3 && g->inplace && !h.control()) {
+    return fail(g, E_UNSUPPORTED, "an in-place feed leaves the sections where they were received: lz4 topics need SURGE_INGEST_DEVICE_LZ4");
+  } else if (h.codec() == 3) {
+    const int32_t rc = host_lz4(g, &recs, &recs_len);
+    if (rc != OK) return rc;
+  } else if (h.codec() != 0) {
+    return fail(g, E_UNSUPPORTED, "compression codec not supported (only none and lz4; the reference publishes lz4)");
+  }
+  Batch b;
+  b.producer_id = h.producer_id;
+  int control_type = -1;
+  if (g->frames && !h.control()) {
+    if (defer_crc && recs != h.recs) return fail(g, E_UNSUPPORTED, "SURGE_INGEST_DEVICE_CRC needs the sections to travel as they are on the wire (SURGE_INGEST_DEVICE_LZ4 for lz4 topics)");
+    place_section(g, b, h, recs, recs_len, sect_codec, defer_crc);
+  } else {
+    const int32_t rc = parse_records(g, b, h, recs, recs_len, &control_type);
+    if (rc != OK) return rc;
+  }
+  g->counters[C_BATCHES] += 1;
+  if (h.control()) {
+    g->counters[C_CONTROL_BATCHES] += 1;
+    if (control_type == 0 || control_type == 1) apply_marker(g, h.producer_id, control_type, n_open);
+    return OK;
+  }
+  b.decided = (h.transactional() && g->isolation == SURGE_INGEST_READ_COMMITTED) ? 0 : 1;
+  if (!b.recs.empty() || b.count > 0) {
+    *n_open += b.decided == 0;
+    g->queue.push_back(std::move(b));
+  }
+  return OK;
+}
+
+// surge_ingest_feed's walk.  *pos: where the first batch not consumed begins — a failure in batch k leaves batches 0..k-1 of
+// this buffer decoded and queued: they are reported as consumed, so a caller that retries (or skips the bad batch) never
+// feeds them twice.  What throws (no memory, a full slice) leaves *pos where it stands.
+int32_t feed_batches(surge_ingest* g, const uint8_t* data, int64_t len, int64_t* pos) {
+  if (g->frames && (g->handed_out || g->grouped)) {
+    rotate_arena(g, len);  // (a feed that follows no drain keeps appending where the last one stopped: nothing is copied)
+  } else if (g->queue.empty()) {
+    // nothing queued and (FRAMES: no span of this arena handed out since the switch) nothing to keep: start over
+    g->arena_now().clear();
+  }
+  // With more than one CRC thread the batches' checksums are verified up front, in parallel (a batch's CRC depends on
+  // nothing but its own bytes; the walk below then looks the verdicts up in order, so what is reported, and when, is
+  // exactly what the one-thread walk reports).
+  std::vector<uint8_t> crc_ok;
+  if (g->crc_threads > 1 && len >= (1 << 20) && !g->device_crc) verify_crcs_in_parallel(data, len, g->crc_threads, &crc_ok);
+  int64_t n_open = 0;
+  for (const Batch& qb : g->queue) n_open += qb.decided == 0;
+  BatchHeader h;
+  for (size_t batch_no = 0;; ++batch_no, *pos += h.size()) {
+    const HeaderRead got = read_batch_header(data, len, *pos, &h);
+    if (got == HeaderRead::SHORT) return fail(g, SURGE_E_CORRUPT, "batchLength below the v2 header size");
+    if (got == HeaderRead::CUT) break;  // partial batch: wait for more bytes
+    __builtin_prefetch(h.recs + h.recs_len);  // the next batch's header: a fresh cache line every few KB of a buffer that was just received
+    __builtin_prefetch(h.recs + h.recs_len + 64);
+    const int32_t rc = take_batch(g, h, batch_no < crc_ok.size() ? &crc_ok[batch_no] : nullptr, &n_open);
+    if (rc != OK) return rc;
+  }
+  g->counters[C_OPEN_TRANSACTIONS] = n_open;
   return OK;
 }
 
@@ -465,62 +691,19 @@ uint32_t surge_crc32c_portable(const uint8_t* data, int64_t len) {
   return c ^ 0xffffffffu;
 }
 
-int64_t surge_lz4_frame_decompress(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap) {
-  if (!src || n < 7 || (!dst && cap > 0)) return E_INVALID;
-  const uint8_t* p = src;
-  const uint8_t* end = src + n;
-  if (!(p[0] == 0x04 && p[1] == 0x22 && p[2] == 0x4D && p[3] == 0x18)) return SURGE_E_CORRUPT;  // 0x184D2204 LE
-  p += 4;
-  const uint8_t flg = *p++;
-  p++;  // BD: block maximum size, not needed to decode
-  if ((flg >> 6) != 1) return SURGE_E_CORRUPT;  // version 01
-  const bool block_checksum = flg & 0x10, content_size = flg & 0x08, content_checksum = flg & 0x04, dict_id = flg & 0x01;
-  const uint8_t* const descriptor = p - 2;
-  if (content_size) p += 8;
-  if (dict_id) p += 4;
-  if (p >= end) return SURGE_E_CORRUPT;
-  // header checksum: second byte of XXH32(descriptor); kafka-clients verifies it for message format v2
-  if (*p != (uint8_t)(surge_xxh32(descriptor, (int64_t)(p - descriptor), 0) >> 8)) return SURGE_E_CORRUPT;
-  p += 1;
-  int64_t op = 0;
-  while (true) {
-    if (end - p < 4) return SURGE_E_CORRUPT;
-    const uint32_t bs = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-    p += 4;
-    if (bs == 0) break;  // EndMark
-    const uint32_t size = bs & 0x7fffffffu;
-    if ((int64_t)size > end - p) return SURGE_E_CORRUPT;
-    if (bs & 0x80000000u) {  // stored uncompressed
-      if (cap - op < (int64_t)size) return -6;
-      std::memcpy(dst + op, p, size);
-      op += size;
-    } else {
-      const int rc = lz4_block(p, p + size, dst, &op, cap);
-      if (rc == LZ4_NOSPACE) return -6;
-      if (rc != LZ4_OK) return SURGE_E_CORRUPT;
-    }
-    p += size;
-    if (block_checksum) p += 4;
-  }
-  if (content_checksum) p += 4;
-  return op;
-}
-
 int32_t surge_ingest_create(int32_t isolation_level, surge_ingest** out) {
   if (!out) return fail(nullptr, E_INVALID, "out is NULL");
   *out = nullptr;
-  const bool frames = (isolation_level & (SURGE_INGEST_FRAMES | SURGE_INGEST_DEVICE_LZ4 | SURGE_INGEST_DEVICE_CRC)) != 0;
-  const bool device_lz4 = (isolation_level & SURGE_INGEST_DEVICE_LZ4) != 0;
-  const bool device_crc = (isolation_level & SURGE_INGEST_DEVICE_CRC) != 0;
-  isolation_level &= ~(SURGE_INGEST_FRAMES | SURGE_INGEST_DEVICE_LZ4 | SURGE_INGEST_DEVICE_CRC);
+  const int32_t flags = isolation_level & (SURGE_INGEST_FRAMES | SURGE_INGEST_DEVICE_LZ4 | SURGE_INGEST_DEVICE_CRC);
+  isolation_level &= ~flags;
   if (isolation_level != SURGE_INGEST_READ_UNCOMMITTED && isolation_level != SURGE_INGEST_READ_COMMITTED)
     return fail(nullptr, E_INVALID, "unknown isolation level");
   surge_ingest* g = new (std::nothrow) surge_ingest();
   if (!g) return fail(nullptr, E_NOMEM, "out of host memory");
   g->isolation = isolation_level;
-  g->frames = frames;
-  g->device_lz4 = device_lz4;
-  g->device_crc = device_crc;
+  g->frames = flags != 0;
+  g->device_lz4 = (flags & SURGE_INGEST_DEVICE_LZ4) != 0;
+  g->device_crc = (flags & SURGE_INGEST_DEVICE_CRC) != 0;
   *out = g;
   return OK;
 }
@@ -532,43 +715,6 @@ int32_t surge_ingest_destroy(surge_ingest* g) {
 
 const char* surge_ingest_last_error(const surge_ingest* g) { return g ? g->err.c_str() : g_err.c_str(); }
 
-namespace {
-
-// The whole batches at the front of data[0, len), found the way surge_ingest_feed's walk finds them (it stops where this
-// stops: a batchLength below the header size, a cut batch, a magic other than 2), and for each whether its CRC-32C holds.
-void verify_crcs_in_parallel(const uint8_t* data, int64_t len, int n_threads, std::vector<uint8_t>* ok) {
-  struct Span { const uint8_t* from; int64_t n; uint32_t crc; };
-  std::vector<Span> spans;
-  int64_t pos = 0;
-  while (len - pos >= 12) {
-    const uint8_t* h = data + pos;
-    const int32_t batch_len = (int32_t)(((uint32_t)h[8] << 24) | ((uint32_t)h[9] << 16) | ((uint32_t)h[10] << 8) | h[11]);
-    if (batch_len < 49 || len - pos - 12 < batch_len) break;
-    if (h[16] != 2) break;
-    const uint32_t crc = ((uint32_t)h[17] << 24) | ((uint32_t)h[18] << 16) | ((uint32_t)h[19] << 8) | h[20];
-    spans.push_back(Span{h + 21, (int64_t)batch_len - 9, crc});  // attributes .. end of the batch
-    pos += 12 + (int64_t)batch_len;
-  }
-  ok->assign(spans.size(), 0);
-  if (spans.empty()) return;
-  (void)surge_crc32c((const uint8_t*)"", 0);  // initialise the dispatch / tables before threads race for them
-  std::atomic<size_t> next{0};
-  auto work = [&]() {
-    constexpr size_t kGrab = 32;
-    for (size_t b = next.fetch_add(kGrab); b < spans.size(); b = next.fetch_add(kGrab))
-      for (size_t k = b; k < spans.size() && k < b + kGrab; ++k) (*ok)[k] = surge_crc32c(spans[k].from, spans[k].n) == spans[k].crc;
-  };
-  std::vector<std::thread> th;
-  try {
-    for (int t = 1; t < n_threads; ++t) th.emplace_back(work);
-  } catch (...) {  // the threads that did start, and this one, do the work
-  }
-  work();
-  for (std::thread& t : th) t.join();
-}
-
-}  // namespace
-
 int32_t surge_ingest_set_threads(surge_ingest* g, int32_t n_threads) {
   if (!g || n_threads < 1 || n_threads > 64) return fail(g, E_INVALID, "threads must be in 1 .. 64");
   g->crc_threads = n_threads;
@@ -578,227 +724,30 @@ int32_t surge_ingest_set_threads(surge_ingest* g, int32_t n_threads) {
 int32_t surge_ingest_feed(surge_ingest* g, const uint8_t* data, int64_t len, int64_t* consumed_out) {
   if (!g) return fail(nullptr, E_INVALID, "handle is NULL");
   if (len < 0 || (!data && len > 0)) return fail(g, E_INVALID, "bad buffer");
-  if (consumed_out) *consumed_out = 0;
-  if (g->frames && (g->handed_out || g->grouped)) {
-    // switch arenas: the sections still queued (open transactions, undrained batches) move along, the ones the last
-    // drain handed out stay untouched in the arena this feed leaves behind (valid through the five feeds after it).  A feed
-    // that follows no drain keeps appending where the last one stopped: nothing is copied.
-    try {
-      Arena& next = g->grouped ? g->ext[(g->cur + 1) % surge_ingest::kArenas] : g->arenas[(g->cur + 1) % surge_ingest::kArenas];
-      const Arena& prev = g->arena_now();
-      if (g->grouped) next.view(g->ext_next, g->ext_next_cap); else next.clear();
-      if (!g->grouped) {  // room for the whole feed at once: a page-locked arena that doubles its way up costs an allocation per step
-        size_t queued = 0;
-        for (const Batch& qb : g->queue) queued += qb.sect_off >= 0 ? (size_t)qb.sect_len : 0;
-        next.reserve(queued + (size_t)len);
-      }
-      for (Batch& qb : g->queue) {
-        if (qb.sect_off < 0) continue;
-        const int64_t at = (int64_t)next.size();
-        next.append(prev.data() + qb.sect_off, (size_t)qb.sect_len);
-        qb.sect_off = at;
-      }
-      g->cur = (g->cur + 1) % surge_ingest::kArenas;
-      g->handed_out = false;
-    } catch (const SliceOverflow&) {
-      g->slice_overflow = true;
-      return fail(g, E_NOMEM, "the group's slice for this partition is full");
-    } catch (const std::bad_alloc&) {
-      return fail(g, E_NOMEM, "out of host memory while decoding");
-    }
-  } else if (g->queue.empty()) {
-    // nothing queued and (FRAMES: no span of this arena handed out since the switch) nothing to keep: start over
-    g->arena_now().clear();
-  }
   int64_t pos = 0;
-  // With more than one CRC thread the batches' checksums are verified up front, in parallel (a batch's CRC depends on
-  // nothing but its own bytes; the walk below then looks the verdicts up in order, so what is reported, and when, is
-  // exactly what the one-thread walk reports).
-  std::vector<uint8_t> crc_ok;
-  if (g->crc_threads > 1 && len >= (1 << 20) && !g->device_crc) {
-    try {
-      verify_crcs_in_parallel(data, len, g->crc_threads, &crc_ok);
-    } catch (...) {  // no memory / no thread: the walk computes the CRCs itself
-      crc_ok.clear();
-    }
-  }
-  size_t batch_no = 0;
-  // open transactions' batches in the queue (few at a feed's start; a marker looks for its producer's among them from the
-  // back and stops at the oldest open one — the first version walked the whole queue per marker: every batch of the feed)
-  int64_t n_open = 0;
-  for (const Batch& qb : g->queue) n_open += qb.decided == 0;
-  // A failure in batch k leaves batches 0..k-1 of this buffer decoded and queued: report them as consumed so a
-  // caller that retries (or skips the bad batch) never feeds them twice.
-  auto bail = [&](int32_t code, const char* msg) {
-    if (consumed_out) *consumed_out = pos;
-    return fail(g, code, msg);
-  };
+  int32_t rc;
   try {
-    while (len - pos >= 12) {
-      Reader h{data + pos, data + len};
-      const int64_t base_offset = h.i64();
-      const int32_t batch_len = h.i32();
-      if (batch_len < 49) return bail(SURGE_E_CORRUPT, "batchLength below the v2 header size");
-      if (len - pos - 12 < batch_len) break;  // partial batch: wait for more bytes
-      const uint8_t* body = data + pos + 12;
-      __builtin_prefetch(body + batch_len);       // the next batch's header: a fresh cache line every few KB of a buffer that was just received
-      __builtin_prefetch(body + batch_len + 64);
-      Reader r{body, body + batch_len};
-      (void)r.i32();  // partitionLeaderEpoch
-      const uint8_t magic = r.u8();
-      if (magic != 2) return bail(E_UNSUPPORTED, "only message format v2 (magic 2) is supported");
-      const uint32_t crc = (uint32_t)r.i32();
-      // SURGE_INGEST_DEVICE_CRC: the CRC of a data batch (the control bit is the 0x20 of the attributes, the two bytes behind
-      // the CRC) is only STARTED here — over the 40 header bytes it covers in front of the records section — and finished
-      // where the section's bytes go anyway: on the device.  What this thread still touches of a batch is its header.
-      const bool defer_crc = g->device_crc && batch_len >= 49 && !(r.p[1] & 0x20);
-      uint32_t crc_state = 0;
-      if (defer_crc) {
-        if (!g->inplace) crc_state = ~surge_crc32c(r.p, 40);  // the register (not finalised) after attributes .. recordCount
-      } else {
-        const bool crc_good = batch_no < crc_ok.size() ? crc_ok[batch_no] != 0 : surge_crc32c(r.p, r.end - r.p) == crc;
-        if (!crc_good) return bail(SURGE_E_CORRUPT, "record batch CRC-32C mismatch");
-      }
-      ++batch_no;
-      const int16_t attrs = r.i16();
-      (void)r.i32();  // lastOffsetDelta
-      (void)r.i64();  // baseTimestamp
-      (void)r.i64();  // maxTimestamp
-      const int64_t producer_id = r.i64();
-      (void)r.i16();  // producerEpoch
-      (void)r.i32();  // baseSequence
-      const int32_t count = r.i32();
-      if (!r.ok || count < 0) return bail(SURGE_E_CORRUPT, "truncated batch header");
-      const int codec = attrs & 7;
-      const bool transactional = attrs & 0x10, control = attrs & 0x20;
-      // (a header that is only verified later, on the device, must not drive anything out of bounds before that: a record takes
-      // at least 7 bytes, and LZ4 expands at most 255 x)
-      if (defer_crc && (int64_t)count > ((r.end - r.p) / 7 + 1) * (codec ? 255 : 1))
-        return bail(SURGE_E_CORRUPT, "recordCount impossible for the batch's size (damaged header)");
-      const uint8_t* recs = r.p;
-      int64_t recs_len = r.end - r.p;
-      int sect_codec = 0;
-      if (codec == 3 && g->device_lz4 && !control) {
-        sect_codec = 3;  // the frame travels as it is: the device decoder walks its blocks and decodes them on the GPU
-      } else if (codec == 3 && g->inplace && !control) {
-        return bail(E_UNSUPPORTED, "an in-place feed leaves the sections where they were received: lz4 topics need SURGE_INGEST_DEVICE_LZ4");
-      } else if (codec == 3) {
-        // first guess: the frame's content-size field when the producer wrote one, else 8x (Kafka's LZ4 output
-        // stream omits it); a too-small guess comes back as -6 (out of space) and is grown, never as "corrupt"
-        int64_t cap = recs_len * 8 + 1024;
-        if (recs_len >= 15 && (recs[4] & 0x08)) {
-          uint64_t cs = 0;
-          for (int k = 7; k >= 0; --k) cs = (cs << 8) | recs[6 + k];
-          if (cs > 0 && cs <= (1ull << 31)) cap = (int64_t)cs;
-        }
-        int64_t got;
-        while (true) {
-          g->scratch.resize((size_t)cap);
-          got = surge_lz4_frame_decompress(recs, recs_len, g->scratch.data(), cap);
-          if (got != -6) break;
-          cap *= 4;
-          if (cap > (1ll << 31)) return bail(SURGE_E_CORRUPT, "LZ4 batch expands beyond 2 GiB");
-        }
-        if (got < 0) return bail(SURGE_E_CORRUPT, "bad LZ4 frame in record batch");
-        g->counters[6] += got;
-        recs = g->scratch.data();
-        recs_len = got;
-      } else if (codec != 0) {
-        return bail(E_UNSUPPORTED, "compression codec not supported (only none and lz4; the reference publishes lz4)");
-      }
-      Batch b;
-      b.producer_id = producer_id;
-      b.transactional = transactional;
-      int control_type = -1;
-      if (g->frames && !control) {
-        // device decode: the records section travels as it is (the device chains and parses the records)
-        b.sect_off = (int64_t)g->arena_now().size();
-        b.sect_len = recs_len;
-        b.base_offset = base_offset;
-        b.count = count;
-        b.sect_codec = sect_codec;
-        if (defer_crc && recs != r.p) return bail(E_UNSUPPORTED, "SURGE_INGEST_DEVICE_CRC needs the sections to travel as they are on the wire (SURGE_INGEST_DEVICE_LZ4 for lz4 topics)");
-        if (g->inplace) {
-          // nothing is copied: the section is where the fetch response was received (inside the slab this slice is a view of);
-          // with the device CRC the 44 bytes in front of it — the crc field and the header bytes it covers — go along as they are
-          b.crc_prefix = defer_crc ? 44 : 0;
-          b.sect_off = (int64_t)(recs - g->arena_now().data()) - b.crc_prefix;
-          b.sect_len = recs_len + b.crc_prefix;
-        } else {
-          if (defer_crc) {
-            const uint32_t pre[2] = {crc, crc_state};
-            g->arena_now().append((const uint8_t*)pre, 8);
-            b.sect_len += 8;
-            b.crc_prefix = 8;
-          }
-          g->arena_now().append(recs, (size_t)recs_len);
-        }
-        g->counters[1] += count;
-      } else {
-        const int32_t rc = parse_records(g, b, recs, recs_len, count, base_offset, control, &control_type);
-        if (rc != OK) {
-          if (consumed_out) *consumed_out = pos;
-          return rc;
-        }
-      }
-      g->counters[0] += 1;
-      if (control) {
-        g->counters[4] += 1;
-        if (control_type == 0 || control_type == 1) {  // ABORT / COMMIT ends this producer's open transaction
-          int64_t still_to_see = n_open;
-          for (auto qb = g->queue.rbegin(); qb != g->queue.rend() && still_to_see > 0; ++qb) {
-            if (qb->decided != 0) continue;
-            --still_to_see;
-            if (qb->producer_id == producer_id) {
-              qb->decided = control_type == 1 ? 1 : 2;
-              --n_open;
-              if (control_type == 0) g->counters[3] += qb->sect_off >= 0 ? (int64_t)qb->count : (int64_t)qb->recs.size();
-            }
-          }
-        }
-      } else {
-        b.decided = (transactional && g->isolation == SURGE_INGEST_READ_COMMITTED) ? 0 : 1;
-        if (!b.recs.empty() || b.count > 0) {
-          n_open += b.decided == 0;
-          g->queue.push_back(std::move(b));
-        }
-      }
-      pos += 12 + batch_len;
-    }
+    rc = feed_batches(g, data, len, &pos);
   } catch (const SliceOverflow&) {
-    if (consumed_out) *consumed_out = pos;
     g->slice_overflow = true;
-    return fail(g, E_NOMEM, "the group's slice for this partition is full");
+    rc = fail(g, E_NOMEM, "the group's slice for this partition is full");
   } catch (const std::bad_alloc&) {
-    if (consumed_out) *consumed_out = pos;
-    return fail(g, E_NOMEM, "out of host memory while decoding");
+    rc = fail(g, E_NOMEM, "out of host memory while decoding");
   }
   if (consumed_out) *consumed_out = pos;
-  g->counters[7] = n_open;
-  return OK;
+  return rc;
 }
 
 int64_t surge_ingest_ready(const surge_ingest* g) { return g ? ready_count(g) : 0; }
 
 int32_t surge_ingest_drain(surge_ingest* g, int64_t max, surge_ingest_record* out, int64_t* n_out) {
   if (!g || !n_out || max < 0 || (!out && max > 0)) return fail(g, E_INVALID, "bad argument");
-  if (g->frames) return fail(g, -2, "this decoder frames batches for a surge_device_decoder (SURGE_INGEST_FRAMES): use surge_ingest_drain_sections");
-  int64_t n = 0;
-  while (n < max && !g->queue.empty()) {
-    Batch& b = g->queue.front();
-    if (b.decided == 0) break;
-    if (b.decided == 2) { g->queue.pop_front(); continue; }
-    while (n < max && b.next < b.recs.size()) {
-      Rec& r = b.recs[b.next++];
-      out[n].offset = r.offset; out[n].agg_idx = deliver_idx(g, r); out[n].key_off = r.key_off; out[n].key_len = r.key_len;
-      out[n].value_len = r.value_len; out[n].value_off = r.value_off;
-      ++n;
-    }
-    if (b.next == b.recs.size()) g->queue.pop_front();
-  }
-  g->counters[2] += n;
-  *n_out = n;
-  return OK;
+  if (g->frames) return fail(g, -2, kFramesOnly);
+  return delivered(g, visit_ready<true>(g, max, [&](Rec& r, int64_t k) {
+    out[k].offset = r.offset; out[k].agg_idx = deliver_idx(g, r); out[k].key_off = r.key_off; out[k].key_len = r.key_len;
+    out[k].value_len = r.value_len; out[k].value_off = r.value_off;
+    return true;
+  }), n_out);
 }
 
 const uint8_t* surge_ingest_arena(const surge_ingest* g) { return g ? g->arena_now().data() : nullptr; }
@@ -814,77 +763,49 @@ int32_t surge_ingest_set_allocator(surge_ingest* g, void* (*alloc)(size_t), void
   return OK;
 }
 
+// The two drains below are all or nothing: a first walk looks at (decodes) what the call would deliver and pops nothing, so a
+// value that is refused leaves the queue as it was; the second walk delivers.
 int32_t surge_ingest_drain_fixed16(surge_ingest* g, int64_t max, int64_t* agg_idx_out, void* events16_out,
                                    int64_t* offsets_out, int64_t* n_out) {
   if (!g || !n_out || max < 0 || ((!agg_idx_out || !events16_out) && max > 0)) return fail(g, E_INVALID, "bad argument");
-  // validate before popping anything
-  if (g->frames) return fail(g, -2, "this decoder frames batches for a surge_device_decoder (SURGE_INGEST_FRAMES): use surge_ingest_drain_sections");
-  int64_t avail = 0;
-  for (const Batch& b : g->queue) {
-    if (b.decided == 0) break;
-    if (b.decided == 2) continue;
-    for (size_t i = b.next; i < b.recs.size() && avail < max; ++i, ++avail)
-      if (b.recs[i].value_len != 16 || b.recs[i].agg_idx == -1)
-        return fail(g, E_INVALID, "record value is not a 16-byte fixed event (or the key is null)");
-    if (avail >= max) break;
-  }
-  int64_t n = 0;
+  if (g->frames) return fail(g, -2, kFramesOnly);
+  int32_t refused = OK;
+  visit_ready<false>(g, max, [&](Rec& r, int64_t) {
+    if (r.value_len == 16 && r.agg_idx != -1) return true;
+    refused = fail(g, E_INVALID, "record value is not a 16-byte fixed event (or the key is null)");
+    return false;
+  });
+  if (refused != OK) return refused;
   uint8_t* ev = (uint8_t*)events16_out;
-  while (n < max && !g->queue.empty()) {
-    Batch& b = g->queue.front();
-    if (b.decided == 0) break;
-    if (b.decided == 2) { g->queue.pop_front(); continue; }
-    while (n < max && b.next < b.recs.size()) {
-      Rec& r = b.recs[b.next++];
-      agg_idx_out[n] = deliver_idx(g, r);
-      std::memcpy(ev + n * 16, g->arena_now().data() + r.value_off, 16);
-      if (offsets_out) offsets_out[n] = r.offset;
-      ++n;
-    }
-    if (b.next == b.recs.size()) g->queue.pop_front();
-  }
-  g->counters[2] += n;
-  *n_out = n;
-  return OK;
+  return delivered(g, visit_ready<true>(g, max, [&](Rec& r, int64_t k) {
+    agg_idx_out[k] = deliver_idx(g, r);
+    std::memcpy(ev + k * 16, g->arena_now().data() + r.value_off, 16);
+    if (offsets_out) offsets_out[k] = r.offset;
+    return true;
+  }), n_out);
 }
 
 int32_t surge_ingest_drain_json(surge_ingest* g, int64_t max, const surge_event_json_template* tmpl, int64_t* agg_idx_out,
                                 void* events16_out, int64_t* offsets_out, int64_t* n_out) {
   if (!g || !n_out || !tmpl || max < 0 || ((!agg_idx_out || !events16_out) && max > 0)) return fail(g, E_INVALID, "bad argument");
-  if (g->frames) return fail(g, -2, "this decoder frames batches for a surge_device_decoder (SURGE_INGEST_FRAMES): use surge_ingest_drain_sections");
+  if (g->frames) return fail(g, -2, kFramesOnly);
   if (surge_event_json_validate(tmpl) != 0) return fail(g, E_INVALID, std::string("event template: ") + surge_event_json_last_error());
-  // decode before popping anything: a value that does not decode leaves the queue as it was
   uint8_t* ev = (uint8_t*)events16_out;
-  int64_t avail = 0;
-  for (const Batch& b : g->queue) {
-    if (b.decided == 0) break;
-    if (b.decided == 2) continue;
-    for (size_t i = b.next; i < b.recs.size() && avail < max; ++i, ++avail) {
-      const Rec& r = b.recs[i];
-      if (r.agg_idx == -1 || r.value_len < 0)
-        return fail(g, SURGE_E_CORRUPT, "record at offset " + std::to_string(r.offset) + " has a null key or value (not an event)");
-      const int32_t rc = surge_event_json_decode(tmpl, g->arena_now().data() + r.value_off, r.value_len, ev + avail * 16);
-      if (rc != OK)
-        return fail(g, SURGE_E_CORRUPT, "record at offset " + std::to_string(r.offset) + ": " + surge_event_json_last_error());
+  int32_t refused = OK;
+  visit_ready<false>(g, max, [&](Rec& r, int64_t k) {
+    if (r.agg_idx == -1 || r.value_len < 0) {
+      refused = fail(g, SURGE_E_CORRUPT, "record at offset " + std::to_string(r.offset) + " has a null key or value (not an event)");
+    } else if (surge_event_json_decode(tmpl, g->arena_now().data() + r.value_off, r.value_len, ev + k * 16) != OK) {
+      refused = fail(g, SURGE_E_CORRUPT, "record at offset " + std::to_string(r.offset) + ": " + surge_event_json_last_error());
     }
-    if (avail >= max) break;
-  }
-  int64_t n = 0;
-  while (n < max && !g->queue.empty()) {
-    Batch& b = g->queue.front();
-    if (b.decided == 0) break;
-    if (b.decided == 2) { g->queue.pop_front(); continue; }
-    while (n < max && b.next < b.recs.size()) {
-      Rec& r = b.recs[b.next++];
-      agg_idx_out[n] = deliver_idx(g, r);
-      if (offsets_out) offsets_out[n] = r.offset;
-      ++n;
-    }
-    if (b.next == b.recs.size()) g->queue.pop_front();
-  }
-  g->counters[2] += n;
-  *n_out = n;
-  return OK;
+    return refused == OK;
+  });
+  if (refused != OK) return refused;
+  return delivered(g, visit_ready<true>(g, max, [&](Rec& r, int64_t k) {
+    agg_idx_out[k] = deliver_idx(g, r);
+    if (offsets_out) offsets_out[k] = r.offset;
+    return true;
+  }), n_out);
 }
 
 int32_t surge_ingest_drain_sections(surge_ingest* g, int64_t max_sections, surge_batch_section* out, int64_t* n_out) {
@@ -905,7 +826,7 @@ int32_t surge_ingest_drain_sections(surge_ingest* g, int64_t max_sections, surge
     }
     g->queue.pop_front();
   }
-  g->counters[2] += recs;  // handed to the device decoder (its own counters tell flush records from events)
+  g->counters[C_RECORDS_DELIVERED] += recs;  // handed to the device decoder (its own counters tell flush records from events)
   if (n > 0) g->handed_out = true;
   *n_out = n;
   return OK;
@@ -987,11 +908,15 @@ struct FramingPool {
   }
 };
 
+
+// what a group feed changes in a member, and is undone from (once per save: restore trades the queues)
 struct MemberSave {
   std::deque<Batch> queue;
-  int64_t counters[8];
+  int64_t counters[C_COUNT];
   int cur;
   bool handed_out;
+  void save(const surge_ingest& x) { queue = x.queue; std::memcpy(counters, x.counters, sizeof counters); cur = x.cur; handed_out = x.handed_out; }
+  void restore(surge_ingest& x) { x.queue.swap(queue); std::memcpy(x.counters, counters, sizeof counters); x.cur = cur; x.handed_out = handed_out; }
 };
 
 }  // namespace
@@ -1017,6 +942,178 @@ struct surge_ingest_group {
     for (surge_ingest* x : g) delete x;
   }
 };
+
+namespace {
+
+int64_t thread_cpu_ns() {
+  struct timespec ts;
+  if (clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts) != 0) return 0;
+  return (int64_t)ts.tv_sec * 1000000000ll + ts.tv_nsec;
+}
+
+// Every partition's slice of the next slab, 16-byte aligned: what the partition still holds (open transactions, batches not
+// drained yet) + bytes[p] (nullptr: nothing).  off (nullable) gets the n + 1 slice bounds; the total comes back.
+int64_t lay_out_slices(const surge_ingest_group* grp, const int64_t* bytes, int64_t times, int64_t* off) {
+  int64_t total = 0;
+  for (size_t p = 0; p < grp->g.size(); ++p) {
+    if (off) off[p] = total;
+    total = (total + queued_section_bytes(*grp->g[p]) + (bytes ? bytes[p] * times : 0) + 15) & ~15ll;
+  }
+  if (off) off[grp->g.size()] = total;
+  return total;
+}
+
+// A slab with room for fewer than `want` bytes gets `roomy` — and so does every other slab when it is the group's FIRST.  OK or E_NOMEM.
+// Page-locking a 30 - 45 MB slab takes 1.5 ms on a good day and 20 ms on a bad one (bytes -> states on the small-flush topic:
+// two of a dozen runs lost a 24 ms fetch to it and with it two thirds of their rate).  Fetch responses of one consumer are
+// alike, so a recovery pays for page-locking once, before its pipeline fills, not once per slab over its first six fetches.
+int32_t size_slab(surge_ingest_group* grp, Arena& slab, size_t want, size_t roomy) try {
+  if (slab.cap >= want) return OK;
+  bool first = true;
+  for (const Arena& a : grp->slabs) first = first && a.cap == 0;
+  if (!first) slab.reserve_exact(roomy);
+  else for (Arena& a : grp->slabs) a.reserve_exact(roomy);
+  return OK;
+} catch (const std::bad_alloc&) {
+  grp->err = "out of host memory for the group's slab";
+  return E_NOMEM;
+}
+
+// A fetch response's bytes into the slab with non-temporal stores.  What is written is read again by the framer — one header line
+// per few KB, prefetched a batch ahead — and by the copy engine; a cached copy reads every destination line first (read for
+// ownership: a third more memory traffic) and evicts what the other threads work on.  memcpy without AVX2 / on other hosts.
+#if defined(__x86_64__) || defined(__i386__)
+__attribute__((target("avx2"))) void stream_copy_avx2(uint8_t* to, const uint8_t* from, size_t n) {
+  size_t head = (size_t)(-(intptr_t)to) & 31u;
+  if (head > n) head = n;
+  std::memcpy(to, from, head);
+  to += head; from += head; n -= head;
+  size_t i = 0;
+  for (; i + 128 <= n; i += 128) {
+    const __m256i a = _mm256_loadu_si256((const __m256i*)(from + i)), b = _mm256_loadu_si256((const __m256i*)(from + i + 32));
+    const __m256i c = _mm256_loadu_si256((const __m256i*)(from + i + 64)), d = _mm256_loadu_si256((const __m256i*)(from + i + 96));
+    _mm256_stream_si256((__m256i*)(to + i), a);
+    _mm256_stream_si256((__m256i*)(to + i + 32), b);
+    _mm256_stream_si256((__m256i*)(to + i + 64), c);
+    _mm256_stream_si256((__m256i*)(to + i + 96), d);
+  }
+  _mm_sfence();
+  std::memcpy(to + i, from + i, n - i);
+}
+#endif
+void stream_copy(uint8_t* to, const uint8_t* from, size_t n) {
+#if defined(__x86_64__) || defined(__i386__)
+  static const bool avx2 = __builtin_cpu_supports("avx2") && std::getenv("SURGE_INGEST_RECEIVE_COPY") == nullptr;  // (any value: plain memcpy, for A/B)
+  if (avx2 && n >= 4096) return stream_copy_avx2(to, from, n);
+#endif
+  std::memcpy(to, from, n);
+}
+
+// In place: every partition's bytes lie inside the region surge_ingest_group_receive_buffer handed out for this feed.  The
+// sections then stay where they were received — the slab is not written at all beyond the few carried sections in front.
+bool received_in_place(const surge_ingest_group* grp, const uint8_t* const* data, const int64_t* len) {
+  if (grp->recv_slab != (grp->cur + 1) % surge_ingest::kArenas) return false;
+  const uint8_t *lo = grp->slabs[grp->recv_slab].data() + grp->recv_carry, *hi = lo + grp->recv_bytes;
+  bool any = false;
+  for (size_t p = 0; p < grp->g.size(); ++p) {
+    if (len[p] == 0) continue;
+    any = true;
+    if (data[p] < lo || data[p] + len[p] > hi) return false;
+  }
+  return any;
+}
+
+// A framing thread takes the partitions eight at a time and first walks their batch LENGTHS side by side — one step per partition
+// in turn, the next header of each prefetched while the other seven take theirs: a batch header is a cache line nobody has
+// touched since the response was received (with non-temporal stores: not in any cache), and a framer that meets them one
+// after the other waits out a memory latency per batch — most of what a batch costs it.
+constexpr int32_t kTogether = 8;
+void touch_headers(const uint8_t* const* data, const int64_t* len, int32_t p0, int32_t p1) {
+  int64_t at[kTogether];
+  int32_t live = 0;
+  for (int32_t p = p0; p < p1; ++p) {
+    at[p - p0] = len[p] >= 12 ? 0 : -1;
+    if (len[p] >= 12) { __builtin_prefetch(data[p]); ++live; }
+  }
+  while (live > 0) {
+    for (int32_t p = p0; p < p1; ++p) {
+      int64_t& pos = at[p - p0];
+      if (pos < 0) continue;
+      int32_t batch_len;
+      if (read_batch_length(data[p], len[p], pos, &batch_len) != HeaderRead::WHOLE) { pos = -1; --live; continue; }  // (the real walk decides what a bad length means)
+      pos += 12 + (int64_t)batch_len;
+      __builtin_prefetch(data[p] + pos);
+      __builtin_prefetch(data[p] + pos + 60);
+    }
+  }
+}
+
+// One partition's share of a group feed: its bytes framed into its slice of the slab, what is deliverable drained, the
+// sections' offsets made the slab's.  The outcome goes into grp->status / consumed / drained (nothing may leave a thread).
+void frame_partition(surge_ingest_group* grp, int32_t p, uint8_t* slab, const uint8_t* data, int64_t len, bool inplace) {
+  surge_ingest* x = grp->g[(size_t)p];
+  const int64_t slice_at = grp->off[(size_t)p];
+  int32_t rc = OK;
+  int64_t consumed = 0;
+  try {
+    x->ext_next = slab + slice_at;
+    x->ext_next_cap = (size_t)(grp->off[(size_t)p + 1] - slice_at);
+    x->slice_overflow = false;
+    x->inplace = inplace;
+    rc = surge_ingest_feed(x, data, len, &consumed);
+    x->inplace = false;
+    std::vector<surge_batch_section>& out = grp->drained[(size_t)p];
+    out.clear();
+    if (rc == OK && !x->queue.empty()) {
+      out.resize(x->queue.size());
+      int64_t got = 0;
+      rc = surge_ingest_drain_sections(x, (int64_t)out.size(), out.data(), &got);
+      out.resize(rc == OK ? (size_t)got : 0);
+      for (surge_batch_section& sct : out) sct.byte_off += slice_at;
+    }
+  } catch (...) {
+    rc = E_NOMEM;
+  }
+  grp->status[(size_t)p] = rc;
+  grp->consumed[(size_t)p] = consumed;
+}
+
+// A group feed's set-up, with `expand` times the room for what is framed by copy: every member saved (what a failed feed is undone
+// from), the slices laid out, the slab sized for them.  OK, or the status with the group's message set.
+int32_t prepare_slab(surge_ingest_group* grp, Arena& slab, const int64_t* len, bool inplace, int64_t expand) {
+  try {
+    for (size_t p = 0; p < grp->g.size(); ++p) grp->saved[p].save(*grp->g[p]);
+  } catch (const std::bad_alloc&) {
+    grp->err = "out of host memory";
+    return E_NOMEM;
+  }
+  const int64_t total = lay_out_slices(grp, inplace ? nullptr : len, expand, grp->off.data());
+  if (inplace) {
+    if (total <= grp->recv_carry) return OK;  // (always: nothing was fed between receive_buffer and this call)
+    grp->err = "the partitions' carried sections outgrew the room surge_ingest_group_receive_buffer left for them";
+    return E_INVALID;
+  }
+  slab.clear();
+  return size_slab(grp, slab, (size_t)total + 16, (size_t)total + (size_t)total / 4 + 65536);
+}
+
+// ... and its framing: the partitions on `threads` threads, the calling one + the group's pool
+void frame_partitions(surge_ingest_group* grp, uint8_t* slab, const uint8_t* const* data, const int64_t* len, int32_t threads, bool inplace) {
+  const int32_t n = (int32_t)grp->g.size();
+  std::atomic<int32_t> next{0};
+  const std::function<void()> work = [&]() {
+    const int64_t t0 = thread_cpu_ns();
+    for (int32_t p0 = next.fetch_add(kTogether); p0 < n; p0 = next.fetch_add(kTogether)) {
+      const int32_t p1 = p0 + kTogether < n ? p0 + kTogether : n;
+      touch_headers(data, len, p0, p1);
+      for (int32_t p = p0; p < p1; ++p) frame_partition(grp, p, slab, data[p], len[p], inplace);
+    }
+    grp->cpu_ns[1] += thread_cpu_ns() - t0;
+  };
+  grp->pool.run(work, (threads < 1 ? 1 : threads > n ? n : threads) - 1);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1075,12 +1172,6 @@ int64_t surge_ingest_group_queued_sections(const surge_ingest_group* grp) {
   return n;
 }
 
-static int64_t thread_cpu_ns() {
-  struct timespec ts;
-  if (clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts) != 0) return 0;
-  return (int64_t)ts.tv_sec * 1000000000ll + ts.tv_nsec;
-}
-
 int32_t surge_ingest_group_slab_bytes(const surge_ingest_group* grp, int64_t* bytes_out, int32_t* custom_allocator_out) {
   if (!grp || !bytes_out) return E_INVALID;
   int64_t total = 0;
@@ -1101,40 +1192,17 @@ int32_t surge_ingest_group_cpu_seconds(const surge_ingest_group* grp, double out
   return OK;
 }
 
-// what the partitions still hold (open transactions, batches not drained yet), 16-byte aligned per partition
-static int64_t group_carry_bytes(const surge_ingest_group* grp) {
-  int64_t total = 0;
-  for (const surge_ingest* x : grp->g) {
-    int64_t queued = 0;
-    for (const Batch& qb : x->queue) queued += qb.sect_off >= 0 ? qb.sect_len : 0;
-    total = (total + queued + 15) & ~15ll;
-  }
-  return total;
-}
-
 int32_t surge_ingest_group_receive_buffer(surge_ingest_group* grp, int64_t bytes, uint8_t** buf_out) {
   if (!grp || !buf_out || bytes < 0) return fail(nullptr, E_INVALID, "bad argument");
   *buf_out = nullptr;
   const int next = (grp->cur + 1) % surge_ingest::kArenas;
   Arena& slab = grp->slabs[next];
-  const int64_t carry = (group_carry_bytes(grp) + 63) & ~63ll;
-  try {
-    slab.clear();
-    const size_t want = (size_t)(carry + bytes) + 64;
-    if (slab.cap < want) {
-      const size_t roomy = want + want / 4 + 65536;  // (as surge_ingest_group_feed sizes them: every slab by the first response)
-      bool first = true;
-      for (const Arena& a : grp->slabs) first = first && a.cap == 0;
-      if (first) {
-        for (Arena& a : grp->slabs) a.reserve_exact(roomy);
-      } else {
-        slab.reserve_exact(roomy);
-      }
-    }
-  } catch (const std::bad_alloc&) {
-    grp->err = "out of host memory for the group's slab";
-    return E_NOMEM;
-  }
+  // room in front for what the partitions still hold (their carried sections move there), 16-byte aligned per partition
+  const int64_t carry = (lay_out_slices(grp, nullptr, 0, nullptr) + 63) & ~63ll;
+  slab.clear();
+  const size_t want = (size_t)(carry + bytes) + 64;
+  const int32_t rc = size_slab(grp, slab, want, want + want / 4 + 65536);
+  if (rc != OK) return rc;
   grp->recv_slab = next;
   grp->recv_carry = carry;
   grp->recv_bytes = bytes;
@@ -1145,34 +1213,6 @@ int32_t surge_ingest_group_receive_buffer(surge_ingest_group* grp, int64_t bytes
 // For a host whose fetch responses lie elsewhere (a test harness, a consumer library that owns its buffers): the one copy a
 // socket read would have made — every partition's bytes into the group's receive buffer, on `threads` threads (the calling
 // thread + the group's pool), cut into pieces of 1 MiB — and where each partition's bytes now are.
-namespace {
-// A fetch response's bytes into the slab with non-temporal stores.  What is written is read again by the framer — one header line
-// per few KB, prefetched a batch ahead — and by the copy engine; a cached copy reads every destination line first (read for
-// ownership: a third more memory traffic) and evicts what the other threads work on.  Falls back to memcpy without AVX2.
-__attribute__((target("avx2"))) void stream_copy_avx2(uint8_t* to, const uint8_t* from, size_t n) {
-  size_t head = (size_t)(-(intptr_t)to) & 31u;
-  if (head > n) head = n;
-  std::memcpy(to, from, head);
-  to += head; from += head; n -= head;
-  size_t i = 0;
-  for (; i + 128 <= n; i += 128) {
-    const __m256i a = _mm256_loadu_si256((const __m256i*)(from + i)), b = _mm256_loadu_si256((const __m256i*)(from + i + 32));
-    const __m256i c = _mm256_loadu_si256((const __m256i*)(from + i + 64)), d = _mm256_loadu_si256((const __m256i*)(from + i + 96));
-    _mm256_stream_si256((__m256i*)(to + i), a);
-    _mm256_stream_si256((__m256i*)(to + i + 32), b);
-    _mm256_stream_si256((__m256i*)(to + i + 64), c);
-    _mm256_stream_si256((__m256i*)(to + i + 96), d);
-  }
-  _mm_sfence();
-  std::memcpy(to + i, from + i, n - i);
-}
-void stream_copy(uint8_t* to, const uint8_t* from, size_t n) {
-  static const bool avx2 = __builtin_cpu_supports("avx2") && std::getenv("SURGE_INGEST_RECEIVE_COPY") == nullptr;  // (any value: plain memcpy, for A/B)
-  if (avx2 && n >= 4096) stream_copy_avx2(to, from, n);
-  else std::memcpy(to, from, n);
-}
-}  // namespace
-
 int32_t surge_ingest_group_receive_copy(surge_ingest_group* grp, const uint8_t* const* data, const int64_t* len, int32_t threads, const uint8_t** placed_out) {
   if (!grp || !data || !len || !placed_out) return fail(nullptr, E_INVALID, "bad argument");
   const int32_t n = (int32_t)grp->g.size();
@@ -1219,40 +1259,21 @@ int32_t surge_ingest_group_feed(surge_ingest_group* grp, const uint8_t* const* d
   const int32_t n = (int32_t)grp->g.size();
   *n_sections_out = 0;
   *slab_out = nullptr;
-  if (consumed_out)
-    for (int32_t p = 0; p < n; ++p) consumed_out[p] = 0;
+  if (consumed_out) std::memset(consumed_out, 0, sizeof(int64_t) * (size_t)n);
   for (int32_t p = 0; p < n; ++p)
     if (len[p] < 0 || (!data[p] && len[p] > 0)) { grp->err = "bad buffer for partition " + std::to_string(p); return E_INVALID; }
-  const int group_cur = grp->cur;
-  // In place: every partition's bytes lie inside the region surge_ingest_group_receive_buffer handed out for this feed.  The
-  // sections then stay where they were received — the slab is not written at all beyond the few carried sections in front.
-  bool inplace = grp->recv_slab == (group_cur + 1) % surge_ingest::kArenas;
-  if (inplace) {
-    const uint8_t* lo = grp->slabs[grp->recv_slab].data() + grp->recv_carry;
-    const uint8_t* hi = lo + grp->recv_bytes;
-    bool any = false;
-    for (int32_t p = 0; p < n; ++p) {
-      if (len[p] == 0) continue;
-      any = true;
-      if (data[p] < lo || data[p] + len[p] > hi) inplace = false;
-    }
-    inplace = inplace && any;
-  }
+  const int group_cur = grp->cur, group_next = (group_cur + 1) % surge_ingest::kArenas;
+  const bool inplace = received_in_place(grp, data, len);
   grp->recv_slab = -1;
+  Arena& slab = grp->slabs[group_next];
   auto undo = [&]() {
     for (int32_t p = 0; p < n; ++p) {
-      surge_ingest* x = grp->g[(size_t)p];
-      MemberSave& sv = grp->saved[(size_t)p];
-      x->queue.swap(sv.queue);
-      std::memcpy(x->counters, sv.counters, sizeof sv.counters);
-      x->cur = sv.cur;
-      x->handed_out = sv.handed_out;
+      grp->saved[(size_t)p].restore(*grp->g[(size_t)p]);
       grp->drained[(size_t)p].clear();
     }
     grp->cur = group_cur;
-    if (inplace) grp->recv_slab = (group_cur + 1) % surge_ingest::kArenas;  // (the received bytes are still there: the caller may feed them again)
-    if (consumed_out)
-      for (int32_t p = 0; p < n; ++p) consumed_out[p] = 0;
+    if (inplace) grp->recv_slab = group_next;  // (the received bytes are still there: the caller may feed them again)
+    if (consumed_out) std::memset(consumed_out, 0, sizeof(int64_t) * (size_t)n);
   };
   // Every partition's slice: what it still holds (open transactions, batches not drained yet) + this feed.  With
   // SURGE_INGEST_DEVICE_LZ4 a section is never longer than its batch; without it the host decompresses lz4 batches INTO the
@@ -1261,129 +1282,16 @@ int32_t surge_ingest_group_feed(surge_ingest_group* grp, const uint8_t* const* d
   // topic otherwise framed — CRC, decompression and all — every fetch two or three times over, for ever; the factor is capped
   // at 256: an LZ4 block expands at most 255 x)
   for (int64_t expand = grp->expand_hint;; expand *= 4) {
-    // what a failed feed is undone from
-    try {
-      for (int32_t p = 0; p < n; ++p) {
-        const surge_ingest* x = grp->g[(size_t)p];
-        MemberSave& sv = grp->saved[(size_t)p];
-        sv.queue = x->queue;
-        std::memcpy(sv.counters, x->counters, sizeof sv.counters);
-        sv.cur = x->cur;
-        sv.handed_out = x->handed_out;
-      }
-    } catch (const std::bad_alloc&) {
-      grp->err = "out of host memory";
-      return E_NOMEM;
-    }
-    int64_t total = 0;
-    for (int32_t p = 0; p < n; ++p) {
-      int64_t queued = 0;
-      for (const Batch& qb : grp->g[(size_t)p]->queue) queued += qb.sect_off >= 0 ? qb.sect_len : 0;
-      grp->off[(size_t)p] = total;
-      total = (total + queued + (inplace ? 0 : len[p] * expand) + 15) & ~15ll;
-    }
-    grp->off[(size_t)n] = total;
-    Arena& slab = grp->slabs[(group_cur + 1) % surge_ingest::kArenas];
-    try {
-      if (inplace) {
-        if (total > grp->recv_carry) {  // (cannot happen: nothing was fed between receive_buffer and this call)
-          grp->err = "the partitions' carried sections outgrew the room surge_ingest_group_receive_buffer left for them";
-          return E_INVALID;
-        }
-      } else {
-        slab.clear();
-      }
-      if (!inplace && slab.cap < (size_t)total + 16) {
-        // Page-locking a 30 - 45 MB slab takes 1.5 ms on a good day and 20 ms on a bad one (bytes -> states on the small-flush
-        // topic: two of a dozen runs lost a 24 ms fetch to it and with it two thirds of their rate).  So the group's FIRST feed
-        // sizes ALL its slabs, with a quarter to spare — fetch responses of one consumer are alike — and a recovery pays for
-        // page-locking once, before its pipeline fills, not once per slab over its first six fetches.
-        const size_t roomy = (size_t)total + (size_t)total / 4 + 65536;
-        bool first = true;
-        for (const Arena& a : grp->slabs) first = first && a.cap == 0;
-        if (first) {
-          for (Arena& a : grp->slabs) a.reserve_exact(roomy);
-        } else {
-          slab.reserve_exact(roomy);
-        }
-      }
-    } catch (const std::bad_alloc&) {
-      grp->err = "out of host memory for the group's slab";
-      return E_NOMEM;
-    }
-    grp->cur = (group_cur + 1) % surge_ingest::kArenas;
-    std::atomic<int32_t> next{0};
-    // A thread takes the partitions eight at a time and first walks their batch LENGTHS side by side — one step per partition
-    // in turn, the next header of each prefetched while the other seven take theirs: a batch header is a cache line nobody has
-    // touched since the response was received (with non-temporal stores: not in any cache), and a framer that meets them one
-    // after the other waits out a memory latency per batch — most of what a batch costs it.
-    constexpr int32_t kTogether = 8;
-    auto touch_headers = [&](int32_t p0, int32_t p1) {
-      const uint8_t* d[kTogether];
-      int64_t ln[kTogether], at[kTogether];
-      int32_t live = 0;
-      for (int32_t p = p0; p < p1; ++p) {
-        d[p - p0] = data[p];
-        ln[p - p0] = len[p];
-        at[p - p0] = 0;
-        if (len[p] >= 12) { __builtin_prefetch(data[p]); ++live; } else at[p - p0] = -1;
-      }
-      while (live > 0) {
-        for (int32_t i = 0; i < p1 - p0; ++i) {
-          if (at[i] < 0) continue;
-          const uint8_t* q = d[i] + at[i];
-          const int64_t bl = ((int64_t)q[8] << 24) | ((int64_t)q[9] << 16) | ((int64_t)q[10] << 8) | (int64_t)q[11];
-          const int64_t nxt = at[i] + 12 + bl;
-          if (bl < 49 || nxt + 12 > ln[i]) { at[i] = -1; --live; continue; }  // (the real walk decides what a bad length means)
-          __builtin_prefetch(d[i] + nxt);
-          __builtin_prefetch(d[i] + nxt + 60);
-          at[i] = nxt;
-        }
-      }
-    };
-    const std::function<void()> work = [&]() {
-      const int64_t t0 = thread_cpu_ns();
-      for (;;) {
-        const int32_t p0 = next.fetch_add(kTogether);
-        if (p0 >= n) break;
-        const int32_t p1 = p0 + kTogether < n ? p0 + kTogether : n;
-        touch_headers(p0, p1);
-        for (int32_t p = p0; p < p1; ++p) {
-        surge_ingest* x = grp->g[(size_t)p];
-        int32_t rc = OK;
-        int64_t consumed = 0;
-        try {  // (nothing may leave a thread)
-          x->ext_next = slab.data() + grp->off[(size_t)p];
-          x->ext_next_cap = (size_t)(grp->off[(size_t)p + 1] - grp->off[(size_t)p]);
-          x->slice_overflow = false;
-          x->inplace = inplace;
-          rc = surge_ingest_feed(x, data[p], len[p], &consumed);
-          x->inplace = false;
-          std::vector<surge_batch_section>& out = grp->drained[(size_t)p];
-          out.clear();
-          if (rc == OK && !x->queue.empty()) {
-            out.resize(x->queue.size());
-            int64_t got = 0;
-            rc = surge_ingest_drain_sections(x, (int64_t)out.size(), out.data(), &got);
-            out.resize(rc == OK ? (size_t)got : 0);
-            for (surge_batch_section& sct : out) sct.byte_off += grp->off[(size_t)p];
-          }
-        } catch (...) {
-          rc = E_NOMEM;
-        }
-        grp->status[(size_t)p] = rc;
-        grp->consumed[(size_t)p] = consumed;
-        }
-      }
-      grp->cpu_ns[1] += thread_cpu_ns() - t0;
-    };
-    int32_t t = threads < 1 ? 1 : threads;
-    if (t > n) t = n;
-    grp->pool.run(work, t - 1);
+    const int32_t rc = prepare_slab(grp, slab, len, inplace, expand);
+    if (rc != OK) return rc;
+    grp->cur = group_next;
+    frame_partitions(grp, slab.data(), data, len, threads, inplace);
     int32_t first_bad = OK;
     bool overflow = false;
+    int64_t need = 0;
     for (int32_t p = 0; p < n; ++p) {
       overflow |= grp->g[(size_t)p]->slice_overflow;
+      need += (int64_t)grp->drained[(size_t)p].size();
       if (grp->status[(size_t)p] != OK && first_bad == OK) {
         first_bad = grp->status[(size_t)p];
         grp->err = "partition " + std::to_string(p) + ": " + grp->g[(size_t)p]->err;
@@ -1393,13 +1301,11 @@ int32_t surge_ingest_group_feed(surge_ingest_group* grp, const uint8_t* const* d
       undo();
       continue;
     }
-    if (first_bad == OK) grp->expand_hint = expand;
     if (first_bad != OK) {
       undo();
       return first_bad;
     }
-    int64_t need = 0;
-    for (int32_t p = 0; p < n; ++p) need += (int64_t)grp->drained[(size_t)p].size();
+    grp->expand_hint = expand;
     if (need > max_sections) {
       undo();
       *n_sections_out = need;

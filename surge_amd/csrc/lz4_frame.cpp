@@ -1,7 +1,7 @@
-// lz4_frame.cpp — the WRITING half of the LZ4 frame format (the reading half lives in ingest.cpp) and XXH32, restated
-// from the published specifications (lz4_Frame_format.md, lz4_Block_format.md, xxhash_spec.md).  Host side of
-// libsurge_replay.so: the state-topic snapshot writer compresses its record batches the way the reference's producer
-// does (compression.type = lz4, modules/common/src/main/resources/reference.conf:112; kafka-clients frames a
+// lz4_frame.cpp — both halves of the LZ4 frame format, writing and reading, and XXH32, restated from the published
+// specifications (lz4_Frame_format.md, lz4_Block_format.md, xxhash_spec.md).  Host side of libsurge_replay.so.  Reading: the
+// host framer (ingest.cpp) decompresses the lz4 batches that do not go to the device compressed.  Writing: the state-topic
+// snapshot writer compresses its record batches the way the reference's producer does (compression.type = lz4, modules/common/src/main/resources/reference.conf:112; kafka-clients frames a
 // compressed batch's records as ONE LZ4 frame: version 01, block independence, 64 KiB blocks, no block / content
 // checksum, header checksum = second byte of XXH32(descriptor) — KafkaLZ4BlockOutputStream).
 //
@@ -77,6 +77,52 @@ int64_t compress_block(const uint8_t* src, int64_t n, uint8_t* dst) {
   return op - dst;
 }
 
+inline bool get_len(const uint8_t*& ip, const uint8_t* iend, int64_t& n) {  // put_len's inverse; false: the input ends inside the length
+  for (uint8_t b = 255; b == 255; n += b) {
+    if (ip >= iend) return false;
+    b = *ip++;
+  }
+  return true;
+}
+
+// LZ4 block (sequence) decoder into dst[*op .. cap); matches may reach back into everything already written.
+// LZ4_OK, LZ4_CORRUPT (malformed input) or LZ4_NOSPACE (dst too small: the caller grows it and retries).
+enum { LZ4_OK = 0, LZ4_CORRUPT = 1, LZ4_NOSPACE = 2 };
+int lz4_block(const uint8_t* ip, const uint8_t* iend, uint8_t* dst, int64_t* op_io, int64_t cap) {
+  int64_t op = *op_io;
+  while (ip < iend) {
+    const uint8_t token = *ip++;
+    int64_t lit = token >> 4;
+    if (lit == 15 && !get_len(ip, iend, lit)) return LZ4_CORRUPT;
+    if (iend - ip < lit) return LZ4_CORRUPT;
+    if (cap - op < lit) return LZ4_NOSPACE;
+    std::memcpy(dst + op, ip, (size_t)lit);
+    ip += lit;
+    op += lit;
+    if (ip >= iend) break;  // the last sequence carries literals only
+    if (iend - ip < 2) return LZ4_CORRUPT;
+    const int64_t offset = ip[0] | (ip[1] << 8);
+    ip += 2;
+    if (offset == 0 || offset > op) return LZ4_CORRUPT;
+    int64_t ml = token & 15;
+    if (ml == 15 && !get_len(ip, iend, ml)) return LZ4_CORRUPT;
+    ml += 4;
+    if (cap - op < ml) return LZ4_NOSPACE;
+    if (offset >= ml) {
+      std::memcpy(dst + op, dst + op - offset, (size_t)ml);
+    } else if (offset >= 8) {  // overlapping, but every 8-byte step reads bytes already final
+      int64_t k = 0;
+      for (; k + 8 <= ml; k += 8) std::memcpy(dst + op + k, dst + op + k - offset, 8);
+      for (; k < ml; ++k) dst[op + k] = dst[op + k - offset];
+    } else {
+      for (int64_t k = 0; k < ml; ++k) dst[op + k] = dst[op + k - offset];  // short period: the overlap is the point
+    }
+    op += ml;
+  }
+  *op_io = op;
+  return LZ4_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -113,6 +159,47 @@ uint32_t surge_xxh32(const uint8_t* p, int64_t len, uint32_t seed) {
   h *= P3;
   h ^= h >> 16;
   return h;
+}
+
+int64_t surge_lz4_frame_decompress(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap) {
+  if (!src || n < 7 || (!dst && cap > 0)) return -1;
+  const uint8_t* p = src;
+  const uint8_t* end = src + n;
+  if (!(p[0] == 0x04 && p[1] == 0x22 && p[2] == 0x4D && p[3] == 0x18)) return SURGE_E_CORRUPT;  // 0x184D2204 LE
+  p += 4;
+  const uint8_t flg = *p++;
+  p++;  // BD: block maximum size, not needed to decode
+  if ((flg >> 6) != 1) return SURGE_E_CORRUPT;  // version 01
+  const bool block_checksum = flg & 0x10, content_size = flg & 0x08, content_checksum = flg & 0x04, dict_id = flg & 0x01;
+  const uint8_t* const descriptor = p - 2;
+  if (content_size) p += 8;
+  if (dict_id) p += 4;
+  if (p >= end) return SURGE_E_CORRUPT;
+  // header checksum: second byte of XXH32(descriptor); kafka-clients verifies it for message format v2
+  if (*p != (uint8_t)(surge_xxh32(descriptor, (int64_t)(p - descriptor), 0) >> 8)) return SURGE_E_CORRUPT;
+  p += 1;
+  int64_t op = 0;
+  while (true) {
+    if (end - p < 4) return SURGE_E_CORRUPT;
+    const uint32_t bs = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+    p += 4;
+    if (bs == 0) break;  // EndMark
+    const uint32_t size = bs & 0x7fffffffu;
+    if ((int64_t)size > end - p) return SURGE_E_CORRUPT;
+    if (bs & 0x80000000u) {  // stored uncompressed
+      if (cap - op < (int64_t)size) return -6;
+      std::memcpy(dst + op, p, size);
+      op += size;
+    } else {
+      const int rc = lz4_block(p, p + size, dst, &op, cap);
+      if (rc == LZ4_NOSPACE) return -6;
+      if (rc != LZ4_OK) return SURGE_E_CORRUPT;
+    }
+    p += size;
+    if (block_checksum) p += 4;
+  }
+  if (content_checksum) p += 4;
+  return op;
 }
 
 int64_t surge_lz4_frame_bound(int64_t n) {
