@@ -629,3 +629,78 @@ def sdk_sample_state_bytes(aggregate_id: str, state: SdkBankAccount) -> bytes:
     if key:
         out += b"\x0a" + protobuf_varint(len(key)) + key
     return out + b"\x12" + protobuf_varint(len(payload)) + payload
+
+
+def parse_state_envelope(data: bytes):
+    """``protobuf.State.parseFrom(body)`` (GenericSurgeCommandBusinessLogic.scala:25-27) for the one shape scalapb writes:
+    optionally field 1 (tag ``0x0A``, length varint, id bytes), then optionally field 2 (tag ``0x12``, length varint, payload
+    bytes), nothing else.  Returns ``(aggregate_id, payload)``; raises ``ValueError`` for anything else (an unknown or
+    repeated field, another order, a length beyond the end, stray bytes)."""
+    pos, fields = 0, {}
+    for tag in (0x0A, 0x12):
+        if pos < len(data) and data[pos] == tag:
+            pos += 1
+            n = shift = 0
+            while True:
+                if pos >= len(data) or shift > 28:
+                    raise ValueError("State: truncated or over-long length varint")
+                b = data[pos]
+                pos += 1
+                n |= (b & 0x7F) << shift
+                shift += 7
+                if not b & 0x80:
+                    break
+            if n > 2**31 - 1 or n > len(data) - pos:
+                raise ValueError("State: a field reaches beyond the value's end")
+            fields[tag] = data[pos:pos + n]
+            pos += n
+    if pos != len(data):
+        raise ValueError("State: not `[aggregateId] [payload]` and nothing else")
+    return fields.get(0x0A, b"").decode("utf-8"), fields.get(0x12, b"")
+
+
+class SdkSampleStateFormat(SurgeAggregateFormatting[SdkBankAccount]):
+    """What the multilanguage gateway stores for the sample: ``State(aggregateId, payload = write(state)).toByteArray``
+    (GenericSurgeCommandBusinessLogic.scala:36-39, the payload is the SDK's json4s text, Main.scala:41-60), read back with
+    ``State.parseFrom`` (:25-27).  The SDK's state has no id of its own — the gateway holds it beside the payload — so the
+    id comes with the call (``write_state_with_id``, ``surge_amd.core.write_state_of``); ``write_state`` alone writes the
+    empty id, which proto3 leaves out.  ``read_state`` gives the SDK's state, ``read_state_with_id`` the pair."""
+
+    def write_state_with_id(self, aggregate_id: str, agg: SdkBankAccount) -> SerializedAggregate:
+        return SerializedAggregate(sdk_sample_state_bytes(aggregate_id, agg))
+
+    def write_state(self, agg: SdkBankAccount) -> SerializedAggregate:
+        return self.write_state_with_id("", agg)
+
+    def read_state_with_id(self, data: bytes):
+        aggregate_id, payload = parse_state_envelope(bytes(data))
+        return aggregate_id, SdkBankAccount(int(json.loads(payload)["balance"]))
+
+    def read_state(self, data: bytes) -> Optional[SdkBankAccount]:
+        try:
+            return self.read_state_with_id(data)[1]
+        except Exception:
+            return None
+
+
+class SdkSampleBusinessLogic(SurgeCommandBusinessLogic[SdkBankAccount, DepositMoney, SdkEvent]):
+    """The sample behind ``GenericSurgeCommandBusinessLogic`` (GenericSurgeCommandBusinessLogic.scala:14-45): the sample's
+    model, states stored in the protobuf ``State`` envelope.  Names are the gateway's defaults
+    (modules/multilanguage/src/main/resources/application.conf:42-47)."""
+
+    aggregate_name = "aggregate"
+    state_topic = KafkaTopic("state")
+    events_topic = KafkaTopic("events")
+
+    def __init__(self):
+        self._model = SdkSampleCommandModel()
+        self._agg_format = SdkSampleStateFormat()
+
+    def command_model(self):
+        return self._model
+
+    def aggregate_read_formatting(self):
+        return self._agg_format
+
+    def aggregate_write_formatting(self):
+        return self._agg_format

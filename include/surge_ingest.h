@@ -331,6 +331,12 @@ int32_t surge_replay_stage_decoded(struct surge_replay_handle* h, surge_device_d
  * (surge_replay_set_decode_base).  ABI v2 handles: SURGE_E_UNSUPPORTED (the decode's; nothing is cleared). */
 struct surge_json_template;
 int32_t surge_device_decoder_load_states(surge_device_decoder* d, struct surge_replay_handle* h, const struct surge_json_template* tmpl, int64_t counts_out[4]);
+/* surge_device_decoder_load_states for a state topic a multilanguage (SDK) application wrote: every value is the protobuf
+ * State message around the text payload_tmpl describes (surge_replay_decode_protobuf_states in surge_replay.h; the reference
+ * reads them with protobuf.State.parseFrom, GenericSurgeCommandBusinessLogic.scala:25-27).  The same hand-over, the same
+ * naming of the first refused record by its topic offset, the same merge of kept strings. */
+int32_t surge_device_decoder_load_protobuf_states(surge_device_decoder* d, struct surge_replay_handle* h, const struct surge_json_template* payload_tmpl,
+                                                  int64_t counts_out[4]);
 /* The STR fields of the loaded states, kept on the device (off by default: load_states then behaves exactly as described
  * above).  surge_device_decoder_keep_strings(d, 1) — state decoders only (SURGE_E_STATE otherwise), before the first
  * load_states — makes every load_states also reserve a span buffer for the decode and, for every column a SURGE_JP_STR part

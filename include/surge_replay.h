@@ -516,6 +516,7 @@ int32_t surge_replay_encode_protobuf_state(surge_replay_handle* h, const surge_j
 #define SURGE_STATE_DECODE_TRAILING     8 /* bytes behind the last part                                               */
 #define SURGE_STATE_DECODE_AMBIGUOUS    9 /* device only, transient: a Double the fast algorithm cannot decide        */
 #define SURGE_STATE_DECODE_SURROGATE   10 /* a \uD800 .. \uDFFF escape                                                */
+#define SURGE_STATE_DECODE_ENVELOPE    11 /* protobuf State values only: not `[0x0A len id] [0x12 len payload]` and nothing else */
 #define SURGE_STATE_DECODE_SKIPPED    255 /* d_status_out only: a later record names the same aggregate; not parsed   */
 
 /* One value on the host (thread-safe; needs no device): 0 or a SURGE_STATE_DECODE_* status (> 0), SURGE_E_INVALID for a
@@ -525,6 +526,23 @@ int32_t surge_replay_encode_protobuf_state(surge_replay_handle* h, const surge_j
  * surge_parse_f64_json does. */
 int32_t surge_decode_json_state(const surge_json_template* tmpl, const uint8_t* value, int64_t len, const uint8_t* key,
                                 int64_t key_len, void* state64_out, int64_t* str_span_out);
+
+/* The same for a value the multilanguage module wrote: the text wrapped in its protobuf message
+ *   message State { string aggregateId = 1; bytes payload = 2; }   (multilanguage-protocol.proto:7-10)
+ * = what surge_replay_encode_protobuf_state writes and the reference reads with protobuf.State.parseFrom(body)
+ * (GenericSurgeCommandBusinessLogic.scala:25-27).  Accepted: optionally field 1 (tag 0x0A, a length varint, that many id
+ * bytes), then optionally field 2 (tag 0x12, a length varint, that many payload bytes), and nothing else — the value ends
+ * exactly behind the last accepted field (proto3 omits an empty field; only the order scalapb writes is read).  A length
+ * varint has 1 - 5 bytes and a value <= 2^31 - 1; over-long spellings are accepted as the protobuf runtime accepts them.
+ * SURGE_STATE_DECODE_ENVELOPE: any other tag, a repeated field, field 2 before field 1, a length beyond the value's end, bytes
+ * behind field 2, a value that ends inside a tag or a varint.  With a key, field 1's raw bytes must be the id byte for byte
+ * (no unescaping; an absent field 1 is the empty id), else KEY_MISMATCH.  The payload is then parsed through payload_tmpl
+ * exactly as surge_decode_json_state parses a bare value (a KEY part in it is compared too) and its statuses are reported as
+ * they are: an absent or empty payload is LITERAL through the template, text behind the template's last part inside the
+ * payload TRAILING.  str_span_out offsets are relative to `value`, not to the payload.  Unknown fields are refused, not
+ * skipped.  Never reads at or beyond value + len. */
+int32_t surge_decode_protobuf_state(const surge_json_template* payload_tmpl, const uint8_t* value, int64_t len, const uint8_t* key,
+                                    int64_t key_len, void* state64_out, int64_t* str_span_out);
 
 /* n_records values on the device, in offset order: record r's text is d_values[d_value_off[r] .. d_value_off[r+1]) and
  * names aggregate d_agg_idx[r] (d_agg_idx NULL: record r is aggregate r, n_records <= n_agg).  Per aggregate the LAST
@@ -545,6 +563,16 @@ int32_t surge_replay_decode_json_states(surge_replay_handle* h, const surge_json
                                         const int64_t* d_value_off, int64_t n_records, const uint8_t* d_keys_utf8,
                                         const int64_t* d_key_off, const int64_t* d_agg_idx, int64_t n_agg, void* d_states64,
                                         uint8_t* d_status_out, int64_t* d_str_span_out, int64_t counts_out[4]);
+
+/* The same call for values in the protobuf State envelope (surge_decode_protobuf_state's grammar; the envelope is the same
+ * for every record of a call): arguments, counts, statuses and return values as above.  An empty value is a tombstone,
+ * decided before the envelope is looked at.  d_str_span_out offsets are relative to the record's value, so
+ * surge_replay_merge_state_strings takes them as they are.  A Double the device cannot decide goes through
+ * surge_decode_protobuf_state. */
+int32_t surge_replay_decode_protobuf_states(surge_replay_handle* h, const surge_json_template* payload_tmpl, const uint8_t* d_values,
+                                            const int64_t* d_value_off, int64_t n_records, const uint8_t* d_keys_utf8,
+                                            const int64_t* d_key_off, const int64_t* d_agg_idx, int64_t n_agg, void* d_states64,
+                                            uint8_t* d_status_out, int64_t* d_str_span_out, int64_t counts_out[4]);
 
 /* A STR span (the bytes between the quotes, as reported above) -> the string, on the host, by the routine the device runs:
  * the escapes above, \uXXXX as 1 - 3 bytes of UTF-8, bytes from 0x80 on as they are.  Returns the unescaped length — the

@@ -213,6 +213,17 @@ class AggregateStateStore {
     return counts;
   }
 
+  // The same for values in the multilanguage module's protobuf State envelope (surge_replay_decode_protobuf_states: what
+  // GenericSurgeCommandBusinessLogic stores; payload_tmpl describes the payload's text).
+  std::array<int64_t, 4> decodeProtobufStates(const surge_json_template& payload_tmpl, const uint8_t* d_values, const int64_t* d_value_off,
+                                              int64_t n_records, const uint8_t* d_keys_utf8, const int64_t* d_key_off, const int64_t* d_agg_idx,
+                                              int64_t n_agg, void* d_states64, uint8_t* d_status_out = nullptr, int64_t* d_str_span_out = nullptr) {
+    std::array<int64_t, 4> counts{};
+    check(surge_replay_decode_protobuf_states(h_, &payload_tmpl, d_values, d_value_off, n_records, d_keys_utf8, d_key_off, d_agg_idx, n_agg,
+                                              d_states64, d_status_out, d_str_span_out, counts.data()));
+    return counts;
+  }
+
   // The STR spans that decode left -> string column `column` over n_agg aggregates (surge_replay_merge_state_strings; arguments
   // as in surge_replay.h).  Returns the column's bytes; a buffer that is too small is not an error here: the total is
   // returned (> out_capacity), nothing was written to d_out_utf8, call again with room.  Throws on any other failure.

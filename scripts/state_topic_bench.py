@@ -1,6 +1,7 @@
 """Restoring the aggregate store from the state topic's BYTES: the device route against the host route, in one process.
 
     python scripts/state_topic_bench.py [n_aggregates=2000000] [pairs=5] > profiles/state_topic_restore.json
+    python scripts/state_topic_bench.py --envelope protobuf_state [n_aggregates] [pairs] > profiles/state_topic_restore_protobuf.json
     rocprofv3 --kernel-trace --stats -d DIR -- python scripts/state_topic_bench.py --one-push [n_aggregates]
     python scripts/state_topic_bench.py --kernel-split DIR profiles/state_topic_restore.json   # folds the trace's stats into the JSON
 
@@ -17,7 +18,10 @@ Both end in the same 64-byte rows (checked).  ``device_core`` times the device r
 pushes, loads; no key table to the host).  One JSON line: the seconds of every repeat, medians, spreads, aggregates/s, and
 whether the device route wins every pair by more than both spreads.  ``--one-push`` runs one push + load of the whole topic
 (for a kernel trace); ``--kernel-split`` reads that trace's kernel stats: per kernel of the push its time, and for the value
-gather its time against the bytes it moves (read + written) as a fraction of 8 TB/s — recorded, not held to a bar."""
+gather its time against the bytes it moves (read + written) as a fraction of 8 TB/s — recorded, not held to a bar.
+``--envelope protobuf_state`` (in front of the other arguments) publishes the same aggregates as a multilanguage (SDK)
+application stores them — ``encode_states(envelope="protobuf_state")`` behind the same device framer — and restores them
+through the envelope route of every call above."""
 import csv
 import glob
 import json
@@ -33,6 +37,7 @@ sys.path.insert(0, os.path.join(ROOT, "examples"))
 
 N_PART = 4
 PEAK_BYTES_PER_S = 8e12
+ENVELOPE = "none"  # --envelope: how the topic's values are written and read
 
 
 def publish_topic(n):
@@ -48,7 +53,7 @@ def publish_topic(n):
     with ReplayEngine() as eng:
         eng.load_csr(so, ev)
         eng.fold()
-        pub = BulkSnapshotPublisher(eng, keys, N_PART, compression="lz4", device_compression=True)
+        pub = BulkSnapshotPublisher(eng, keys, N_PART, compression="lz4", device_compression=True, envelope=ENVELOPE)
         try:
             out = {p: bytes(b) for p, b in pub.publish().items()}
             text = int(pub.timings["text_bytes"])
@@ -62,7 +67,7 @@ def device_route(bl, topic):
 
     store = GpuReplayStateStore(bl)
     t0 = time.perf_counter()
-    counts = store.restore_from_state_topic([[topic.get(p) for p in range(N_PART)]], n_partitions=N_PART)
+    counts = store.restore_from_state_topic([[topic.get(p) for p in range(N_PART)]], n_partitions=N_PART, envelope=ENVELOPE)
     return time.perf_counter() - t0, store, counts
 
 
@@ -77,7 +82,7 @@ def host_route(bl, topic):
         with EventsTopicIngest() as g:
             g.feed(topic[p])
             records.extend((k.decode("utf-8"), v) for _, _, k, v in g.drain_records())
-    store.restore_from_state_records(records)
+    store.restore_from_state_records(records, envelope=ENVELOPE)
     return time.perf_counter() - t0, store, None
 
 
@@ -100,7 +105,7 @@ def device_core(topic, template):
             parts = [(sec, arena) for sec, arena in (item if isinstance(item, list) else [item]) if sec.shape[0]]
             d.push_async(parts)
             d.finish()
-            counts = d.load_states_into(eng, template)
+            counts = d.load_states_into(eng, template, envelope=ENVELOPE)
     dt = time.perf_counter() - t0
     d.close()
     eng.close()
@@ -119,7 +124,7 @@ def run(n, pairs):
 
     bl = CounterBusinessLogic()
     keys, topic, text_bytes = publish_topic(n)
-    out = {"aggregates": n, "partitions": N_PART, "topic_bytes": sum(len(b) for b in topic.values()), "value_bytes": text_bytes, "pairs": pairs}
+    out = {"aggregates": n, "envelope": ENVELOPE, "partitions": N_PART, "topic_bytes": sum(len(b) for b in topic.values()), "value_bytes": text_bytes, "pairs": pairs}
     small = {p: b for p, b in publish_topic(20000)[1].items()}
     for route in (device_route, host_route):  # warm-up of both (code objects, pinned slabs' first touch, Python imports)
         route(bl, small)[1].close()
@@ -171,6 +176,11 @@ def kernel_split(trace_dir, json_path):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
+    if args and args[0] == "--envelope":
+        ENVELOPE = args[1]
+        if ENVELOPE not in ("none", "protobuf_state"):
+            raise SystemExit(f"unknown envelope {ENVELOPE!r}")
+        args = args[2:]
     if args and args[0] == "--kernel-split":
         kernel_split(args[1], args[2])
     elif args and args[0] == "--one-push":

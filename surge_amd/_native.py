@@ -70,6 +70,7 @@ EXPORTS = (
     "surge_replay_encode_json",
     "surge_replay_encode_protobuf_state",
     "surge_replay_decode_json_states",
+    "surge_replay_decode_protobuf_states",
     "surge_replay_merge_state_strings",
     "surge_replay_set_decode_base",
     "surge_replay_pack_states",
@@ -139,6 +140,7 @@ INGEST_EXPORTS = (
     "surge_device_decoder_state_result",
     "surge_device_decoder_clear",
     "surge_device_decoder_load_states",
+    "surge_device_decoder_load_protobuf_states",
     "surge_device_decoder_keep_strings",
     "surge_device_decoder_state_strings",
     "surge_replay_append_decoded",
@@ -184,7 +186,7 @@ SNAPSHOT_EXPORTS = (
 )
 
 #: the host half of the state decoder (declared in ``include/surge_replay.h``; needs no handle and no device)
-STATE_EXPORTS = ("surge_decode_json_state", "surge_unescape_json_string")
+STATE_EXPORTS = ("surge_decode_json_state", "surge_decode_protobuf_state", "surge_unescape_json_string")
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -320,7 +322,9 @@ def load() -> ctypes.CDLL:
         "surge_replay_encode_protobuf_state": ([vp, vp, vp, vp, vp, i64, vp, ctypes.POINTER(i64)], i32),
         "surge_replay_decode_json_states": ([vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, ctypes.POINTER(i64 * 4)], i32),
         "surge_replay_set_decode_base": ([vp, vp], i32),
+        "surge_replay_decode_protobuf_states": ([vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, ctypes.POINTER(i64 * 4)], i32),
         "surge_decode_json_state": ([vp, vp, i64, vp, i64, vp, vp], i32),
+        "surge_decode_protobuf_state": ([vp, vp, i64, vp, i64, vp, vp], i32),
         "surge_unescape_json_string": ([vp, i64, vp, i64], i64),
         "surge_replay_merge_state_strings": ([vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, i64, vp, ctypes.POINTER(i64)], i32),
         "surge_replay_pack_states": ([vp, vp, i64, vp, vp], i32),
@@ -390,6 +394,7 @@ def load() -> ctypes.CDLL:
                                                ctypes.POINTER(i64)], i32),
         "surge_device_decoder_clear": ([vp], i32),
         "surge_device_decoder_load_states": ([vp, vp, vp, ctypes.POINTER(i64 * 4)], i32),
+        "surge_device_decoder_load_protobuf_states": ([vp, vp, vp, ctypes.POINTER(i64 * 4)], i32),
         "surge_device_decoder_keep_strings": ([vp, i32], i32),
         "surge_device_decoder_state_strings": ([vp, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64)], i32),
         "surge_replay_append_decoded": ([vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),

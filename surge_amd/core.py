@@ -49,6 +49,15 @@ class SurgeAggregateFormatting(SurgeAggregateReadFormatting[State], SurgeAggrega
     pass
 
 
+def write_state_of(formatting, aggregate_id: str, state) -> SerializedAggregate:
+    """``writeState`` where the caller knows the aggregate's id.  A format whose stored value carries the id beside the
+    state — the multilanguage module's ``State{aggregateId, payload}`` (``GenericSurgeCommandBusinessLogic.scala:36-39``),
+    whose SDK-side state has no id of its own — offers ``write_state_with_id(aggregate_id, state)`` and gets it; every other
+    format is asked ``write_state(state)`` as before."""
+    with_id = getattr(formatting, "write_state_with_id", None)
+    return with_id(aggregate_id, state) if with_id is not None else formatting.write_state(state)
+
+
 class SurgeEventWriteFormatting(Generic[Event]):
     def write_event(self, evt: Event) -> SerializedMessage:
         raise NotImplementedError

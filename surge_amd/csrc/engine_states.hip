@@ -175,12 +175,12 @@ int32_t surge_replay_set_decode_base(surge_replay_handle* h, const void* state64
   return SURGE_OK;
 }
 
-int32_t surge_replay_decode_json_states(surge_replay_handle* h, const surge_json_template* tmpl, const uint8_t* d_values,
-                                        const int64_t* d_value_off, int64_t n_records, const uint8_t* d_keys_utf8,
-                                        const int64_t* d_key_off, const int64_t* d_agg_idx, int64_t n_agg, void* d_states64,
-                                        uint8_t* d_status_out, int64_t* d_str_span_out, int64_t counts_out[4]) {
+// envelope: every value is a protobuf State message around the template's text (surge_replay_decode_protobuf_states)
+static int32_t decode_states(surge_replay_handle* h, const surge_json_template* tmpl, const uint8_t* d_values, const int64_t* d_value_off,
+                             int64_t n_records, const uint8_t* d_keys_utf8, const int64_t* d_key_off, const int64_t* d_agg_idx, int64_t n_agg,
+                             void* d_states64, uint8_t* d_status_out, int64_t* d_str_span_out, int64_t counts_out[4], bool envelope) {
   if (!h) return fail(nullptr, SURGE_E_INVALID, "handle is NULL");
-  if (h->v2) return fail(h, SURGE_E_UNSUPPORTED, "decode_json_states serves ABI v1 handles (a slot schema keeps its presence word elsewhere)");
+  if (h->v2) return fail(h, SURGE_E_UNSUPPORTED, envelope ? "decode_protobuf_states serves ABI v1 handles (a slot schema keeps its presence word elsewhere)" : "decode_json_states serves ABI v1 handles (a slot schema keeps its presence word elsewhere)");
   if (const char* why = state_template_problem(tmpl)) return fail(h, SURGE_E_INVALID, why);
   if (!counts_out) return fail(h, SURGE_E_INVALID, "counts_out is NULL");
   counts_out[0] = counts_out[1] = counts_out[2] = counts_out[3] = 0;
@@ -207,6 +207,7 @@ int32_t surge_replay_decode_json_states(surge_replay_handle* h, const surge_json
   p.spans = d_str_span_out;
   p.ptab = (const F64ParseTable*)h->sd_ptab.ptr;
   p.counts = (unsigned long long*)h->sd_counts.ptr;
+  p.envelope = envelope;
   // the base row, without the bytes the template names and the flags word: the kernel ORs it into the parsed row
   alignas(16) uint8_t base[64];
   std::memcpy(base, h->decode_base, 64);
@@ -260,7 +261,8 @@ int32_t surge_replay_decode_json_states(surge_replay_handle* h, const surge_json
       HIPCHK(h, hipStreamSynchronize(h->stream));
       alignas(16) uint8_t row[64];
       int64_t span[2 * SURGE_JSON_STRING_COLUMNS];
-      const int32_t rc = surge_decode_json_state(tmpl, text.data(), (int64_t)text.size(), key.data(), key_len, row, span);
+      // (in envelope mode the span comes back relative to the value, as the kernel reports it)
+      const int32_t rc = (envelope ? surge_decode_protobuf_state : surge_decode_json_state)(tmpl, text.data(), (int64_t)text.size(), key.data(), key_len, row, span);
       const uint8_t st = (uint8_t)(rc < 0 ? SURGE_STATE_DECODE_NUMBER : rc);
       if (rc == SURGE_STATE_DECODE_OK) {
         for (int b = 0; b < 64; ++b) row[b] |= base[b];
@@ -289,6 +291,22 @@ int32_t surge_replay_decode_json_states(surge_replay_handle* h, const surge_json
                                     " (SURGE_STATE_DECODE_*); everything else was decoded");
   }
   return SURGE_OK;
+}
+
+int32_t surge_replay_decode_json_states(surge_replay_handle* h, const surge_json_template* tmpl, const uint8_t* d_values,
+                                        const int64_t* d_value_off, int64_t n_records, const uint8_t* d_keys_utf8,
+                                        const int64_t* d_key_off, const int64_t* d_agg_idx, int64_t n_agg, void* d_states64,
+                                        uint8_t* d_status_out, int64_t* d_str_span_out, int64_t counts_out[4]) {
+  return decode_states(h, tmpl, d_values, d_value_off, n_records, d_keys_utf8, d_key_off, d_agg_idx, n_agg, d_states64, d_status_out, d_str_span_out,
+                       counts_out, false);
+}
+
+int32_t surge_replay_decode_protobuf_states(surge_replay_handle* h, const surge_json_template* payload_tmpl, const uint8_t* d_values,
+                                            const int64_t* d_value_off, int64_t n_records, const uint8_t* d_keys_utf8,
+                                            const int64_t* d_key_off, const int64_t* d_agg_idx, int64_t n_agg, void* d_states64,
+                                            uint8_t* d_status_out, int64_t* d_str_span_out, int64_t counts_out[4]) {
+  return decode_states(h, payload_tmpl, d_values, d_value_off, n_records, d_keys_utf8, d_key_off, d_agg_idx, n_agg, d_states64, d_status_out,
+                       d_str_span_out, counts_out, true);
 }
 
 int32_t surge_replay_merge_state_strings(surge_replay_handle* h, int32_t column, const uint8_t* d_values, const int64_t* d_value_off, int64_t n_records,

@@ -1158,9 +1158,12 @@ int32_t surge_device_decoder_state_result(surge_device_decoder* d, int64_t* n_re
   return OK;
 }
 
+}  // extern "C"
+
 // state values -> resident state: what a KTable restore of the state topic does with the records it is handed
-// (SurgeStateStoreConsumer.scala:69), behind one call
-int32_t surge_device_decoder_load_states(surge_device_decoder* d, surge_replay_handle* h, const surge_json_template* tmpl, int64_t counts_out[4]) {
+// (SurgeStateStoreConsumer.scala:69), behind one call.  envelope: the values are protobuf State messages around the
+// template's text (surge_device_decoder_load_protobuf_states)
+static int32_t load_states(surge_device_decoder* d, surge_replay_handle* h, const surge_json_template* tmpl, int64_t counts_out[4], bool envelope) {
   if (!h || !d || !counts_out) return dfail(d, E_INVALID, "NULL argument");
   counts_out[0] = counts_out[1] = counts_out[2] = counts_out[3] = 0;
   if (!d->states) return dfail(d, SURGE_E_STATE, "not a state decoder (surge_device_decoder_create_states): an events decoder hands over with surge_replay_append_decoded");
@@ -1181,7 +1184,7 @@ int32_t surge_device_decoder_load_states(surge_device_decoder* d, surge_replay_h
   DCHK(d, hipEventRecord(d->ready, d->stream));
   DCHK(d, hipStreamWaitEvent((hipStream_t)hs, d->ready, 0));
   // (rows [0, n_keys): every aggregate index of the result is below the decoder's key count, and its key table has that many ids)
-  rc = surge_replay_decode_json_states(h, tmpl, (const uint8_t*)d->r_val.p, (const int64_t*)d->r_val_off.p, d->n_records, (const uint8_t*)d->arena.p,
+  rc = (envelope ? surge_replay_decode_protobuf_states : surge_replay_decode_json_states)(h, tmpl, (const uint8_t*)d->r_val.p, (const int64_t*)d->r_val_off.p, d->n_records, (const uint8_t*)d->arena.p,
                                        (const int64_t*)d->key_off.p, (const int64_t*)d->r_agg.p, d->n_keys, d_states, (uint8_t*)d->st_status.p,
                                        d->keep_strings ? (int64_t*)d->st_spans.p : nullptr, counts_out);
   if (rc != OK && rc != SURGE_E_CORRUPT) return dfail(d, rc, surge_replay_last_error(h));  // nothing was loaded: the records stay
@@ -1228,6 +1231,17 @@ int32_t surge_device_decoder_load_states(surge_device_decoder* d, surge_replay_h
   d->n_records = 0;  // (cleared whether or not a winner was refused: the call returns when the rows are written)
   d->val_bytes = 0;
   return rc == OK ? OK : dfail(d, rc, refused);
+}
+
+extern "C" {
+
+int32_t surge_device_decoder_load_states(surge_device_decoder* d, surge_replay_handle* h, const surge_json_template* tmpl, int64_t counts_out[4]) {
+  return load_states(d, h, tmpl, counts_out, false);
+}
+
+int32_t surge_device_decoder_load_protobuf_states(surge_device_decoder* d, surge_replay_handle* h, const surge_json_template* payload_tmpl,
+                                                  int64_t counts_out[4]) {
+  return load_states(d, h, payload_tmpl, counts_out, true);
 }
 
 int32_t surge_device_decoder_keep_strings(surge_device_decoder* d, int32_t on) {

@@ -110,7 +110,7 @@ struct JsonSide {
 hipError_t launch_json_encode(const surge_json_template& tmpl, const uint4* states, int64_t n, const uint8_t* keys,
                               const int64_t* key_off, int64_t* d_len_off, int64_t* d_totals, uint8_t* out, bool write_pass,
                               uint32_t envelope, const uint8_t* filter, const JsonSide& side, hipStream_t stream);
-// ---- state_decode.hip: serialized state values -> 64-byte states (surge_replay_decode_json_states) ------------------
+// ---- state_decode.hip: serialized state values -> 64-byte states (surge_replay_decode_json_states / _protobuf_states) ----
 struct F64ParseTable;
 enum { SD_WRITTEN = 0, SD_TOMBSTONES = 1, SD_REFUSED = 2, SD_AMBIGUOUS = 3, SD_FIRST_REFUSED = 4, SD_BAD_INDEX = 5, SD_N_COUNTS = 6 };
 struct StateDecodeParams {
@@ -128,6 +128,7 @@ struct StateDecodeParams {
   int64_t* spans;               // nullable
   const F64ParseTable* ptab;    // device copy of the Eisel-Lemire table (f64_parse.h)
   unsigned long long* counts;   // SD_N_COUNTS entries
+  bool envelope;                // every value is a protobuf State message around the template's text (the same for the whole launch)
 };
 hipError_t launch_state_decode(const surge_json_template& tmpl, const StateDecodeParams& p, hipStream_t stream);
 // ---- state_strings.hip: the STR spans of decoded state values -> a side string column (surge_replay_merge_state_strings) ----

@@ -8,6 +8,9 @@
 // nothing outside the span is read) and every lane parses out of LDS; a block whose span exceeds the stage parses
 // straight from global (block-uniform choice).  A lane composes its row in LDS and stores it with four 16-byte stores
 // once the whole value has parsed; a value that does not parse leaves the row alone.
+// state_decode_kernel<true> is the same kernel for values in the multilanguage module's protobuf State envelope
+// (surge_replay_decode_protobuf_states; state_parse_protobuf_state in state_parse.h): chosen at the launch, the envelope
+// being the same for every record of it.
 #include "replay_internal.h"
 #include "state_parse.h"
 
@@ -37,6 +40,7 @@ __device__ __forceinline__ void count_lanes(bool pred, unsigned long long* count
   if (m && (threadIdx.x & (warpSize - 1)) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(counter, (unsigned long long)__popcll(m));
 }
 
+template <bool ENVELOPE>
 __global__ void __launch_bounds__(kSdBlock) state_decode_kernel(const surge_json_template t, const StateDecodeParams p) {
   extern __shared__ __attribute__((aligned(16))) uint8_t sd_lds[];
   uint8_t* const rows = sd_lds;                 // 256 x 64 B: every lane's row while it parses
@@ -83,7 +87,9 @@ __global__ void __launch_bounds__(kSdBlock) state_decode_kernel(const surge_json
         const uint8_t* key = p.keys ? p.keys + p.key_off[a] : nullptr;
         const int64_t key_len = p.key_off ? p.key_off[a + 1] - p.key_off[a] : -1;
         uint8_t* row = rows + threadIdx.x * 64;
-        rc = state_parse_json<false>(t, v, o1 - o0, key, key_len, p.ptab, row, p.spans ? p.spans + r * (2 * SURGE_JSON_STRING_COLUMNS) : nullptr);
+        int64_t* span = p.spans ? p.spans + r * (2 * SURGE_JSON_STRING_COLUMNS) : nullptr;
+        if constexpr (ENVELOPE) rc = state_parse_protobuf_state<false>(t, v, o1 - o0, key, key_len, p.ptab, row, span);
+        else rc = state_parse_json<false>(t, v, o1 - o0, key, key_len, p.ptab, row, span);
         if (rc == SURGE_STATE_DECODE_OK) {
           const uint4* lr = (const uint4*)row;
 #pragma unroll
@@ -122,7 +128,8 @@ hipError_t launch_state_decode(const surge_json_template& tmpl, const StateDecod
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(state_last_record_kernel, dim3(blocks), dim3(kSdBlock), 0, stream, p.agg_idx, p.n_records, p.n_agg, p.last1, p.counts);
   }
-  hipLaunchKernelGGL(state_decode_kernel, dim3(blocks), dim3(kSdBlock), kSdLdsBytes, stream, tmpl, p);
+  if (p.envelope) hipLaunchKernelGGL(state_decode_kernel<true>, dim3(blocks), dim3(kSdBlock), kSdLdsBytes, stream, tmpl, p);
+  else hipLaunchKernelGGL(state_decode_kernel<false>, dim3(blocks), dim3(kSdBlock), kSdLdsBytes, stream, tmpl, p);
   return hipGetLastError();
 }
 

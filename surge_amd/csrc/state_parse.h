@@ -16,6 +16,8 @@
 // \" \\ \/ \b \f \n \r \t and \uXXXX for a code point outside the surrogate range, unescaped to UTF-8.  Bytes from 0x80
 // on are taken as they are (the id is compared byte for byte).
 // The parser never reads at or beyond value + len, and writes nothing but row[0 .. 64) and span[0 .. 8).
+// A value the multilanguage module wrote holds that text inside a protobuf State message: state_parse_protobuf_state (at
+// the end of this file) reads the envelope and hands the payload to the same parser.
 #pragma once
 #include <stdint.h>
 
@@ -232,6 +234,89 @@ SURGE_HD int state_parse_json(const surge_json_template& t, const uint8_t* v, in
   }
   if (i != len) return SURGE_STATE_DECODE_TRAILING;
   *(uint32_t*)(row + 36) = SURGE_STATE_PRESENT;
+  return SURGE_STATE_DECODE_OK;
+}
+
+// ---- the multilanguage module's envelope around such a text ------------------------------------------------------------
+//   message State { string aggregateId = 1; bytes payload = 2; }   (multilanguage-protocol.proto:7-10)
+// as the state encoders write it with envelope == 1 (state_kernels.hip) and GenericSurgeCommandBusinessLogic stores it
+// (pbState.toByteArray, GenericSurgeCommandBusinessLogic.scala:36-39; read back with State.parseFrom, :25-27).
+// Accepted: optionally field 1 (tag 0x0A, a length varint, that many id bytes), then optionally field 2 (tag 0x12, a
+// length varint, that many payload bytes), and nothing else: the value ends exactly behind the last accepted field.
+// proto3 omits an empty field; scalapb writes field 1 before field 2 and only that order is read, as only case-class order
+// is read of the JSON.  Any other tag, a repeated field, field 2 before field 1, a length beyond the value's end, bytes
+// behind field 2 and a value that ends inside a tag or a varint are SURGE_STATE_DECODE_ENVELOPE.
+
+// A length varint at v[*pos]: 1 - 5 bytes, value <= 2^31 - 1; an over-long (non-minimal) spelling is accepted, as the
+// protobuf runtime accepts it.  Never reads at or beyond v + len.
+SURGE_HD int sp_length_varint(const uint8_t* v, int64_t len, int64_t* pos, int64_t* value) {
+  uint64_t x = 0;
+  int64_t i = *pos;
+  for (int b = 0; b < 5; ++b) {
+    if (i >= len) return SURGE_STATE_DECODE_ENVELOPE;  // the value ends inside the varint
+    const uint32_t c = v[i++];
+    x |= (uint64_t)(c & 0x7Fu) << (7 * b);
+    if (!(c & 0x80u)) {
+      if (x > 0x7FFFFFFFull) return SURGE_STATE_DECODE_ENVELOPE;
+      *value = (int64_t)x;
+      *pos = i;
+      return SURGE_STATE_DECODE_OK;
+    }
+  }
+  return SURGE_STATE_DECODE_ENVELOPE;  // the 5th byte still continues
+}
+
+// The envelope alone: where the payload lies (*pay_off / *pay_len; an absent field 2 is the empty payload at the value's
+// end), and, with key_len >= 0, the raw bytes of field 1 against the id byte for byte (no unescaping: the encoder writes the
+// raw UTF-8 id; an absent field 1 is the empty id).  Grammar errors come before the comparison.
+SURGE_HD int sp_envelope(const uint8_t* v, int64_t len, const uint8_t* key, int64_t key_len, int64_t* pay_off, int64_t* pay_len) {
+  int64_t i = 0, id_off = 0, id_len = 0, n = 0;
+  if (i < len && v[i] == 0x0Au) {
+    ++i;
+    const int rc = sp_length_varint(v, len, &i, &n);
+    if (rc != SURGE_STATE_DECODE_OK) return rc;
+    if (n > len - i) return SURGE_STATE_DECODE_ENVELOPE;
+    id_off = i;
+    id_len = n;
+    i += n;
+  }
+  *pay_off = i;
+  *pay_len = 0;
+  if (i < len && v[i] == 0x12u) {
+    ++i;
+    const int rc = sp_length_varint(v, len, &i, &n);
+    if (rc != SURGE_STATE_DECODE_OK) return rc;
+    if (n > len - i) return SURGE_STATE_DECODE_ENVELOPE;
+    *pay_off = i;
+    *pay_len = n;
+    i += n;
+  }
+  if (i != len) return SURGE_STATE_DECODE_ENVELOPE;  // another tag, a repeated field, field 1 behind field 2, stray bytes
+  if (key_len >= 0) {
+    if (id_len != key_len) return SURGE_STATE_DECODE_KEY_MISMATCH;
+    for (int64_t b = 0; b < id_len; ++b)
+      if (v[id_off + b] != key[b]) return SURGE_STATE_DECODE_KEY_MISMATCH;
+  }
+  return SURGE_STATE_DECODE_OK;
+}
+
+// One enveloped value: sp_envelope, then the payload through state_parse_json with the payload template exactly as a bare
+// value (a KEY part inside the payload is still compared; the payload's statuses are reported as they are: an absent or
+// empty payload is what the template makes of no text).  The STR spans are relative to v, not to the payload, so that what
+// reads them (sp_unescape over the record's value) needs to know nothing of the envelope.
+template <bool RESOLVE>
+SURGE_HD int state_parse_protobuf_state(const surge_json_template& t, const uint8_t* v, int64_t len, const uint8_t* key, int64_t key_len,
+                                        const F64ParseTable* tb, uint8_t* row, int64_t* span) {
+  int64_t pay_off = 0, pay_len = 0;
+  int rc = sp_envelope(v, len, key, key_len, &pay_off, &pay_len);
+  if (rc != SURGE_STATE_DECODE_OK) return rc;
+  rc = state_parse_json<RESOLVE>(t, v + pay_off, pay_len, key, key_len, tb, row, span);
+  if (rc != SURGE_STATE_DECODE_OK || !span) return rc;
+  for (uint32_t c = 0; c < SURGE_JSON_STRING_COLUMNS; ++c) {  // (once per column, however many parts name it)
+    bool named = false;
+    for (uint32_t p = 0; p < t.n_parts; ++p) named = named || (t.part[p].kind == SURGE_JP_STR && t.part[p].field_offset == c);
+    if (named) span[2 * c] += pay_off;
+  }
   return SURGE_STATE_DECODE_OK;
 }
 

@@ -103,10 +103,9 @@ def encode_states(engine: ReplayEngine, template: JsonTemplate, d_keys_utf8, d_k
     holds a NaN / infinite Double (no JSON number exists; those aggregates get zero bytes)."""
     import torch
 
-    if envelope not in ("none", "protobuf_state"):
-        raise ValueError(f"unknown envelope {envelope!r}")
+    wrapped = check_envelope(envelope)
     lib = _native.load()
-    fn = lib.surge_replay_encode_json if envelope == "none" else lib.surge_replay_encode_protobuf_state
+    fn = lib.surge_replay_encode_protobuf_state if wrapped else lib.surge_replay_encode_json
     n = engine.n_agg
     dev = d_key_off.device
     for c in range(STRING_COLUMNS):
@@ -137,9 +136,18 @@ def encode_states(engine: ReplayEngine, template: JsonTemplate, d_keys_utf8, d_k
 # ---- the way back: serialized state values -> fixed 64-byte states -----------------------------------------------------
 #: ``SURGE_STATE_DECODE_*`` (``include/surge_replay.h``)
 DECODE_STATUS = {0: "OK", 1: "LITERAL", 2: "STRING", 3: "ESCAPE", 4: "KEY_MISMATCH", 5: "INT", 6: "RANGE", 7: "NUMBER", 8: "TRAILING",
-                 9: "AMBIGUOUS", 10: "SURROGATE", 255: "SKIPPED"}
+                 9: "AMBIGUOUS", 10: "SURROGATE", 11: "ENVELOPE", 255: "SKIPPED"}
 DECODE_OK, DECODE_LITERAL, DECODE_STRING, DECODE_ESCAPE, DECODE_KEY_MISMATCH, DECODE_INT, DECODE_RANGE = 0, 1, 2, 3, 4, 5, 6
 DECODE_NUMBER, DECODE_TRAILING, DECODE_AMBIGUOUS, DECODE_SURROGATE, DECODE_SKIPPED = 7, 8, 9, 10, 255
+DECODE_ENVELOPE = 11
+ENVELOPES = ("none", "protobuf_state")
+
+
+def check_envelope(envelope) -> bool:
+    """``True`` for the protobuf ``State`` envelope, ``False`` for bare text; the spellings are ``encode_states``'."""
+    if envelope not in ENVELOPES:
+        raise ValueError(f"unknown envelope {envelope!r}")
+    return envelope == "protobuf_state"
 
 
 class DecodedStates(tuple):
@@ -150,28 +158,34 @@ class DecodedStates(tuple):
     refused = None
 
 
-def decode_state_host(template: JsonTemplate, value: bytes, key=None):
-    """One serialized state value on the host (``surge_decode_json_state``: the parser the device kernel runs).  Returns
+def decode_state_host(template: JsonTemplate, value: bytes, key=None, envelope: str = "none"):
+    """One serialized state value on the host (``surge_decode_json_state``: the parser the device kernel runs;
+    ``envelope="protobuf_state"``: ``surge_decode_protobuf_state``, the value is the multilanguage module's
+    ``State{aggregateId, payload}`` message around the template's text, field 1 is compared with ``key`` byte for byte and the
+    spans are relative to the whole value).  Returns
     ``(status, state, spans)``: a ``SURGE_STATE_DECODE_*`` status, the state (a one-element ``STATE_DTYPE`` array, zeros
     unless the status is 0) and ``spans[c] = (offset, length)`` of STR column ``c``'s still-escaped bytes.  ``key``
     (``str`` or UTF-8 ``bytes``): the id the KEY string must equal; ``None``: not compared."""
     from .schema import STATE_DTYPE
 
+    lib = _native.load()
+    fn = lib.surge_decode_protobuf_state if check_envelope(envelope) else lib.surge_decode_json_state
     t = template.to_c()
     value = bytes(value)
     kb = None if key is None else (key.encode("utf-8") if isinstance(key, str) else bytes(key))
     state = np.zeros(1, dtype=STATE_DTYPE)
     span = (ctypes.c_int64 * (2 * STRING_COLUMNS))()
-    rc = _native.load().surge_decode_json_state(ctypes.byref(t), value, len(value), kb, -1 if kb is None else len(kb),
-                                                state.ctypes.data_as(ctypes.c_void_p), span)
+    rc = fn(ctypes.byref(t), value, len(value), kb, -1 if kb is None else len(kb), state.ctypes.data_as(ctypes.c_void_p), span)
     if rc < 0:
-        raise ValueError("surge_decode_json_state: bad argument or inconsistent template")
+        raise ValueError(("surge_decode_json_state" if envelope == "none" else "surge_decode_protobuf_state") + ": bad argument or inconsistent template")
     return rc, state, [(span[2 * c], span[2 * c + 1]) for c in range(STRING_COLUMNS)]
 
 
 def decode_states(engine: ReplayEngine, template: JsonTemplate, d_values, d_value_off, d_keys_utf8=None, d_key_off=None, d_agg_idx=None,
-                  out=None, want_spans: bool = False, raise_on_refused: bool = False):
-    """Decode state-topic record values on the device (``surge_replay_decode_json_states``): record ``r``'s text is
+                  out=None, want_spans: bool = False, raise_on_refused: bool = False, envelope: str = "none"):
+    """Decode state-topic record values on the device (``surge_replay_decode_json_states``; ``envelope="protobuf_state"``:
+    ``surge_replay_decode_protobuf_states``, every value is a ``State{aggregateId, payload}`` message around the template's
+    text and the spans are relative to the whole value): record ``r``'s text is
     ``d_values[d_value_off[r]:d_value_off[r+1]]`` (empty = tombstone) and names aggregate ``d_agg_idx[r]`` (``None``: aggregate
     ``r``); per aggregate the last record wins.  ``out``: the ``n_agg x 64`` byte CUDA tensor the rows go to (rows nothing
     names, and rows whose winner does not decode, keep what they hold) — ``None``: a fresh all-None tensor of one row per
@@ -183,6 +197,7 @@ def decode_states(engine: ReplayEngine, template: JsonTemplate, d_values, d_valu
     import torch
 
     lib = _native.load()
+    fn = lib.surge_replay_decode_protobuf_states if check_envelope(envelope) else lib.surge_replay_decode_json_states
     n = int(d_value_off.numel()) - 1
     dev = d_value_off.device
     if out is None:
@@ -196,7 +211,7 @@ def decode_states(engine: ReplayEngine, template: JsonTemplate, d_values, d_valu
     counts = (ctypes.c_int64 * 4)()
     t = template.to_c()
     ptr = lambda x: ctypes.c_void_p(x.data_ptr()) if x is not None and x.numel() else None  # noqa: E731
-    rc = lib.surge_replay_decode_json_states(
+    rc = fn(
         engine._h, ctypes.byref(t), ptr(d_values), ctypes.c_void_p(d_value_off.data_ptr()), n, ptr(d_keys_utf8),
         ctypes.c_void_p(d_key_off.data_ptr()) if d_key_off is not None else None, ptr(d_agg_idx), n_agg, ctypes.c_void_p(out.data_ptr()),
         ptr(status), ptr(spans), ctypes.byref(counts))

@@ -707,16 +707,21 @@ class DeviceDecoder:
         values = view(pv, total, "|u1") if total else torch.zeros(0, dtype=torch.uint8, device=dev)
         return view(pa, n.value, "<i8"), values, value_off, view(po, n.value, "<i8"), nk.value
 
-    def load_states_into(self, engine, template):
-        """A state decoder's hand-over (``surge_device_decoder_load_states``): everything delivered since the last clear is
+    def load_states_into(self, engine, template, envelope: str = "none"):
+        """A state decoder's hand-over (``surge_device_decoder_load_states``; ``envelope="protobuf_state"``:
+        ``surge_device_decoder_load_protobuf_states``, the values are the multilanguage module's ``State`` messages around the
+        template's text): everything delivered since the last clear is
         decoded through ``template`` (the model's serialized state, ``encode.JsonTemplate``) into ``engine``'s resident state
         — grown first for ids seen for the first time; per aggregate the last record wins, a tombstone zeroes the row — and
         the decoder is cleared.  Returns the decode's counts ``(rows written, tombstones, winners refused, Doubles re-parsed
         on the host)``; a refused winner raises ``IngestError`` (CORRUPT, naming the record's topic offset) after everything
         else was loaded."""
+        from .encode import check_envelope
+
+        fn = self._lib.surge_device_decoder_load_protobuf_states if check_envelope(envelope) else self._lib.surge_device_decoder_load_states
         counts = (ctypes.c_int64 * 4)()
         t = template.to_c()
-        rc = self._lib.surge_device_decoder_load_states(self._h, engine._h, ctypes.byref(t), ctypes.byref(counts))
+        rc = fn(self._h, engine._h, ctypes.byref(t), ctypes.byref(counts))
         engine.n_agg = max(engine.n_agg, self.n_keys)  # (grown inside the call)
         self._check(rc)
         return tuple(int(c) for c in counts)

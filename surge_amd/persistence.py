@@ -31,7 +31,7 @@ from dataclasses import dataclass, field
 from typing import Callable, Dict, Generic, List, Optional, Sequence, Tuple, TypeVar
 
 from .command import SurgeCommandBusinessLogic
-from .core import SurgeContext
+from .core import SurgeContext, write_state_of
 from .snapshot import StateRecord
 from .store import AggregateInitializationException, GpuReplayStateStore
 
@@ -187,7 +187,7 @@ class GpuPersistentActor(Generic[Agg]):
         topic = self.business_logic.state_topic.name
         if state is None:
             return StateRecord(topic, self.assigned_partition, self.aggregate_id, None)
-        ser = self.business_logic.aggregate_write_formatting().write_state(state)
+        ser = write_state_of(self.business_logic.aggregate_write_formatting(), self.aggregate_id, state)
         return StateRecord(topic, self.assigned_partition, self.aggregate_id, ser.value, dict(ser.headers))
 
     def _serialize_events(self, events: Sequence[Tuple[object, object]]) -> List[EventRecord]:

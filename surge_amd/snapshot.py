@@ -23,6 +23,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native
+from .core import write_state_of
 from .kafka import partition_for_keys
 from .schema import STATE_POISONED, STATE_PRESENT
 from .store import GpuReplayStateStore
@@ -60,7 +61,7 @@ class SnapshotWriter:
             if fl & STATE_POISONED:
                 continue  # replay of this aggregate failed: publish nothing rather than a state the JVM fold never had
             if fl & STATE_PRESENT:
-                ser = fmt.write_state(self.store.model.state_from_fixed(k, st))
+                ser = write_state_of(fmt, k, self.store.model.state_from_fixed(k, st))
                 out.append(StateRecord(self.topic, int(part), k, ser.value, dict(ser.headers)))
             else:
                 out.append(StateRecord(self.topic, int(part), k, None))
@@ -228,16 +229,21 @@ class BulkSnapshotPublisher:
     ``keys`` are the aggregate ids in dense-index order; ``template`` declares the model's serialized state."""
 
     def __init__(self, engine, keys: Optional[Sequence[str]], n_partitions: int, template=None, device=None, tables=None,
-                 compression: str = "none", device_framing: bool = True, device_compression: bool = False, strings=()):
+                 compression: str = "none", device_framing: bool = True, device_compression: bool = False, strings=(),
+                 envelope: str = "none"):
         """``keys``: aggregate ids in dense-index order; or ``tables = (keys_utf8, key_off, keys_utf16, off16)`` as
         tensors / arrays built without Python strings (large synthetic populations).  ``compression``: "none" or "lz4"
         (the reference producer's ``compression.type``).  ``device_compression``: lz4 batches are framed AND compressed
         by the ``DeviceFramer`` (needs ``device_framing``); without it they go through the host writer and its compressor.
         ``strings``: the side string columns of a template with ``(JP_STR, column)`` parts, as ``encode_states`` takes them
-        (e.g. a resumed store's ``state_string_columns()``); the attribute may be replaced between publishes."""
+        (e.g. a resumed store's ``state_string_columns()``); the attribute may be replaced between publishes.
+        ``envelope``: ``encode_states``' — ``"protobuf_state"`` publishes what a multilanguage (SDK) application stores."""
         import torch
 
-        from .encode import JsonTemplate, key_table_utf8
+        from .encode import JsonTemplate, check_envelope, key_table_utf8
+
+        check_envelope(envelope)
+        self.envelope = envelope
         from .kafka import utf16_table
 
         self.engine, self.n_partitions = engine, n_partitions
@@ -297,7 +303,7 @@ class BulkSnapshotPublisher:
         eng._check(lib.surge_replay_set_encode_filter(eng._h, ctypes.c_void_p(d_kind.data_ptr())))
         try:
             d_out, d_off = encode_states(eng, self.template, self.d_keys, self.d_key_off, capacity_hint=max(64, 96 * nv.value + int(self.d_keys.numel())) if not self.strings else 0,
-                                          strings=self.strings)
+                                          strings=self.strings, envelope=self.envelope)
         finally:
             eng._check(lib.surge_replay_set_encode_filter(eng._h, None))
         torch.cuda.synchronize(self.device)
@@ -371,7 +377,7 @@ class BulkSnapshotPublisher:
         eng._check(lib.surge_replay_set_encode_filter(eng._h, ctypes.c_void_p(d_kind.data_ptr())))
         try:
             d_out, d_off = encode_states(eng, self.template, self.d_keys, self.d_key_off, capacity_hint=max(64, 96 * nv.value + int(self.d_keys.numel())) if not self.strings else 0,
-                                          strings=self.strings)
+                                          strings=self.strings, envelope=self.envelope)
         except Exception:
             eng._check(lib.surge_replay_set_encode_filter(eng._h, None))
             eng._check(lib.surge_replay_snapshot_invalidate(eng._h, ctypes.c_void_p(d_kind.data_ptr())))

@@ -23,6 +23,7 @@ from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .command import ReplayableCommandModel, SurgeCommandBusinessLogic
+from .core import write_state_of
 from .log import EventLog, KeyTable, pack_events
 from .replay import ReplayEngine
 from .schema import ALGO_AUTO, STATE_DTYPE, STATE_POISONED, STATE_PRESENT
@@ -265,7 +266,7 @@ class GpuReplayStateStore:
         self._restored = True
         return counters
 
-    def restore_from_state_records(self, records, events_tail: Sequence = (), template=None) -> dict:
+    def restore_from_state_records(self, records, events_tail: Sequence = (), template=None, envelope: str = "none") -> dict:
         """Resume from the compacted *state* topic instead of replaying every event — what the reference's restore does
         (``SurgeStateStoreConsumer.scala:57-76``, records written by ``SurgeModel.scala:57-65``).  ``records``: ``(key,
         value_or_None)`` pairs or ``snapshot.StateRecord`` objects in offset order; per key the last record wins and
@@ -275,15 +276,18 @@ class GpuReplayStateStore:
         events behind the snapshot — is folded on top.  Fields the template does not name take the algebra's defaults,
         as ``state_to_fixed`` gives them on the ``restore(prior=...)`` path; the POISONED flag and the sign of ``-0.0``
         are not in the text and are not restored.  A winning value that does not decode raises ``ReplayError`` (CORRUPT).
-        Returns the decoder's counts."""
+        ``envelope="protobuf_state"``: the values are what a multilanguage (SDK) application stores, the protobuf
+        ``State{aggregateId, payload}`` message around the template's text (``GenericSurgeCommandBusinessLogic.scala:25-27,
+        36-39``); any other field, order or repetition is refused, not skipped.  Returns the decoder's counts."""
         import ctypes
 
         import torch
 
         from . import _native
-        from .encode import STRING_COLUMNS, JsonTemplate, decode_states, key_table_utf8, merge_state_strings
+        from .encode import STRING_COLUMNS, JsonTemplate, check_envelope, decode_states, key_table_utf8, merge_state_strings
         from .schema import EVENT_DTYPE
 
+        check_envelope(envelope)
         template = template or JsonTemplate.counter()
         str_columns = _str_columns(template)
         self.state_strings = None
@@ -312,7 +316,7 @@ class GpuReplayStateStore:
             d_off, d_agg = to_dev(off), to_dev(np.asarray(agg_idx, dtype=np.int64))
             try:
                 res = decode_states(eng, template, d_values, d_off, to_dev(data), to_dev(key_off), d_agg,
-                                    out=eng.device_state(), want_spans=bool(str_columns), raise_on_refused=True)
+                                    out=eng.device_state(), want_spans=bool(str_columns), raise_on_refused=True, envelope=envelope)
             finally:
                 eng._check(lib.surge_replay_set_decode_base(eng._h, None))
             counts = res[2]
@@ -333,7 +337,7 @@ class GpuReplayStateStore:
         return {"rows_written": counts[0], "tombstones": counts[1], "refused": counts[2], "reparsed_on_host": counts[3]}
 
     def restore_from_state_topic(self, fetches, n_partitions: int = 0, template=None, events_tail: Sequence = (), framing_threads: int = 4,
-                                 device_crc: bool = True, in_place: bool = True) -> dict:
+                                 device_crc: bool = True, in_place: bool = True, envelope: str = "none") -> dict:
         """``restore_from_state_records`` from what a consumer of the state topic actually receives: ``fetches`` yields the
         topic's bytes — message-format-v2 record batches, LZ4 or uncompressed, transactional, with the producer's flush
         records, tombstones as null values and the offset gaps log compaction leaves — one ``bytes`` per fetch, or with
@@ -341,18 +345,19 @@ class GpuReplayStateStore:
         ``restore_from_fetches``' (``FramedFetches`` / ``PartitionedFramedFetches``, ``read_committed``); a state-mode
         ``DeviceDecoder`` finds the records and interns the ids on the device (up to four pushes in flight; the oldest is
         finished, then loaded: ``load_states_into``) — no per-record work in Python.  The loaded states become the snapshot
-        baseline, then ``events_tail`` is folded on top, exactly as ``restore_from_state_records`` does.  Returns the
+        baseline, then ``events_tail`` is folded on top, exactly as ``restore_from_state_records`` does (``envelope`` as there).  Returns the
         framer's and the decoder's counters plus the summed decode counts."""
         import ctypes
 
         import torch
 
         from . import _native
-        from .encode import JsonTemplate
+        from .encode import JsonTemplate, check_envelope
         from .ingest import DeviceDecoder, FramedFetches, PartitionedFramedFetches
         from .log import KeyTable
         from .schema import EVENT_DTYPE
 
+        check_envelope(envelope)
         template = template or JsonTemplate.counter()
         eng, lib = self.engine, _native.load()
         eng.load_csr(np.zeros(1, dtype=np.int64), np.zeros(0, dtype=EVENT_DTYPE))
@@ -368,7 +373,7 @@ class GpuReplayStateStore:
 
             def finish_one():
                 d.finish()
-                for i, c in enumerate(d.load_states_into(eng, template)):
+                for i, c in enumerate(d.load_states_into(eng, template, envelope=envelope)):
                     totals[i] += c
 
             framer = (PartitionedFramedFetches(fetches, n_partitions, threads=framing_threads, hold=depth, overlap=True, device_crc=device_crc, in_place=in_place)
@@ -476,7 +481,7 @@ class GpuReplayStateStore:
         agg = self.get_aggregate(aggregate_id)
         if agg is None:
             return None
-        return self.business_logic.aggregate_write_formatting().write_state(agg).value
+        return write_state_of(self.business_logic.aggregate_write_formatting(), aggregate_id, agg).value
 
     def get_aggregate(self, aggregate_id: str):
         idx = self.keys.get(aggregate_id)
