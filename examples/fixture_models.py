@@ -600,6 +600,14 @@ class SdkSampleCommandModel(ReplayableCommandModel[SdkBankAccount, DepositMoney,
     def aggregate_id_of(self, event: SdkEvent) -> str:
         return event.aggregateId
 
+    def event_json_template(self):
+        """What the gateway stores on the events topic for the sample: ``Event(aggregateId, payload).toByteArray``
+        (GenericSurgeCommandBusinessLogic.scala:30-34) around the SDK's json4s text ``{"amount":N}`` (Main.scala:21, 42-58) —
+        one event class, no discriminator."""
+        from surge_amd.ingest import ARG_I32, EventJsonTemplate
+
+        return EventJsonTemplate("", [("", SDK_DEPOSITED, "", "amount", ARG_I32)], envelope="protobuf_event")
+
     def state_from_fixed(self, aggregate_id: str, fixed) -> SdkBankAccount:
         return SdkBankAccount(int(fixed["count"]))
 
@@ -624,6 +632,17 @@ def sdk_sample_state_bytes(aggregate_id: str, state: SdkBankAccount) -> bytes:
     """``protobuf.State(aggregateId, ByteString(write(state))).toByteArray``: json4s' compact text in field 2, the
     id in field 1; proto3 leaves an empty field out."""
     payload = ('{"balance":%d}' % state.balance).encode("ascii")
+    key = aggregate_id.encode("utf-8")
+    out = b""
+    if key:
+        out += b"\x0a" + protobuf_varint(len(key)) + key
+    return out + b"\x12" + protobuf_varint(len(payload)) + payload
+
+
+def sdk_sample_event_bytes(aggregate_id: str, event: MoneyDeposited) -> bytes:
+    """``protobuf.Event(aggregateId, ByteString(write(event))).toByteArray``: the message has ``State``'s shape
+    (multilanguage-protocol.proto:17-20), the payload is json4s' compact text of the event."""
+    payload = ('{"amount":%d}' % event.amount).encode("ascii")
     key = aggregate_id.encode("utf-8")
     out = b""
     if key:
@@ -683,6 +702,19 @@ class SdkSampleStateFormat(SurgeAggregateFormatting[SdkBankAccount]):
             return None
 
 
+class SdkSampleEventFormat:
+    """``GenericSurgeCommandBusinessLogic.eventWriteFormatting`` (GenericSurgeCommandBusinessLogic.scala:30-34):
+    ``SerializedMessage(evt.aggregateId, Event(aggregateId, payload).toByteArray)`` — the record key is the aggregate id
+    alone.  ``read_event`` is additive (``Event.parseFrom``: the envelope's one accepted shape, ``parse_state_envelope``)."""
+
+    def write_event(self, evt: SdkEvent) -> SerializedMessage:
+        return SerializedMessage(evt.aggregateId, sdk_sample_event_bytes(evt.aggregateId, evt.payload))
+
+    def read_event(self, msg: SerializedMessage) -> SdkEvent:
+        aggregate_id, payload = parse_state_envelope(bytes(msg.value))
+        return SdkEvent(aggregate_id, MoneyDeposited(int(json.loads(payload)["amount"])))
+
+
 class SdkSampleBusinessLogic(SurgeCommandBusinessLogic[SdkBankAccount, DepositMoney, SdkEvent]):
     """The sample behind ``GenericSurgeCommandBusinessLogic`` (GenericSurgeCommandBusinessLogic.scala:14-45): the sample's
     model, states stored in the protobuf ``State`` envelope.  Names are the gateway's defaults
@@ -695,6 +727,7 @@ class SdkSampleBusinessLogic(SurgeCommandBusinessLogic[SdkBankAccount, DepositMo
     def __init__(self):
         self._model = SdkSampleCommandModel()
         self._agg_format = SdkSampleStateFormat()
+        self._evt_format = SdkSampleEventFormat()
 
     def command_model(self):
         return self._model
@@ -704,3 +737,6 @@ class SdkSampleBusinessLogic(SurgeCommandBusinessLogic[SdkBankAccount, DepositMo
 
     def aggregate_write_formatting(self):
         return self._agg_format
+
+    def event_write_formatting(self):
+        return self._evt_format

@@ -97,9 +97,21 @@ typedef struct surge_event_json_type {
   char     seq_field[SURGE_EVJ_NAME]; /* integer field -> surge_event16.seq ("" = 0)                             */
   char     arg_field[SURGE_EVJ_NAME]; /* field -> payload ("" with SURGE_EVJ_ARG_NONE)                           */
 } surge_event_json_type;
+/* What lies around the JSON text in a record's value.  A multilanguage (SDK) application writes its events topic as the
+ * protobuf message Event { string aggregateId = 1; bytes payload = 2; } (multilanguage-protocol.proto:17-20;
+ * GenericSurgeCommandBusinessLogic.scala:30-34 stores Event(aggregateId, payload).toByteArray under the key aggregateId):
+ * with SURGE_EVJ_ENVELOPE_PROTOBUF_EVENT a value is read as optionally field 1 (tag 0x0A, length varint, id bytes), then
+ * optionally field 2 (tag 0x12, length varint, payload bytes) and nothing else — the grammar of the State envelope
+ * (surge_replay.h): length varints of 1 - 5 bytes and at most 2^31 - 1, over-long spellings read, any other tag, order or
+ * repetition refused — and the payload goes through the rules above exactly as a bare value (an absent or empty payload
+ * is not a JSON object).  Where the record's key is known (surge_ingest_drain_json, surge_event_json_decode_keyed, every
+ * push of a surge_device_decoder) field 1 must equal, byte for byte, the aggregate id the record is interned under: the
+ * key up to the first ':'; an absent field 1 is the empty id.  Grammar errors are reported before a differing id. */
+#define SURGE_EVJ_ENVELOPE_NONE           0 /* the value IS the JSON text (a zeroed field: what this field meant while it was reserved) */
+#define SURGE_EVJ_ENVELOPE_PROTOBUF_EVENT 1
 typedef struct surge_event_json_template {
   uint32_t n_types;
-  uint32_t reserved;
+  uint32_t envelope;                      /* SURGE_EVJ_ENVELOPE_*; any other value is refused by surge_event_json_validate */
   char     discriminator[SURGE_EVJ_NAME]; /* e.g. "_type"; "" = every value is types[0]                            */
   surge_event_json_type types[SURGE_EVJ_MAX_TYPES];
 } surge_event_json_template;
@@ -107,6 +119,11 @@ int32_t surge_event_json_validate(const surge_event_json_template* t);
 /* One record value -> one 16-byte event.  0 or SURGE_E_CORRUPT (malformed JSON, unknown type, missing field, a number
  * that is not what the template says); the reason is in surge_event_json_last_error() (thread-local). */
 int32_t surge_event_json_decode(const surge_event_json_template* t, const uint8_t* value, int64_t len, void* event16_out);
+/* The same, and with an enveloped template the envelope's aggregateId is compared with key[0 .. key_len): the caller passes
+ * the aggregate id, i.e. the record key already cut at its first ':'.  key_len < 0: no comparison — what
+ * surge_event_json_decode does.  A template without an envelope ignores the key. */
+int32_t surge_event_json_decode_keyed(const surge_event_json_template* t, const uint8_t* key, int64_t key_len, const uint8_t* value, int64_t len,
+                                      void* event16_out);
 const char* surge_event_json_last_error(void);
 /* A JSON number -> the bits of the nearest IEEE double, ties to even (what BigDecimal(text).doubleValue gives play-json):
  * the Eisel-Lemire algorithm (surge_amd/csrc/f64_parse.h — the same code decodes Doubles on the device), with strtod
@@ -115,7 +132,8 @@ const char* surge_event_json_last_error(void);
 int32_t surge_parse_f64_json(const uint8_t* text, int64_t len, uint64_t* bits_out);
 /* Like surge_ingest_drain_fixed16 for topics whose values are JSON events: pops up to max deliverable records and
  * decodes each value through the template — no per-record work in the host language.  Nothing is popped when a value
- * does not decode (SURGE_E_CORRUPT; surge_ingest_last_error names the record's offset and the reason). */
+ * does not decode (SURGE_E_CORRUPT; surge_ingest_last_error names the record's offset and the reason).  Enveloped values
+ * (tmpl->envelope) are decoded with surge_event_json_decode_keyed against the record's aggregate id. */
 int32_t surge_ingest_drain_json(surge_ingest* g, int64_t max, const surge_event_json_template* tmpl, int64_t* agg_idx_out,
                                 void* events16_out, int64_t* offsets_out, int64_t* n_out);
 
@@ -228,7 +246,10 @@ typedef struct surge_device_decoder surge_device_decoder;
  * the interning and the fold of fetch i.) */
 /* tmpl == NULL: record values are 16-byte surge_event16; otherwise the reference's JSON event text, decoded by the
  * template with surge_event_json_decode's rules (Doubles correctly rounded on the device — f64_parse.h — the rare value
- * its fast path cannot decide is re-parsed on the host).  hip_stream: the stream the decoder works on (NULL = default). */
+ * its fast path cannot decide is re-parsed on the host).  tmpl->envelope travels with the template: every push of such a
+ * decoder — push, push_async / push_parts_async, push_records — reads the protobuf Event envelope in front of the JSON text
+ * and compares its aggregateId with the record's aggregate id; a value that is no such envelope, or names another id, fails
+ * the push like every bad record.  hip_stream: the stream the decoder works on (NULL = default). */
 int32_t surge_device_decoder_create(int32_t device_id, void* hip_stream, const surge_event_json_template* tmpl, surge_device_decoder** out);
 /* STATE MODE: a decoder for the compacted STATE topic (what SurgeStateStoreConsumer.scala:57-76 reads, records written by
  * SurgeModel.scala:57-65).  Every other entry point works on it unchanged — push, push_async / push_parts_async,

@@ -152,6 +152,7 @@ INGEST_EXPORTS = (
     "surge_device_decoder_stats",
     "surge_event_json_validate",
     "surge_event_json_decode",
+    "surge_event_json_decode_keyed",
     "surge_event_json_last_error",
     "surge_parse_f64_json",
     "surge_ingest_key_count",
@@ -406,6 +407,7 @@ def load() -> ctypes.CDLL:
         "surge_device_decoder_stats": ([vp, ctypes.POINTER(i64 * 8)], i32),
         "surge_event_json_validate": ([vp], i32),
         "surge_event_json_decode": ([vp, vp, i64, vp], i32),
+        "surge_event_json_decode_keyed": ([vp, vp, i64, vp, i64, vp], i32),
         "surge_event_json_last_error": ([], ctypes.c_char_p),
         "surge_parse_f64_json": ([vp, i64, ctypes.POINTER(ctypes.c_uint64)], i32),
         "surge_ingest_key_count": ([vp], i64),

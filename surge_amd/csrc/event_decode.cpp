@@ -22,6 +22,7 @@
 #include <string>
 
 #include "../../include/surge_ingest.h"
+#include "state_parse.h"  // sp_envelope: the one text of the protobuf envelope's grammar (host, state kernel, event kernels)
 
 namespace {
 
@@ -158,14 +159,33 @@ int32_t surge_event_json_validate(const surge_event_json_template* t) {
     if (e.arg_kind > SURGE_EVJ_ARG_F64) return bad("unknown arg_kind");
     if ((e.arg_kind == SURGE_EVJ_ARG_NONE) != (e.arg_field[0] == 0)) return bad("arg_field and arg_kind disagree");
   }
+  if (t->envelope > SURGE_EVJ_ENVELOPE_PROTOBUF_EVENT) return bad("unknown envelope");
   return 0;
 }
 
 // One record value -> one 16-byte event.  0 = OK; SURGE_E_CORRUPT = not the JSON the template describes (message in
 // surge_event_json_last_error).
 int32_t surge_event_json_decode(const surge_event_json_template* t, const uint8_t* value, int64_t len, void* event16_out) {
+  return surge_event_json_decode_keyed(t, nullptr, -1, value, len, event16_out);
+}
+
+// ... with the envelope the template names read first (sp_envelope, state_parse.h: the grammar, then field 1 against
+// key[0 .. key_len) when key_len >= 0), and the payload through the rules below exactly as a bare value.
+int32_t surge_event_json_decode_keyed(const surge_event_json_template* t, const uint8_t* key, int64_t key_len, const uint8_t* value, int64_t len,
+                                      void* event16_out) {
   auto corrupt = [](const std::string& m) { t_err = m; return (int32_t)SURGE_E_CORRUPT; };
-  if (!t || !event16_out || (!value && len > 0) || len < 0) { t_err = "bad argument"; return -1; }
+  if (!t || !event16_out || (!value && len > 0) || len < 0 || (!key && key_len > 0)) { t_err = "bad argument"; return -1; }
+  if (t->envelope == SURGE_EVJ_ENVELOPE_PROTOBUF_EVENT) {
+    int64_t pay_off = 0, pay_len = 0;
+    const int rc = surge::sp_envelope(value, len, key, key_len, &pay_off, &pay_len);
+    if (rc == SURGE_STATE_DECODE_KEY_MISMATCH) return corrupt("the aggregateId in the event's envelope is not the record's aggregate id");
+    if (rc != SURGE_STATE_DECODE_OK) return corrupt("event value is not the protobuf Event envelope ([aggregateId] [payload] and nothing else)");
+    value += pay_off;
+    len = pay_len;
+  } else if (t->envelope != SURGE_EVJ_ENVELOPE_NONE) {
+    t_err = "unknown envelope";
+    return -1;
+  }
   Scanner sc{value, value + len};
   sc.ws();
   if (sc.p >= sc.end || *sc.p != '{') return corrupt("event value is not a JSON object");

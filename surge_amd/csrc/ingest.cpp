@@ -792,10 +792,16 @@ int32_t surge_ingest_drain_json(surge_ingest* g, int64_t max, const surge_event_
   if (surge_event_json_validate(tmpl) != 0) return fail(g, E_INVALID, std::string("event template: ") + surge_event_json_last_error());
   uint8_t* ev = (uint8_t*)events16_out;
   int32_t refused = OK;
+  auto decode_keyed = [&](const Rec& r, uint8_t* out) {  // an enveloped value names its aggregate: the id the record is interned under (the key up to ':')
+    const uint8_t* key = g->arena_now().data() + r.key_off;
+    int64_t n = 0;
+    while (n < r.key_len && key[n] != (uint8_t)':') ++n;  // PartitionStringUpToColon, as intern() cuts it
+    return surge_event_json_decode_keyed(tmpl, key, n, g->arena_now().data() + r.value_off, r.value_len, out);
+  };
   visit_ready<false>(g, max, [&](Rec& r, int64_t k) {
     if (r.agg_idx == -1 || r.value_len < 0) {
       refused = fail(g, SURGE_E_CORRUPT, "record at offset " + std::to_string(r.offset) + " has a null key or value (not an event)");
-    } else if (surge_event_json_decode(tmpl, g->arena_now().data() + r.value_off, r.value_len, ev + k * 16) != OK) {
+    } else if (decode_keyed(r, ev + k * 16) != OK) {
       refused = fail(g, SURGE_E_CORRUPT, "record at offset " + std::to_string(r.offset) + ": " + surge_event_json_last_error());
     }
     return refused == OK;

@@ -391,13 +391,18 @@ int32_t surge_device_decoder_destroy(surge_device_decoder* d) {
 
 namespace {
 
+// the envelope the decoder's template names (h_tmpl: validated at create), as JsonCtx carries it
+int16_t envelope_of(const surge_device_decoder* d) { return d->json ? (int16_t)d->h_tmpl.envelope : (int16_t)0; }
+
 const char* why_bad(uint32_t status) {
   static const char* why[] = {"", "", "has a null key or value (not an event)", "is malformed (a length runs past its record or batch)",
                               "is not the JSON object the event template describes", "names an event type the template does not know",
                               "lacks a field the template names, or the field is not the number it should be", "is not a 16-byte fixed event", "",
                               "collides with another key on its 64-bit hash",
-                              "has an empty, non-null value under a key (a state record carries a value or the null of a tombstone)"};
-  return status < 11 ? why[status] : "is bad";
+                              "has an empty, non-null value under a key (a state record carries a value or the null of a tombstone)",
+                              "is not the protobuf Event envelope the event template names ([aggregateId] [payload] and nothing else)",
+                              "names another aggregateId in its envelope than the aggregate id of its key"};
+  return status < 13 ? why[status] : "is bad";
 }
 
 struct DeviceScope {  // the calling thread's device, restored on the way out
@@ -700,7 +705,7 @@ int32_t stage1_wire(surge_device_decoder* d, PushSlot& s, int32_t n_parts, const
   Lz4Work w{dbg_decode() / 10, (int32_t*)s.lz4_sizes.p, (int32_t*)s.lz4_nseq.p, (uint2*)s.lz4_seq.p, (int32_t*)s.lz4_cls.p, nullptr};
   DCHK(d, launch_lz4(s.lz4, dby, (uint8_t*)s.d_bytes.p + L.area_base(), (const Lz4Block*)s.lz4_blocks.p, w, dsec, derr, st));
   laps.lap("lz4 launches");
-  JsonCtx jc{d->json ? (const EvjDevice*)d->d_tmpl.p : nullptr, (const surge::F64ParseTable*)d->d_ptab.p, dbg_decode() % 10, d->states ? 1 : 0};
+  JsonCtx jc{d->json ? (const EvjDevice*)d->d_tmpl.p : nullptr, (const surge::F64ParseTable*)d->d_ptab.p, dbg_decode() % 10, (int16_t)(d->states ? 1 : 0), envelope_of(d)};
   DCHK(d, launch_sections(dby, dsec, L.total_sections, L.max_recs, seed, jc, (RecMeta*)s.meta.p, (uint4*)s.ev_tmp.p, (uint32_t*)s.f64_list.p, derr, st));
   laps.lap("section launches");
   s.n_rec = L.n_rec;
@@ -746,7 +751,7 @@ int32_t stage1_records(surge_device_decoder* d, PushSlot& s, const uint8_t* keys
   DCHK(d, hipMemcpyAsync(s.rec_b.p, p_vo, off_bytes, hipMemcpyHostToDevice, st));
   if (offsets) DCHK(d, hipMemcpyAsync(s.rec_c.p, p_of, (size_t)n * 8, hipMemcpyHostToDevice, st));
   DCHK(d, launch_records((const uint8_t*)s.d_bytes.p, (const int64_t*)s.rec_a.p, (const int64_t*)s.rec_b.p, offsets ? (const int64_t*)s.rec_c.p : nullptr, kb, n, seed,
-                         JsonCtx{d->json ? (const EvjDevice*)d->d_tmpl.p : nullptr, (const surge::F64ParseTable*)d->d_ptab.p, 0, d->states ? 1 : 0}, (RecMeta*)s.meta.p,
+                         JsonCtx{d->json ? (const EvjDevice*)d->d_tmpl.p : nullptr, (const surge::F64ParseTable*)d->d_ptab.p, 0, (int16_t)(d->states ? 1 : 0), envelope_of(d)}, (RecMeta*)s.meta.p,
                          (uint4*)s.ev_tmp.p, (uint32_t*)s.f64_list.p, (ErrorCell*)s.d_err.p, st));
   s.n_rec = n;
   s.seed = seed;
@@ -943,7 +948,7 @@ int32_t stage2(surge_device_decoder* d, PushSlot& s, bool wait) {
       uint8_t ev[16];
       std::vector<uint8_t> value((size_t)m.val_len + 1);
       PCHK(hipMemcpy(value.data(), dby + m.val_off, (size_t)m.val_len, hipMemcpyDeviceToHost));  // (an LZ4 section exists decompressed on the device only)
-      if (surge_event_json_decode(&d->h_tmpl, value.data(), m.val_len, ev) != 0)  // (the device accepted the number's spelling and its length: cannot happen)
+      if (surge_event_json_decode(&d->h_tmpl, value.data(), m.val_len, ev) != 0)  // (the whole value and the template with its envelope; the device compared the id, accepted the number's spelling and its length: cannot happen)
         return poison(dfail(d, SURGE_E_CORRUPT, "record at offset " + std::to_string(m.offset) + ": " + surge_event_json_last_error()));
       PCHK(hipMemcpy((uint8_t*)d->r_ev.p + (size_t)(d->n_records + pos) * 16, ev, 16, hipMemcpyHostToDevice));
     }

@@ -28,6 +28,8 @@ enum : uint32_t {
   RS_F64_HOST = 8,      // a Double the fast parser cannot decide: the host re-parses this value exactly
   RS_COLLISION = 9,     // two different keys with the same 64-bit hash
   RS_EMPTY_VALUE = 10,  // state mode: an empty, non-null value under a key (writeState never writes one; the loader reads empty as a tombstone)
+  RS_ENVELOPE = 11,     // enveloped events (JsonCtx::envelope): the value is not `[aggregateId] [payload]` and nothing else (sp_envelope_spans, state_parse.h)
+  RS_KEY_MISMATCH = 12, // ... its aggregateId is not the aggregate id of the record's key
 };
 
 struct RecMeta {
@@ -165,7 +167,9 @@ struct JsonCtx {  // what the value decoder needs besides the value
   const EvjDevice* tmpl;  // nullptr: 16-byte fixed events
   const surge::F64ParseTable* ptab;
   int32_t dbg = 0;  // SURGE_DBG_DECODE (timing experiments only, results are NOT the topic's): 1 = sections are staged, nothing else; 2 = staged and chained, no record decoded
-  int32_t states = 0;  // state mode (surge_device_decoder_create_states): the id is the whole key, a null value is a tombstone, no value is decoded
+  int16_t states = 0;  // state mode (surge_device_decoder_create_states): the id is the whole key, a null value is a tombstone, no value is decoded
+  int16_t envelope = 0;  // SURGE_EVJ_ENVELOPE_* of the event template: what lies around the JSON text.  (Two halves of what was one int32: the
+                         // struct is a kernel argument, and one that grows moves every argument behind it in section_kernel's instructions.)
 #ifdef SURGE_EXPERIMENTS
   unsigned long long* ticks = nullptr;  // per workgroup: wall clock (10 ns) at start, after staging, after the chain, at the end
 #endif

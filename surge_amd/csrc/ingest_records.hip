@@ -2,11 +2,15 @@
 // (key span, value span, offset; 64-bit hash of the key up to ':') and their values decoded (16-byte events as they are, or
 // the reference's play-json text through the event template, surge_amd/csrc/event_decode.cpp's rules).  In state mode
 // (JsonCtx::states, the state topic) the id is the whole key, a null value is a delivered tombstone and no value is decoded: the
-// value spans stay in RecMeta for stage 2's gather.  Nothing here reads or writes the key table.
+// value spans stay in RecMeta for stage 2's gather.  Enveloped events (JsonCtx::envelope: a multilanguage application's events
+// topic) carry the JSON text inside the protobuf message Event{aggregateId, payload}: the envelope is read with state_parse.h's
+// reader, its id compared with the record's aggregate id, the payload decoded as a bare value.  Nothing here reads or writes
+// the key table.
 #include <cstdio>
 #include <cstdlib>
 
 #include "ingest_device.h"
+#include "state_parse.h"
 
 namespace surge {
 namespace ingest {
@@ -288,9 +292,30 @@ __device__ __forceinline__ uint32_t decode_value(const JsonCtx& jc, P vp, int va
   return RS_OK;
 }
 
+// An enveloped record value (JsonCtx::envelope == SURGE_EVJ_ENVELOPE_PROTOBUF_EVENT) -> event16 + status: the grammar first
+// (sp_envelope_spans, state_parse.h: the text the host and the state kernel compile), then field 1 against the record's aggregate
+// id [key, key + key_len) — the key already cut at its ':' — then the payload through decode_json_event as a bare value (an absent
+// or empty payload is RS_JSON: no object).  The reader is byte-wise and bounded by the value's length: a value that ends inside
+// a varint or a field never reads its neighbour.  The ids are compared four bytes at a time (load4 reads up to 7 bytes past its
+// pointer, masked here: the staged bytes end 16 bytes behind their last byte) — byte by byte, two dependent loads and a branch
+// per byte of a 13-byte id were most of what the envelope cost.
+template <typename P, typename PK>
+__device__ __forceinline__ uint32_t decode_enveloped_value(const JsonCtx& jc, P vp, int val_len, PK key, int key_len, uint4* e) {
+  int64_t id_off = 0, id_len = 0, pay_off = 0, pay_len = 0;
+  if (surge::sp_envelope_spans(vp, (int64_t)val_len, &id_off, &id_len, &pay_off, &pay_len) != SURGE_STATE_DECODE_OK) return RS_ENVELOPE;
+  if (id_len != (int64_t)key_len) return RS_KEY_MISMATCH;
+  const P id = vp + id_off;
+  for (int b = 0; b < key_len; b += 4) {
+    const int left = key_len - b;
+    const uint32_t keep = left >= 4 ? 0xffffffffu : ((1u << (8 * left)) - 1u);
+    if (((load4(id + b) ^ load4(key + b)) & keep) != 0u) return RS_KEY_MISMATCH;
+  }
+  return decode_json_event(jc.tmpl, jc.ptab, vp + pay_off, (int)pay_len, e);
+}
+
 // One record body [body, end) of a section that starts at `base` (absolute offset sec_off in the staged bytes); `valid` =
-// this lane has a record.
-template <typename P>
+// this lane has a record.  kEnvelope: the values are enveloped events (an instantiation of its own, see section_kernel).
+template <bool kEnvelope, typename P>
 __device__ __forceinline__ void decode_record(P base, int64_t sec_off, int64_t base_offset, bool valid, int32_t body, int32_t end, int64_t gi, uint64_t seed,
                                               const JsonCtx& jc, RecMeta* __restrict__ meta, uint4* __restrict__ ev_tmp,
                                               uint32_t* __restrict__ f64_host_list, ErrorCell* err) {
@@ -299,6 +324,7 @@ __device__ __forceinline__ void decode_record(P base, int64_t sec_off, int64_t b
   uint4 e = make_uint4(0, 0, 0, 0);
   bool has_value = false;
   P val = base;
+  P id = base;  // (kEnvelope) the aggregate id: the key up to ':'
   int vlen32 = 0;
   if (valid && body >= 0) {
     ReaderT<P> q{base + body, base + end, true};
@@ -336,13 +362,16 @@ __device__ __forceinline__ void decode_record(P base, int64_t sec_off, int64_t b
         m.val_off = sec_off + (val - base);
         m.val_len = (int32_t)vlen;
         m.hash = hash_key_end(hk, n, seed);
+        if constexpr (kEnvelope) id = key;
         has_value = true;
         vlen32 = (int32_t)vlen;
       }
     }
   }
   if (has_value) {
-    uint32_t st = decode_value(jc, val, vlen32, &e);
+    uint32_t st;
+    if constexpr (kEnvelope) st = decode_enveloped_value(jc, val, vlen32, id, (int)m.key_len, &e);
+    else st = decode_value(jc, val, vlen32, &e);
     if (st == RS_F64_HOST) {
       f64_host_list[atomicAdd(&err->n_f64_host, 1u)] = (uint32_t)gi;
       st = RS_OK;
@@ -417,8 +446,10 @@ constexpr int kSecRecs = 256;  // records chained per round (LDS: two int32 per 
 // record's start hold its whole length varint unless the record is 256 KiB or longer) and a dozen 32-bit instructions.  The
 // first version went through ReaderT's general varlong: two byte loads, 64-bit pointer arithmetic and a loop the compiler
 // could not drop — 0.19 of section_kernel's 0.55 ms per 10^6 records, measured with the decode switched off.)
+// (forced inline: the compiler inlined it into every instantiation of section_kernel while there were eight; left to its cost
+// model with twelve it calls it, and pos / bad then live in scratch memory)
 template <typename P>
-__device__ bool chain_records(P base, int32_t len, int32_t* pos, int32_t cnt, int32_t* rec_body, int32_t* rec_end, int32_t* bad) {
+__device__ __forceinline__ bool chain_records(P base, int32_t len, int32_t* pos, int32_t cnt, int32_t* rec_body, int32_t* rec_end, int32_t* bad) {
   int32_t at = *pos;
   for (int32_t i = 0; i < cnt; ++i) {
     const int32_t room = len - at;
@@ -593,7 +624,9 @@ __device__ bool chain_records_parallel(lds_ptr_t base, int32_t len, int32_t cnt,
 // branch is taken where it is cheapest, at the launch: as a branch INSIDE the one kernel it cost the events path its register
 // budget (80 VGPRs hold the kernel only because ~170 scalar registers already live in spare vector lanes; a second record path
 // pushed those into scratch memory).
-template <int kSecThreads, bool kStates>
+// kEnvelope: the same again for enveloped event values (JsonCtx::envelope, launch-uniform too): the envelope reader in front of
+// the JSON walk is an instantiation of its own, and the two above keep their instructions and registers.
+template <int kSecThreads, bool kStates, bool kEnvelope>
 __global__ void __launch_bounds__(kSecThreads) __attribute__((amdgpu_waves_per_eu(kSecThreads == 256 ? 5 : 6)))  // (four waves at 80 VGPRs spill)
 section_kernel(const uint8_t* __restrict__ bytes, const Section* __restrict__ sections, int64_t n_sections, int64_t lo_excl, int64_t cap, int32_t take_rest,
                uint64_t seed, JsonCtx jc, RecMeta* __restrict__ meta, uint4* __restrict__ ev_tmp, uint32_t* __restrict__ f64_host_list, ErrorCell* err) {
@@ -631,7 +664,7 @@ section_kernel(const uint8_t* __restrict__ bytes, const Section* __restrict__ se
   if (len >= (1ll << 31)) {  // a section of 2 GiB: nothing writes one (a batch's length is an int32)
     for (int32_t i0 = 0; i0 < sec.n_records; i0 += kSecThreads) {
       if constexpr (kStates) decode_state_record(bytes, 0, 0, i0 + (int32_t)threadIdx.x < sec.n_records, -1, -1, sec.rec_first + i0 + threadIdx.x, seed, meta, err);
-      else decode_record(bytes, 0, 0, i0 + (int32_t)threadIdx.x < sec.n_records, -1, -1, sec.rec_first + i0 + threadIdx.x, seed, jc, meta, ev_tmp, f64_host_list, err);
+      else decode_record<kEnvelope>(bytes, 0, 0, i0 + (int32_t)threadIdx.x < sec.n_records, -1, -1, sec.rec_first + i0 + threadIdx.x, seed, jc, meta, ev_tmp, f64_host_list, err);
     }
     return;
   }
@@ -673,9 +706,9 @@ section_kernel(const uint8_t* __restrict__ bytes, const Section* __restrict__ se
         if (staged) decode_state_record(lbase, sec.byte_off, sec.base_offset, valid, body, end, sec.rec_first + r0 + i, seed, meta, err);
         else decode_state_record(gbase, sec.byte_off, sec.base_offset, valid, body, end, sec.rec_first + r0 + i, seed, meta, err);
       } else if (staged) {
-        decode_record(lbase, sec.byte_off, sec.base_offset, valid, body, end, sec.rec_first + r0 + i, seed, jc, meta, ev_tmp, f64_host_list, err);
+        decode_record<kEnvelope>(lbase, sec.byte_off, sec.base_offset, valid, body, end, sec.rec_first + r0 + i, seed, jc, meta, ev_tmp, f64_host_list, err);
       } else {
-        decode_record(gbase, sec.byte_off, sec.base_offset, valid, body, end, sec.rec_first + r0 + i, seed, jc, meta, ev_tmp, f64_host_list, err);
+        decode_record<kEnvelope>(gbase, sec.byte_off, sec.base_offset, valid, body, end, sec.rec_first + r0 + i, seed, jc, meta, ev_tmp, f64_host_list, err);
       }
     }
     __syncthreads();
@@ -684,7 +717,9 @@ section_kernel(const uint8_t* __restrict__ bytes, const Section* __restrict__ se
 }
 
 // records that arrive already framed (a JVM's ConsumerRecords: key bytes, value bytes, offset per record): the bytes buffer
-// holds the keys first, the values from `val_base` on
+// holds the keys first, the values from `val_base` on.  kEnvelope: enveloped event values — chosen at the launch like
+// section_kernel's (as a branch inside the one kernel the envelope reader cost the bare path two vector registers)
+template <bool kEnvelope>
 __global__ void __launch_bounds__(256) records_kernel(const uint8_t* __restrict__ bytes, const int64_t* __restrict__ key_off, const int64_t* __restrict__ val_off,
                                                       const int64_t* __restrict__ offsets, int64_t val_base, int64_t n_rec, uint64_t seed, JsonCtx jc,
                                                       RecMeta* __restrict__ meta, uint4* __restrict__ ev_tmp, uint32_t* __restrict__ f64_host_list, ErrorCell* err) {
@@ -715,7 +750,9 @@ __global__ void __launch_bounds__(256) records_kernel(const uint8_t* __restrict_
   }
   if (!valid) return;
   if (has_value) {
-    uint32_t st = decode_value(jc, bytes + m.val_off, m.val_len, &e);
+    uint32_t st;
+    if constexpr (kEnvelope) st = decode_enveloped_value(jc, bytes + m.val_off, m.val_len, bytes + m.key_off, m.key_len, &e);
+    else st = decode_value(jc, bytes + m.val_off, m.val_len, &e);
     if (st == RS_F64_HOST) {
       f64_host_list[atomicAdd(&err->n_f64_host, 1u)] = (uint32_t)i;
       st = RS_OK;
@@ -754,17 +791,19 @@ hipError_t launch_sections(const uint8_t* bytes, const Section* sections, int64_
     const size_t lds = (size_t)((caps[c] + 47) & ~15ll) + 2 * (size_t)kSecRecs * 4;
     const int64_t lo_excl = c == 0 ? -1 : caps[c - 1];
     const int32_t rest = c == n_caps - 1 ? 1 : 0;
-#define SURGE_SECTION_LAUNCH(T, S)                                                                                                                  \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(section_kernel<T, S>), dim3((unsigned)n_sections), dim3(T), lds, st, bytes, sections, n_sections, lo_excl, caps[c], rest, seed, jc, meta, \
+#define SURGE_SECTION_LAUNCH(T, S, E)                                                                                                                \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(section_kernel<T, S, E>), dim3((unsigned)n_sections), dim3(T), lds, st, bytes, sections, n_sections, lo_excl, caps[c], rest, seed, jc, meta, \
                      ev_tmp, f64_host_list, err)
-#define SURGE_SECTION_WIDTH(S)                     \
-  do {                                             \
-    if (max_recs <= 64) SURGE_SECTION_LAUNCH(64, S);        \
-    else if (max_recs <= 128) SURGE_SECTION_LAUNCH(128, S); \
-    else if (max_recs <= 192) SURGE_SECTION_LAUNCH(192, S); \
-    else SURGE_SECTION_LAUNCH(256, S);                      \
+#define SURGE_SECTION_WIDTH(S, E)                     \
+  do {                                                \
+    if (max_recs <= 64) SURGE_SECTION_LAUNCH(64, S, E);        \
+    else if (max_recs <= 128) SURGE_SECTION_LAUNCH(128, S, E); \
+    else if (max_recs <= 192) SURGE_SECTION_LAUNCH(192, S, E); \
+    else SURGE_SECTION_LAUNCH(256, S, E);                      \
   } while (0)
-    if (jc.states) SURGE_SECTION_WIDTH(true); else SURGE_SECTION_WIDTH(false);
+    if (jc.states) SURGE_SECTION_WIDTH(true, false);
+    else if (jc.envelope && jc.tmpl) SURGE_SECTION_WIDTH(false, true);  // enveloped event values: an instantiation of their own
+    else SURGE_SECTION_WIDTH(false, false);
 #undef SURGE_SECTION_WIDTH
 #undef SURGE_SECTION_LAUNCH
 #ifdef SURGE_EXPERIMENTS
@@ -793,7 +832,8 @@ hipError_t launch_sections(const uint8_t* bytes, const Section* sections, int64_
 
 hipError_t launch_records(const uint8_t* bytes, const int64_t* key_off, const int64_t* val_off, const int64_t* offsets, int64_t val_base, int64_t n_rec,
                           uint64_t seed, JsonCtx jc, RecMeta* meta, uint4* ev_tmp, uint32_t* f64_host_list, ErrorCell* err, hipStream_t st) {
-  hipLaunchKernelGGL(records_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, bytes, key_off, val_off, offsets, val_base, n_rec, seed, jc, meta,
+  const auto kernel = (jc.envelope && jc.tmpl && !jc.states) ? records_kernel<true> : records_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, bytes, key_off, val_off, offsets, val_base, n_rec, seed, jc, meta,
                      ev_tmp, f64_host_list, err);
   return hipGetLastError();
 }

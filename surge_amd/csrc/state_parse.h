@@ -249,7 +249,10 @@ SURGE_HD int state_parse_json(const surge_json_template& t, const uint8_t* v, in
 
 // A length varint at v[*pos]: 1 - 5 bytes, value <= 2^31 - 1; an over-long (non-minimal) spelling is accepted, as the
 // protobuf runtime accepts it.  Never reads at or beyond v + len.
-SURGE_HD int sp_length_varint(const uint8_t* v, int64_t len, int64_t* pos, int64_t* value) {
+// (P: the kind of pointer the bytes are read through — const uint8_t* on the host and in the state decoder; the event kernels
+// of ingest_records.hip also read a staged section through an LDS pointer.  One text for all of them.)
+template <typename P>
+SURGE_HD int sp_length_varint(P v, int64_t len, int64_t* pos, int64_t* value) {
   uint64_t x = 0;
   int64_t i = *pos;
   for (int b = 0; b < 5; ++b) {
@@ -266,18 +269,21 @@ SURGE_HD int sp_length_varint(const uint8_t* v, int64_t len, int64_t* pos, int64
   return SURGE_STATE_DECODE_ENVELOPE;  // the 5th byte still continues
 }
 
-// The envelope alone: where the payload lies (*pay_off / *pay_len; an absent field 2 is the empty payload at the value's
-// end), and, with key_len >= 0, the raw bytes of field 1 against the id byte for byte (no unescaping: the encoder writes the
-// raw UTF-8 id; an absent field 1 is the empty id).  Grammar errors come before the comparison.
-SURGE_HD int sp_envelope(const uint8_t* v, int64_t len, const uint8_t* key, int64_t key_len, int64_t* pay_off, int64_t* pay_len) {
-  int64_t i = 0, id_off = 0, id_len = 0, n = 0;
+// The envelope's grammar alone: where field 1 lies (*id_off / *id_len; absent = the empty id) and where the payload lies
+// (*pay_off / *pay_len; an absent field 2 is the empty payload at the value's end).  The same message shape holds the
+// events topic's values: Event { string aggregateId = 1; bytes payload = 2; } (multilanguage-protocol.proto:17-20).
+template <typename P>
+SURGE_HD int sp_envelope_spans(P v, int64_t len, int64_t* id_off, int64_t* id_len, int64_t* pay_off, int64_t* pay_len) {
+  int64_t i = 0, n = 0;
+  *id_off = 0;
+  *id_len = 0;
   if (i < len && v[i] == 0x0Au) {
     ++i;
     const int rc = sp_length_varint(v, len, &i, &n);
     if (rc != SURGE_STATE_DECODE_OK) return rc;
     if (n > len - i) return SURGE_STATE_DECODE_ENVELOPE;
-    id_off = i;
-    id_len = n;
+    *id_off = i;
+    *id_len = n;
     i += n;
   }
   *pay_off = i;
@@ -292,6 +298,17 @@ SURGE_HD int sp_envelope(const uint8_t* v, int64_t len, const uint8_t* key, int6
     i += n;
   }
   if (i != len) return SURGE_STATE_DECODE_ENVELOPE;  // another tag, a repeated field, field 1 behind field 2, stray bytes
+  return SURGE_STATE_DECODE_OK;
+}
+
+// The envelope with its id: sp_envelope_spans, then, with key_len >= 0, the raw bytes of field 1 against the id byte for
+// byte (no unescaping: the encoder writes the raw UTF-8 id; an absent field 1 is the empty id).  Grammar errors come
+// before the comparison.  (PK: the key's pointer kind.)
+template <typename P, typename PK>
+SURGE_HD int sp_envelope(P v, int64_t len, PK key, int64_t key_len, int64_t* pay_off, int64_t* pay_len) {
+  int64_t id_off = 0, id_len = 0;
+  const int rc = sp_envelope_spans(v, len, &id_off, &id_len, pay_off, pay_len);
+  if (rc != SURGE_STATE_DECODE_OK) return rc;
   if (key_len >= 0) {
     if (id_len != key_len) return SURGE_STATE_DECODE_KEY_MISMATCH;
     for (int64_t b = 0; b < id_len; ++b)

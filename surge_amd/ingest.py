@@ -35,6 +35,7 @@ assert RECORD_DTYPE.itemsize == 40
 
 EVJ_NAME, EVJ_MAX_TYPES = 64, 16
 ARG_NONE, ARG_I32, ARG_F64 = 0, 1, 2
+EVJ_ENVELOPES = {"none": 0, "protobuf_event": 1}  # SURGE_EVJ_ENVELOPE_*
 
 
 class _CEventJsonType(ctypes.Structure):
@@ -43,7 +44,7 @@ class _CEventJsonType(ctypes.Structure):
 
 
 class CEventJsonTemplate(ctypes.Structure):
-    _fields_ = [("n_types", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("discriminator", ctypes.c_char * EVJ_NAME),
+    _fields_ = [("n_types", ctypes.c_uint32), ("envelope", ctypes.c_uint32), ("discriminator", ctypes.c_char * EVJ_NAME),
                 ("types", _CEventJsonType * EVJ_MAX_TYPES)]
 
 
@@ -51,14 +52,21 @@ class EventJsonTemplate:
     """``surge_event_json_template``: how a model's JSON event text maps onto the 16-byte fixed event.
 
     ``types``: ``(discriminator value, event type, seq field or "", arg field or "", ARG_*)`` per event class;
-    ``discriminator``: the field naming the class (play-json's sealed-family ``"_type"``), ``""`` for single-class topics."""
+    ``discriminator``: the field naming the class (play-json's sealed-family ``"_type"``), ``""`` for single-class topics.
+    ``envelope``: what lies around the JSON text in a record's value — ``"none"``, or ``"protobuf_event"`` for the events topic
+    of a multilanguage (SDK) application, whose values are the protobuf message ``Event{aggregateId, payload}`` with the text
+    as payload (``GenericSurgeCommandBusinessLogic.scala:30-34``).  It travels with the template to every decoder: the host
+    drain, ``DeviceDecoder`` and the store's recoveries."""
 
-    def __init__(self, discriminator: str, types):
-        self.discriminator, self.types = discriminator, list(types)
+    def __init__(self, discriminator: str, types, envelope: str = "none"):
+        if envelope not in EVJ_ENVELOPES:
+            raise ValueError(f"envelope must be one of {sorted(EVJ_ENVELOPES)}, not {envelope!r}")
+        self.discriminator, self.types, self.envelope = discriminator, list(types), envelope
 
     def to_c(self) -> CEventJsonTemplate:
         t = CEventJsonTemplate()
         t.n_types = len(self.types)
+        t.envelope = EVJ_ENVELOPES[self.envelope]
         t.discriminator = self.discriminator.encode()
         for i, (name, ev_type, seq_field, arg_field, arg_kind) in enumerate(self.types):
             e = t.types[i]
@@ -67,16 +75,24 @@ class EventJsonTemplate:
         return t
 
     def decode(self, value: bytes) -> np.ndarray:
-        """One record value -> one ``EVENT_DTYPE`` record (``surge_event_json_decode``)."""
+        """One record value -> one ``EVENT_DTYPE`` record (``surge_event_json_decode``; an enveloped template reads the
+        envelope and compares its id with nothing)."""
+        return self.decode_keyed(None, value)
+
+    def decode_keyed(self, aggregate_id: Optional[bytes], value: bytes) -> np.ndarray:
+        """``surge_event_json_decode_keyed``: like ``decode``, and with an enveloped template the envelope's ``aggregateId`` must
+        equal ``aggregate_id`` byte for byte — the record's key already cut at its first ``:``.  ``None``: no comparison."""
         lib = _native.load()
         out = np.zeros(1, dtype=EVENT_DTYPE)
         c = self.to_c()
         if lib.surge_event_json_validate(ctypes.byref(c)) != 0:
             raise IngestError(-1, (lib.surge_event_json_last_error() or b"").decode())
         buf = (ctypes.c_uint8 * max(len(value), 1)).from_buffer_copy(value or b"\0")
-        rc = lib.surge_event_json_decode(ctypes.byref(c), buf, len(value), out.ctypes.data_as(ctypes.c_void_p))
+        key = None if aggregate_id is None else bytes(aggregate_id)
+        kbuf = None if key is None else (ctypes.c_uint8 * max(len(key), 1)).from_buffer_copy(key or b"\0")
+        rc = lib.surge_event_json_decode_keyed(ctypes.byref(c), kbuf, -1 if key is None else len(key), buf, len(value), out.ctypes.data_as(ctypes.c_void_p))
         if rc != 0:
-            raise IngestError(rc, (lib.surge_event_json_last_error() or b"").decode())
+            raise IngestError(rc, (lib.surge_event_json_last_error() or b"").decode("utf-8", "replace"))  # (the message may quote the value's own bytes)
         return out[0]
 
 

@@ -78,7 +78,9 @@ class GpuReplayStateStore:
         CRC, transactions, LZ4), the GPU parses the records, interns the aggregate ids, decodes the values and groups
         them (``surge_device_decoder`` + the K3 group-by) — no per-record work in any host language.  A model without a
         template falls back to the host decoder and the plugin's ``SurgeEventReadFormatting.read_event`` per record.
-        Returns the ingest counters."""
+        A template that names an envelope (``EventJsonTemplate(envelope="protobuf_event")``: a multilanguage application's
+        topic) decides by itself: its values are never looked at to tell the kind — an enveloped value can be exactly 16
+        bytes long.  Returns the ingest counters."""
         from .core import SerializedMessage
         from .ingest import EventsTopicIngest, IngestError
         from .schema import EVENT_DTYPE
@@ -90,16 +92,20 @@ class GpuReplayStateStore:
             pass  # JSON values and a model without a template: the host decoder + the plugin's reader below
         with EventsTopicIngest() as g:
             g.feed(record_batches)
-            recs = None
-            try:
-                # GPU-ready topic (every value IS the 16-byte fixed event): one vectorised drain, no per-record Python
-                agg_idx, events, _ = g.drain_fixed16()
-            except IngestError:
-                if template is not None:
-                    # the plugin's JSON event text, decoded in the library through the model's template
-                    agg_idx, events, _ = g.drain_json(template)
-                else:
-                    recs = g.drain_records()  # no template: every value through the plugin's own event reader
+            recs = fixed = None
+            if not _enveloped(template):  # (an enveloped value may be 16 bytes long: never taken for a fixed event)
+                try:
+                    # GPU-ready topic (every value IS the 16-byte fixed event): one vectorised drain, no per-record Python
+                    fixed = g.drain_fixed16()
+                except IngestError:
+                    pass
+            if fixed is not None:
+                agg_idx, events, _ = fixed
+            elif template is not None:
+                # the plugin's JSON event text, decoded in the library through the model's template
+                agg_idx, events, _ = g.drain_json(template)
+            else:
+                recs = g.drain_records()  # no template: every value through the plugin's own event reader
             keys = g.key_table()
             counters = g.counters()
         if recs is not None:
@@ -169,7 +175,7 @@ class GpuReplayStateStore:
             if not parts and d is None:
                 return False  # (nothing pushed yet: nothing in flight that the framer could overtake)
             if d is None:
-                kind = None
+                kind = "json" if _enveloped(template) else None  # an envelope is the template's word: the values are not sniffed
                 for sec, arena in parts:
                     kind = kind or _sniff_value_kind(sec, arena)  # "fixed16", "json" or None (no deliverable record)
                 if kind == "json" and template is None:
@@ -583,6 +589,11 @@ class GpuReplayPersistencePlugin:
 
 class _NotDeviceDecodable(ValueError):
     """The topic's values are not something the device decoder reads (JSON text, and the model has no template)."""
+
+
+def _enveloped(template) -> bool:
+    """The model's event template names an envelope around its JSON text: such a topic always gets the template decoder."""
+    return template is not None and getattr(template, "envelope", "none") != "none"
 
 
 def _sniff_value_kind(sections, arena_address: int):
