@@ -1,7 +1,8 @@
 // ingest_device.h — what the translation units of the device decoder share.  Internal, like replay_internal.h: not part of
 // the C ABI.  Each stage is a unit of its own that knows the plain structs below and nothing of the decoder around it
-// (ingest_decoder.hip, the host object): ingest_crc.hip, ingest_lz4.hip, ingest_records.hip, ingest_intern.hip.  Their
-// launch_* functions enqueue on the stream they are given and return what the runtime said; none of them waits for the device.
+// (the host object: ingest_decoder.hip and its units ingest_stage1.hip, ingest_stage2.hip, ingest_handover.hip, which share
+// ingest_decoder_internal.h): ingest_crc.hip, ingest_lz4.hip, ingest_records.hip, ingest_intern.hip.  Their launch_* functions
+// enqueue on the stream they are given and return what the runtime said; none of them waits for the device.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -30,6 +31,7 @@ enum : uint32_t {
   RS_EMPTY_VALUE = 10,  // state mode: an empty, non-null value under a key (writeState never writes one; the loader reads empty as a tombstone)
   RS_ENVELOPE = 11,     // enveloped events (JsonCtx::envelope): the value is not `[aggregateId] [payload]` and nothing else (sp_envelope_spans, state_parse.h)
   RS_KEY_MISMATCH = 12, // ... its aggregateId is not the aggregate id of the record's key
+  RS_COUNT,             // (how many there are: the host's text per status is checked against it, ingest_stage2.hip)
 };
 
 struct RecMeta {

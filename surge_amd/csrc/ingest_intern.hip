@@ -9,7 +9,7 @@
 //   finalize   one thread per delivered record: aggregate index from its slot, event and offset to the result arrays
 //   (state mode) value scan + value gather: the delivered records' value bytes out of the push's bytes into one buffer
 // The control flow around these — the retry after a collision, what is checked before anything is committed, the commit order —
-// is stage 2 of the decoder (ingest_decoder.hip); this unit launches what it is told to.
+// is stage 2 of the decoder (ingest_stage2.hip); this unit launches what it is told to.
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
