@@ -168,6 +168,7 @@ int32_t surge_ingest_drain_json(surge_ingest* g, int64_t max, const surge_event_
                                            the CRC register after the covered header bytes}, little-endian u32 each                  */
 #define SURGE_SECTION_CRC_WIRE    0x200 /* ... (in-place framing) the 44 bytes in front of byte_off are the batch's own crc field (big-endian)
                                            and the 40 header bytes it covers, as received: the device runs the whole CRC             */
+#define SURGE_SECTION_FLOORED     0x400 /* ... the section straddles the framer's start offset (below): records of it lie below the start     */
 typedef struct surge_batch_section {
   int64_t byte_off;    /* the batch's records section inside the arena (surge_ingest_arena)            */
   int64_t byte_len;
@@ -185,6 +186,43 @@ typedef struct surge_batch_section {
  * time; what the other threads touch is only the arena memory.  Batches still queued at a feed (open transactions) move to
  * the new arena with it. */
 int32_t surge_ingest_drain_sections(surge_ingest* g, int64_t max_sections, surge_batch_section* out, int64_t* n_out);
+
+/* ---- start offsets and positions: resuming inside a partition ------------------------------------------------------------
+ * A consumer that seeks to offset o (SurgeStateStoreConsumer.scala:33-46,57-76: the restore consumer of the reference starts
+ * from the offsets committed with its store) is sent the whole batch that contains o and drops the records in front of o,
+ * record by record, behind the decompression.  surge_ingest_set_start_offset(g, o) — before the first feed, SURGE_E_STATE
+ * afterwards; o <= 0: no start — makes the framer do the same: a record is delivered only if its offset is >= o.
+ *   - Transactions are read exactly as without a start: batches below it open and close transactions, markers are read, a
+ *     transaction that straddles the start commits or aborts as a whole.
+ *   - The rule applies where a batch would be handed out.  A batch whose last offset (baseOffset + lastOffsetDelta) lies below
+ *     the start is discarded there (surge_ingest_below_start counts it).  surge_ingest_drain, _drain_fixed16 and _drain_json
+ *     pass over the records below the start: they count as neither decoded nor delivered, their keys are not interned, their
+ *     values are never decoded (a value that would not decode does not fail the drain); a flush record below the start is
+ *     dropped as one of them.  surge_ingest_drain_sections hands the ONE batch that straddles the start out with
+ *     SURGE_SECTION_FLOORED in `codec` — its records below the start are dropped where records are parsed, on the device
+ *     (surge_device_decoder_push_parts_floored_async) — and names it in the floors list.
+ *   - Once a batch that reaches the start has been handed out the start is inert: at most one floored section per partition
+ *     over the framer's life.
+ * The floors list travels beside the sections: take_floors fills it for the sections the last surge_ingest_drain_sections /
+ * surge_ingest_group_feed handed out (valid until the next one; SURGE_E_INVALID with the count in *n_out when `max` is too
+ * small).  `section` indexes that call's section array; `part` is the partition the floor belongs to (0 from a single handle).
+ * surge_ingest_position: the offset a consumer would resume from — behind the last batch the framer has decided (delivered,
+ * aborted, control or discarded), in front of an open transaction and of anything still queued for a drain, never below the
+ * start: what a publisher commits with a snapshot.  A fresh framer started there delivers exactly what this one has not. */
+typedef struct surge_section_floor {
+  int32_t part, reserved;
+  int64_t section;
+  int64_t first_offset;
+} surge_section_floor;
+int32_t surge_ingest_set_start_offset(surge_ingest* g, int64_t first_offset);
+int32_t surge_ingest_take_floors(surge_ingest* g, int64_t max, surge_section_floor* out, int64_t* n_out);
+int64_t surge_ingest_position(const surge_ingest* g);
+/* [0] batches discarded below the start, [1] records dropped below it (host drains: one by one; FRAMES: the discarded batches'
+ * recordCount — what the device drops of the floored section is in surge_device_decoder_below_floor).  In FRAMES mode the
+ * framer cannot see into the floored section: its whole recordCount stays in surge_ingest_counters' "records decoded" and
+ * "records delivered" (handed to the device); subtract surge_device_decoder_below_floor for the records that were decoded and
+ * delivered in the issue's sense (surge_amd/store.py does for its tail_* counts). */
+int32_t surge_ingest_below_start(const surge_ingest* g, int64_t out[2]);
 
 /* A consumer that is assigned several partitions gets, per fetch response, the next bytes of each of them; transactions,
  * last stable offsets and cut batches are per partition, so each partition needs a framer of its own.  A group owns n
@@ -230,6 +268,11 @@ int32_t surge_ingest_group_cpu_seconds(const surge_ingest_group* g, double out[2
 int32_t surge_ingest_group_slab_bytes(const surge_ingest_group* g, int64_t* bytes_out, int32_t* custom_allocator_out);
 int64_t surge_ingest_group_queued_sections(const surge_ingest_group* g); /* batches the partitions hold from earlier feeds (upper bound of what the next feed delivers beyond its own) */
 int32_t surge_ingest_group_counters(const surge_ingest_group* g, int64_t out[8]); /* surge_ingest_counters, summed */
+/* The calls of "start offsets and positions" above for a group: one entry per partition (a value <= 0: that partition has no start) */
+int32_t surge_ingest_group_set_start_offsets(surge_ingest_group* g, const int64_t* first_offset);
+int32_t surge_ingest_group_take_floors(surge_ingest_group* g, int64_t max, surge_section_floor* out, int64_t* n_out);
+int32_t surge_ingest_group_positions(const surge_ingest_group* g, int64_t* out);
+int32_t surge_ingest_group_below_start(const surge_ingest_group* g, int64_t out[2]); /* surge_ingest_below_start, summed */
 int32_t surge_ingest_group_set_allocator(surge_ingest_group* g, void* (*alloc)(size_t), void (*release)(void*));
 int32_t surge_ingest_group_use_pinned_slabs(surge_ingest_group* g); /* page-locked slabs (SURGE_E_DEVICE without a HIP runtime) */
 
@@ -266,6 +309,22 @@ int32_t surge_device_decoder_create(int32_t device_id, void* hip_stream, const s
  * The result is read with surge_device_decoder_state_result and handed over with surge_device_decoder_load_states;
  * surge_device_decoder_result, surge_replay_append_decoded[_async] and surge_replay_stage_decoded return SURGE_E_STATE. */
 int32_t surge_device_decoder_create_states(int32_t device_id, void* hip_stream, surge_device_decoder** out);
+/* A state decoder goes on as the EVENTS decoder of the same aggregates: fold(prev snapshot, new events) on one key table.  The
+ * restore consumer of the reference reads the state topic and then serves (SurgeStateStoreConsumer.scala:33-46,57-76); a store that
+ * resumes from a snapshot reads the events behind it as well, and the dense ids the state decoder interned are the resident
+ * state's row numbers — the events' ids have to be the same numbers.  Both modes hash an id's bytes alike, so the table is good
+ * for both.  Allowed on a state decoder with no push pending and every delivered record loaded or cleared (SURGE_E_STATE
+ * otherwise, and on an events decoder: the switch is one-way); a template that fails surge_event_json_validate: SURGE_E_INVALID,
+ * nothing changed.  The key table — slots, arena, offsets, hashes, seed, key count, reserve — stays where it is, nothing is
+ * copied; the value buffers of state mode are released; the template is set up as surge_device_decoder_create does (NULL:
+ * 16-byte fixed events; tmpl->envelope honoured).  From then on the decoder is an events decoder in every respect: ids are the
+ * key up to the first ':', new ids are numbered from the key count on, state-only calls return SURGE_E_STATE,
+ * surge_replay_append_decoded[_async] and surge_replay_stage_decoded work.  The one exception: string columns kept with
+ * surge_device_decoder_keep_strings stay readable through surge_device_decoder_state_strings until clear or destroy.
+ *   - A state id that contains a colon ("a:b") stays in the table, and keeps its row, but can never be named by an event: the
+ *     event key "a:b:7" is the id "a".
+ *   - A re-seed of the hash function after the switch re-hashes the state-era keys from the arena like any others. */
+int32_t surge_device_decoder_continue_as_events(surge_device_decoder* d, const surge_event_json_template* tmpl);
 int32_t surge_device_decoder_destroy(surge_device_decoder* d);
 const char* surge_device_decoder_last_error(const surge_device_decoder* d);
 /* Decodes the sections (spans of `bytes`, a HOST buffer) and APPENDS their records to the device-resident result.  A
@@ -291,6 +350,24 @@ int32_t surge_device_decoder_push(surge_device_decoder* d, const uint8_t* bytes,
 int32_t surge_device_decoder_push_async(surge_device_decoder* d, const uint8_t* bytes, const surge_batch_section* sections, int64_t n_sections);
 int32_t surge_device_decoder_push_parts_async(surge_device_decoder* d, int32_t n_parts, const uint8_t* const* bytes,
                                               const surge_batch_section* const* sections, const int64_t* n_sections);
+/* The same with the floors of the push's sections (surge_ingest_take_floors / surge_ingest_group_take_floors; "start offsets and
+ * positions" above): floors[i].section counts through the push's sections in push order — part p's follow part p - 1's; with one
+ * part, what every framer here fills, it is the index take_floors wrote — and `part` is not read.  A record of such a section
+ * whose offset (base_offset + its offset delta) lies below first_offset is passed over where records are parsed, right behind its
+ * offset delta: its key is not hashed or interned, its value is never looked at — a value that would not decode is not refused, a
+ * Double the device cannot decide is not handed back to the host — and it is not delivered; it counts in
+ * surge_device_decoder_below_floor, not as a flush record.  A record that is malformed fails the push on either side of the floor,
+ * as it fails the host framer's feed.  The host drains are the pin (tests/test_resume_tail_gpu.py).  Events decoders only
+ * (SURGE_E_STATE on a state decoder: the state topic is read from its beginning); push_records takes no floors — a consumer
+ * that has sought never hands over a record below its position.  n_floors == 0: exactly push_parts_async, the same kernels;
+ * a push that carries a floor launches instantiations of the record stage of its own (section_kernel's kFloor), so every other
+ * push runs the code it ran before.  push_floored: the synchronous form, as surge_device_decoder_push is push_async's. */
+int32_t surge_device_decoder_push_parts_floored_async(surge_device_decoder* d, int32_t n_parts, const uint8_t* const* bytes,
+                                                      const surge_batch_section* const* sections, const int64_t* n_sections, int64_t n_floors,
+                                                      const surge_section_floor* floors);
+int32_t surge_device_decoder_push_floored(surge_device_decoder* d, const uint8_t* bytes, const surge_batch_section* sections, int64_t n_sections, int64_t n_floors,
+                                          const surge_section_floor* floors);
+int32_t surge_device_decoder_below_floor(const surge_device_decoder* d, int64_t* n_out); /* records passed over below a floor so far */
 int32_t surge_device_decoder_push_finish(surge_device_decoder* d);
 /* push_finish without its closing wait for the device: the results are complete in the order of the decoder's stream
  * (hand them over with surge_replay_append_decoded_async, or synchronise that stream before reading them).  The one

@@ -132,6 +132,10 @@ INGEST_EXPORTS = (
     "surge_device_decoder_push_records",
     "surge_device_decoder_push_async",
     "surge_device_decoder_push_parts_async",
+    "surge_device_decoder_push_parts_floored_async",
+    "surge_device_decoder_push_floored",
+    "surge_device_decoder_below_floor",
+    "surge_device_decoder_continue_as_events",
     "surge_device_decoder_push_finish",
     "surge_device_decoder_push_finish_async",
     "surge_device_decoder_pending",
@@ -158,6 +162,14 @@ INGEST_EXPORTS = (
     "surge_ingest_key_count",
     "surge_ingest_key",
     "surge_ingest_counters",
+    "surge_ingest_set_start_offset",
+    "surge_ingest_take_floors",
+    "surge_ingest_position",
+    "surge_ingest_below_start",
+    "surge_ingest_group_set_start_offsets",
+    "surge_ingest_group_take_floors",
+    "surge_ingest_group_positions",
+    "surge_ingest_group_below_start",
     "surge_crc32c",
     "surge_crc32c_portable",
     "surge_lz4_frame_decompress",
@@ -386,6 +398,10 @@ def load() -> ctypes.CDLL:
         "surge_device_decoder_push_records": ([vp, vp, vp, vp, vp, vp, i64], i32),
         "surge_device_decoder_push_async": ([vp, vp, vp, i64], i32),
         "surge_device_decoder_push_parts_async": ([vp, i32, vp, vp, vp], i32),
+        "surge_device_decoder_push_parts_floored_async": ([vp, i32, vp, vp, vp, i64, vp], i32),
+        "surge_device_decoder_push_floored": ([vp, vp, vp, i64, i64, vp], i32),
+        "surge_device_decoder_below_floor": ([vp, ctypes.POINTER(i64)], i32),
+        "surge_device_decoder_continue_as_events": ([vp, vp], i32),
         "surge_device_decoder_push_finish": ([vp], i32),
         "surge_device_decoder_push_finish_async": ([vp], i32),
         "surge_device_decoder_pending": ([vp], i32),
@@ -413,6 +429,14 @@ def load() -> ctypes.CDLL:
         "surge_ingest_key_count": ([vp], i64),
         "surge_ingest_key": ([vp, i64, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(i64)], i32),
         "surge_ingest_counters": ([vp, ctypes.POINTER(i64 * 8)], i32),
+        "surge_ingest_set_start_offset": ([vp, i64], i32),
+        "surge_ingest_take_floors": ([vp, i64, vp, ctypes.POINTER(i64)], i32),
+        "surge_ingest_position": ([vp], i64),
+        "surge_ingest_below_start": ([vp, ctypes.POINTER(i64 * 2)], i32),
+        "surge_ingest_group_set_start_offsets": ([vp, vp], i32),
+        "surge_ingest_group_take_floors": ([vp, i64, vp, ctypes.POINTER(i64)], i32),
+        "surge_ingest_group_positions": ([vp, vp], i32),
+        "surge_ingest_group_below_start": ([vp, ctypes.POINTER(i64 * 2)], i32),
         "surge_crc32c": ([vp, i64], ctypes.c_uint32),
         "surge_crc32c_portable": ([vp, i64], ctypes.c_uint32),
         "surge_lz4_frame_decompress": ([vp, i64, vp, i64], i64),

@@ -50,6 +50,7 @@ struct Batch {
   // the header bytes} written by the framer; 44 = the batch's own crc field and the 40 header bytes it covers, as received
   // (in-place framing: the device runs the whole CRC)
   int32_t crc_prefix = 0;
+  int64_t last_offset = 0;  // baseOffset + lastOffsetDelta (compaction leaves the header's as they were written)
 };
 
 struct CrcTables {
@@ -159,6 +160,7 @@ struct Reader {
 struct BatchHeader {
   int64_t base_offset, producer_id;
   int32_t batch_len, count;  // batch_len: the bytes behind the length field (the batch spans 12 + batch_len)
+  int32_t last_offset_delta;
   uint32_t crc;
   int16_t attrs;
   uint8_t magic;
@@ -197,7 +199,8 @@ inline HeaderRead read_batch_header(const uint8_t* data, int64_t len, int64_t po
   h->crc_from = p + 21;
   h->crc_len = (int64_t)h->batch_len - 9;
   h->attrs = (int16_t)((p[21] << 8) | p[22]);
-  h->producer_id = (int64_t)be64(p + 43);  // behind lastOffsetDelta, baseTimestamp, maxTimestamp
+  h->last_offset_delta = (int32_t)be32(p + 23);
+  h->producer_id = (int64_t)be64(p + 43);  // behind baseTimestamp, maxTimestamp
   h->count = (int32_t)be32(p + 57);        // behind producerEpoch, baseSequence
   h->recs = p + 61;
   h->recs_len = (int64_t)h->batch_len - kHeaderBehindLength;
@@ -294,6 +297,16 @@ struct surge_ingest {
   std::vector<int64_t> slots;      // open-addressing index over keys (power-of-two size, -1 = empty)
   std::vector<uint8_t> scratch;
   int64_t counters[C_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // surge_ingest_set_start_offset: where a consumer that has sought into the partition begins, and how far this one has come
+  struct Start {
+    int64_t first = 0;             // records below it are not delivered (<= 0: no start)
+    bool passed = false;           // a batch that reaches the start has been handed out: the floor is inert from here on
+    bool fed = false;              // (the start is set before the first feed)
+    int64_t next_offset = -1;      // the offset behind the last batch a feed took (-1: none yet)
+    int64_t discarded_batches = 0, dropped_records = 0;  // surge_ingest_below_start
+    int64_t floored_section = -1;  // the section of the last drain_sections that straddles the start (-1: none)
+    bool live() const { return first > 0 && !passed; }
+  } start;
 };
 
 namespace {
@@ -363,9 +376,18 @@ inline int64_t deliver_idx(surge_ingest* g, Rec& r) {
 // number of records deliverable from the head of the queue
 int64_t ready_count(const surge_ingest* g) {
   int64_t n = 0;
+  bool live = g->start.live();
   for (const Batch& b : g->queue) {
     if (b.decided == 0) break;  // an open transaction: nothing behind it is stable yet
-    if (b.decided == 1) n += b.sect_off >= 0 ? (int64_t)b.count : (int64_t)(b.recs.size() - b.next);
+    if (b.decided != 1) continue;
+    if (!live) {
+      n += b.sect_off >= 0 ? (int64_t)b.count : (int64_t)(b.recs.size() - b.next);
+      continue;
+    }
+    // below the start nothing is deliverable (of a section that straddles it the device decides: all of it counts)
+    if (b.sect_off >= 0) n += b.last_offset >= g->start.first ? (int64_t)b.count : 0;
+    else for (size_t i = b.next; i < b.recs.size(); ++i) n += b.recs[i].offset >= g->start.first;
+    live = b.last_offset < g->start.first;
   }
   return n;
 }
@@ -408,7 +430,12 @@ int32_t parse_records(surge_ingest* g, Batch& b, const BatchHeader& h, const uin
       continue;
     }
     if (klen == 0 && vlen == 0) {  // the producer's "flush" record (KafkaProducerActorImpl.scala:322-329)
-      g->counters[C_FLUSH_SKIPPED] += 1;
+      if (g->start.live() && h.base_offset + offset_delta < g->start.first) {  // below the start it is dropped like any record
+        g->counters[C_RECORDS_DECODED] -= 1;
+        g->start.dropped_records += 1;
+      } else {
+        g->counters[C_FLUSH_SKIPPED] += 1;
+      }
       continue;
     }
     Rec rec;
@@ -437,23 +464,53 @@ int64_t queued_section_bytes(const surge_ingest& g) {
 // behind it is stable yet) and passes aborted batches.  fn(rec, k) gets the k-th of them and answers false to refuse it,
 // which ends the walk with -1; otherwise the count comes back.  kPop: what was visited leaves the queue, and the batches
 // that are exhausted or aborted in front of it go with it; without it the queue stays as it is.
+// A start offset (surge_ingest_set_start_offset): records below it are passed over, unseen by fn, until a batch that reaches
+// the start has been visited to its end; the popping walk counts them (and the batches that lie below the start as a whole).
 template <bool kPop, class Fn>
 inline int64_t visit_ready(surge_ingest* g, int64_t max, Fn&& fn) {
   int64_t n = 0;
   size_t at = 0;  // (a popping walk only ever looks at the front)
-  while (n < max && at < g->queue.size()) {
+  surge_ingest::Start& st = g->start;
+  bool live = st.live();
+  while ((n < max || live) && at < g->queue.size()) {  // (below a live start the walk goes on without room: what it passes over takes none)
     Batch& b = g->queue[at];
     if (b.decided == 0) break;
     if (b.decided == 1) {
       size_t i = b.next;
-      for (; n < max && i < b.recs.size(); ++i, ++n)
+      for (; i < b.recs.size(); ++i) {
+        if (live && b.recs[i].offset < st.first) {
+          if (kPop) { g->counters[C_RECORDS_DECODED] -= 1; st.dropped_records += 1; }
+          continue;
+        }
+        if (n == max) break;
         if (!fn(b.recs[i], n)) return -1;
+        ++n;
+      }
       if (kPop) b.next = i;
+      if (i < b.recs.size()) break;  // no room for the batch's next record
+      if (live && i == b.recs.size()) {
+        if (b.last_offset >= st.first) live = false;
+        else if (kPop) st.discarded_batches += 1;
+      }
     }
     if (!kPop) ++at;
     else if (b.decided == 2 || b.next == b.recs.size()) g->queue.pop_front();
   }
+  if (kPop && !live) st.passed = st.first > 0;
   return n;
+}
+
+// The offset a consumer resumes from: behind the last batch a feed took, in front of whatever the queue still holds to be
+// delivered — an open transaction, committed batches not drained yet (aborted ones are already decided) — and never below
+// the start.
+int64_t position_of(const surge_ingest* g) {
+  int64_t pos = g->start.next_offset < 0 ? 0 : g->start.next_offset;
+  for (const Batch& b : g->queue) {
+    if (b.decided == 2) continue;
+    pos = (b.sect_off < 0 && b.next > 0 && b.next < b.recs.size()) ? b.recs[b.next].offset : b.base_offset;
+    break;
+  }
+  return pos < g->start.first ? g->start.first : pos;
 }
 
 constexpr const char* kFramesOnly = "this decoder frames batches for a surge_device_decoder (SURGE_INGEST_FRAMES): use surge_ingest_drain_sections";
@@ -609,6 +666,8 @@ int32_t take_batch(surge_ingest* g, const BatchHeader& h, const uint8_t* crc_ver
   }
   Batch b;
   b.producer_id = h.producer_id;
+  b.base_offset = h.base_offset;
+  b.last_offset = h.base_offset + h.last_offset_delta;
   int control_type = -1;
   if (g->frames && !h.control()) {
     if (defer_crc && recs != h.recs) return fail(g, E_UNSUPPORTED, "SURGE_INGEST_DEVICE_CRC needs the sections to travel as they are on the wire (SURGE_INGEST_DEVICE_LZ4 for lz4 topics)");
@@ -618,6 +677,7 @@ int32_t take_batch(surge_ingest* g, const BatchHeader& h, const uint8_t* crc_ver
     if (rc != OK) return rc;
   }
   g->counters[C_BATCHES] += 1;
+  g->start.next_offset = b.last_offset + 1;
   if (h.control()) {
     g->counters[C_CONTROL_BATCHES] += 1;
     if (control_type == 0 || control_type == 1) apply_marker(g, h.producer_id, control_type, n_open);
@@ -724,6 +784,7 @@ int32_t surge_ingest_set_threads(surge_ingest* g, int32_t n_threads) {
 int32_t surge_ingest_feed(surge_ingest* g, const uint8_t* data, int64_t len, int64_t* consumed_out) {
   if (!g) return fail(nullptr, E_INVALID, "handle is NULL");
   if (len < 0 || (!data && len > 0)) return fail(g, E_INVALID, "bad buffer");
+  g->start.fed = true;
   int64_t pos = 0;
   int32_t rc;
   try {
@@ -818,15 +879,28 @@ int32_t surge_ingest_drain_sections(surge_ingest* g, int64_t max_sections, surge
   if (!g || !n_out || max_sections < 0 || (!out && max_sections > 0)) return fail(g, E_INVALID, "bad argument");
   if (!g->frames) return fail(g, -2, "surge_ingest_drain_sections needs a decoder created with SURGE_INGEST_FRAMES");
   int64_t n = 0, recs = 0;
+  surge_ingest::Start& st = g->start;
+  st.floored_section = -1;
   while (n < max_sections && !g->queue.empty()) {
     Batch& b = g->queue.front();
     if (b.decided == 0) break;  // an open transaction: nothing behind it is stable yet
-    if (b.decided == 1) {
+    if (b.decided == 1 && st.live() && b.last_offset < st.first) {  // below the start as a whole: never handed out
+      g->counters[C_RECORDS_DECODED] -= b.count;
+      st.discarded_batches += 1;
+      st.dropped_records += b.count;
+    } else if (b.decided == 1) {
       out[n].byte_off = b.sect_off + b.crc_prefix;
       out[n].byte_len = b.sect_len - b.crc_prefix;
       out[n].base_offset = b.base_offset;
       out[n].n_records = b.count;
       out[n].codec = b.sect_codec | (b.crc_prefix == 8 ? SURGE_SECTION_CRC_PENDING : b.crc_prefix == 44 ? SURGE_SECTION_CRC_WIRE : 0);
+      if (st.live()) {  // the first batch that reaches the start: the one that can straddle it
+        if (b.base_offset < st.first) {
+          out[n].codec |= SURGE_SECTION_FLOORED;
+          st.floored_section = n;
+        }
+        st.passed = true;
+      }
       recs += b.count;
       ++n;
     }
@@ -921,8 +995,9 @@ struct MemberSave {
   int64_t counters[C_COUNT];
   int cur;
   bool handed_out;
-  void save(const surge_ingest& x) { queue = x.queue; std::memcpy(counters, x.counters, sizeof counters); cur = x.cur; handed_out = x.handed_out; }
-  void restore(surge_ingest& x) { x.queue.swap(queue); std::memcpy(x.counters, counters, sizeof counters); x.cur = cur; x.handed_out = handed_out; }
+  surge_ingest::Start start;
+  void save(const surge_ingest& x) { queue = x.queue; std::memcpy(counters, x.counters, sizeof counters); cur = x.cur; handed_out = x.handed_out; start = x.start; }
+  void restore(surge_ingest& x) { x.queue.swap(queue); std::memcpy(x.counters, counters, sizeof counters); x.cur = cur; x.handed_out = handed_out; x.start = start; }
 };
 
 }  // namespace
@@ -937,6 +1012,7 @@ struct surge_ingest_group {
   std::vector<MemberSave> saved;
   std::vector<int32_t> status;
   std::vector<int64_t> consumed;
+  std::vector<surge_section_floor> floors;  // of the last feed's sections (surge_ingest_group_take_floors)
   // in-place feeds (surge_ingest_group_receive_buffer): the slab the caller is receiving into and the room in front of the
   // receive region that the partitions' carried sections (open transactions) move into
   int recv_slab = -1;
@@ -1265,6 +1341,7 @@ int32_t surge_ingest_group_feed(surge_ingest_group* grp, const uint8_t* const* d
   const int32_t n = (int32_t)grp->g.size();
   *n_sections_out = 0;
   *slab_out = nullptr;
+  grp->floors.clear();
   if (consumed_out) std::memset(consumed_out, 0, sizeof(int64_t) * (size_t)n);
   for (int32_t p = 0; p < n; ++p)
     if (len[p] < 0 || (!data[p] && len[p] > 0)) { grp->err = "bad buffer for partition " + std::to_string(p); return E_INVALID; }
@@ -1320,7 +1397,10 @@ int32_t surge_ingest_group_feed(surge_ingest_group* grp, const uint8_t* const* d
     }
     int64_t at = 0;
     for (int32_t p = 0; p < n; ++p) {
-      for (const surge_batch_section& sct : grp->drained[(size_t)p]) sections_out[at++] = sct;
+      for (const surge_batch_section& sct : grp->drained[(size_t)p]) {
+        if (sct.codec & SURGE_SECTION_FLOORED) grp->floors.push_back(surge_section_floor{p, 0, at, grp->g[(size_t)p]->start.first});
+        sections_out[at++] = sct;
+      }
       if (consumed_out) consumed_out[p] = grp->consumed[(size_t)p];
     }
     *n_sections_out = at;
@@ -1354,3 +1434,5 @@ int32_t surge_ingest_counters(const surge_ingest* g, int64_t out[8]) {
 }
 
 }  // extern "C"
+
+#include "ingest_start.h"  // start offsets, floors and positions: the exports (what they read is above)

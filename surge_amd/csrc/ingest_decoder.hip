@@ -93,7 +93,6 @@ int32_t create_streams_and_events(surge_device_decoder* d, const DecoderOptions&
 // the event template as the kernels use it (EvjDevice: the distinct field names, each once, and per type which of them it
 // reads), to the device with the number parser's table
 int32_t upload_template(surge_device_decoder* d, const surge_event_json_template* tmpl) {
-  d->h_tmpl = *tmpl;
   static EvjDevice ev;  // (a few KB of names: off the stack; create is not a hot path)
   static std::mutex ev_mu;
   std::lock_guard<std::mutex> lk(ev_mu);
@@ -121,6 +120,7 @@ int32_t upload_template(surge_device_decoder* d, const surge_event_json_template
   }
   if (ev.n_names - 1 > (uint32_t)kEvjTrack)
     return dfail(d, E_UNSUPPORTED, "the event template names more than 8 distinct sequence / argument fields (decode this topic with surge_ingest_drain_json)");
+  d->h_tmpl = *tmpl;  // (behind every refusal: a template that is not taken leaves the decoder as it was)
   DCHK(d, d->d_tmpl.reserve(sizeof(ev), false, d->stream));
   DCHK(d, hipMemcpy(d->d_tmpl.p, &ev, sizeof(ev), hipMemcpyHostToDevice));
   DCHK(d, d->d_ptab.reserve(sizeof(surge::F64ParseTable), false, d->stream));
@@ -305,12 +305,17 @@ int32_t surge_device_decoder_destroy(surge_device_decoder* d) {
   return OK;
 }
 
+int32_t surge_device_decoder_push_parts_floored_async(surge_device_decoder* d, int32_t n_parts, const uint8_t* const* bytes, const surge_batch_section* const* sections,
+                                                      const int64_t* n_sections, int64_t n_floors, const surge_section_floor* floors) {
+  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (n_parts < 0 || (n_parts > 0 && (!bytes || !sections || !n_sections)) || n_floors < 0 || (n_floors > 0 && !floors)) return dfail(d, E_INVALID, "bad argument");
+  DeviceScope scope(d->device);
+  return enqueue_push(d, [&](PushSlot& s) { return stage1_wire(d, s, n_parts, bytes, sections, n_sections, n_floors, floors); });
+}
+
 int32_t surge_device_decoder_push_parts_async(surge_device_decoder* d, int32_t n_parts, const uint8_t* const* bytes, const surge_batch_section* const* sections,
                                               const int64_t* n_sections) {
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
-  if (n_parts < 0 || (n_parts > 0 && (!bytes || !sections || !n_sections))) return dfail(d, E_INVALID, "bad argument");
-  DeviceScope scope(d->device);
-  return enqueue_push(d, [&](PushSlot& s) { return stage1_wire(d, s, n_parts, bytes, sections, n_sections); });
+  return surge_device_decoder_push_parts_floored_async(d, n_parts, bytes, sections, n_sections, 0, nullptr);
 }
 
 int32_t surge_device_decoder_push_async(surge_device_decoder* d, const uint8_t* bytes, const surge_batch_section* sections, int64_t n_sections) {
@@ -353,13 +358,41 @@ int32_t surge_device_decoder_reserve(surge_device_decoder* d, int64_t n_keys, in
   return OK;
 }
 
-int32_t surge_device_decoder_push(surge_device_decoder* d, const uint8_t* bytes, const surge_batch_section* sections, int64_t n_sections) {
+int32_t surge_device_decoder_push_floored(surge_device_decoder* d, const uint8_t* bytes, const surge_batch_section* sections, int64_t n_sections, int64_t n_floors,
+                                          const surge_section_floor* floors) {
   if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
   if (n_sections < 0 || (n_sections > 0 && (!bytes || !sections))) return dfail(d, E_INVALID, "bad argument");
   if (d->n_pending != 0) return dfail(d, SURGE_E_STATE, "asynchronous pushes are pending: finish them first (results are appended in push order)");
   if (n_sections == 0) return OK;
-  const int32_t rc = surge_device_decoder_push_async(d, bytes, sections, n_sections);
+  const int32_t rc = surge_device_decoder_push_parts_floored_async(d, 1, &bytes, &sections, &n_sections, n_floors, floors);
   return rc != OK ? rc : surge_device_decoder_push_finish(d);
+}
+
+int32_t surge_device_decoder_push(surge_device_decoder* d, const uint8_t* bytes, const surge_batch_section* sections, int64_t n_sections) {
+  return surge_device_decoder_push_floored(d, bytes, sections, n_sections, 0, nullptr);
+}
+
+// A state decoder that has loaded its topic goes on as the events decoder of the same aggregates: the key table stays where it
+// is — its ids are the resident state's rows — and only what names the mode changes.
+int32_t surge_device_decoder_continue_as_events(surge_device_decoder* d, const surge_event_json_template* tmpl) {
+  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (!d->states) return dfail(d, SURGE_E_STATE, "not a state decoder (surge_device_decoder_create_states): an events decoder is one already, and the switch is one-way");
+  if (d->n_pending != 0) return dfail(d, SURGE_E_STATE, "asynchronous pushes are pending: finish and load them first");
+  if (d->n_records != 0) return dfail(d, SURGE_E_STATE, "delivered state records are waiting: load them (surge_device_decoder_load_states) or clear them first");
+  if (d->poisoned) return dfail(d, SURGE_E_STATE, "an earlier push failed on the device half way: destroy this decoder and create a new one");
+  if (tmpl && surge_event_json_validate(tmpl) != 0) return dfail(d, E_INVALID, std::string("event template: ") + surge_event_json_last_error());
+  DeviceScope scope(d->device);
+  DCHK(d, hipStreamSynchronize(d->stream));  // (the last load read the value buffers on the handle's stream behind an event of this one; it has returned)
+  if (tmpl) {
+    const int32_t rc = upload_template(d, tmpl);  // (the decoder is a state decoder still if this fails)
+    if (rc != OK) return rc;
+  }
+  for (surge_device_decoder::Buf* b : {&d->r_val, &d->r_val_off, &d->vlen, &d->vscan, &d->val_src, &d->long_runs, &d->st_status, &d->st_spans}) b->release();
+  d->val_bytes = 0;
+  d->json = tmpl != nullptr;
+  d->states = false;
+  d->continued = true;
+  return OK;
 }
 
 int32_t surge_device_decoder_push_records(surge_device_decoder* d, const uint8_t* keys, const int64_t* key_off, const uint8_t* values,
@@ -429,6 +462,12 @@ int32_t surge_device_decoder_key_table(surge_device_decoder* d, const uint8_t** 
 int32_t surge_device_decoder_counters(const surge_device_decoder* d, int64_t out[4]) {
   if (!d || !out) return E_INVALID;
   for (int i = 0; i < 4; ++i) out[i] = d->counters[i];
+  return OK;
+}
+
+int32_t surge_device_decoder_below_floor(const surge_device_decoder* d, int64_t* n_out) {
+  if (!d || !n_out) return E_INVALID;
+  *n_out = d->below_floor;
   return OK;
 }
 

@@ -73,6 +73,8 @@ struct PushSlot {
   Lz4Plan lz4;                      // the LZ4 frames' blocks (ingest_lz4.hip plans them)
   std::vector<CrcSpan> h_crc;       // sections whose CRC-32C this push finishes on the device
   Buf crc_spans;
+  std::vector<int64_t> h_floors;    // per section the offset its records must reach (INT64_MIN: none); empty: a push without floors
+  Buf d_floors;
   ErrorCell h_err;
   hipStream_t stream = nullptr;
   hipEvent_t done = nullptr;      // recorded on `stream` behind stage 1
@@ -97,6 +99,7 @@ struct surge_device_decoder {
   hipStream_t stream = nullptr;
   bool json = false;
   bool states = false;  // state mode (surge_device_decoder_create_states): values are kept (r_val / r_val_off), not decoded into events
+  bool continued = false;  // was a state decoder (surge_device_decoder_continue_as_events): its key table and kept string columns are that decoder's
   // Two host threads may drive one decoder: one enqueues stage 1 (push_async / push_parts_async), the other finishes pushes
   // (push_finish*, result, clear, append_decoded*).  `mu` covers what both touch: the slot queue and the error text.
   std::mutex mu;
@@ -150,6 +153,7 @@ struct surge_device_decoder {
   int64_t poll_ns = 0;  // > 0 (SURGE_INGEST_WAIT=poll): the waits query the event between naps of this length instead
   bool consumed_valid = false;
   int64_t counters[4] = {0, 0, 0, 0};  // records seen, delivered, flush records skipped, f64 values re-parsed on the host
+  int64_t below_floor = 0;             // records passed over below their section's floor (surge_device_decoder_below_floor)
   int64_t chain_fallbacks = 0;         // batches whose records the one-lane walk chained after the parallel recognition declined (SURGE_EXPERIMENTS builds print it)
   int64_t reseeds = 0, pushes = 0;
   bool slots_sized = false;  // the first wire push has sized every slot's buffers like its own
@@ -230,7 +234,7 @@ inline hipError_t wait_stream(surge_device_decoder* d, hipStream_t st) {
 
 // ---- ingest_stage1.hip: nothing here reads or writes the key table; everything is enqueued on the slot's stream ------------
 int32_t stage1_wire(surge_device_decoder* d, PushSlot& s, int32_t n_parts, const uint8_t* const* bytes, const surge_batch_section* const* sections,
-                    const int64_t* n_sections);
+                    const int64_t* n_sections, int64_t n_floors, const surge_section_floor* floors);
 int32_t stage1_records(surge_device_decoder* d, PushSlot& s, const uint8_t* keys, const int64_t* key_off, const uint8_t* values, const int64_t* value_off,
                        const int64_t* offsets, int64_t n);
 // ---- ingest_stage2.hip: interning, compaction, append on the decoder's stream; wait = false leaves the closing wait out -----

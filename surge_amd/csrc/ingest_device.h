@@ -31,6 +31,7 @@ enum : uint32_t {
   RS_EMPTY_VALUE = 10,  // state mode: an empty, non-null value under a key (writeState never writes one; the loader reads empty as a tombstone)
   RS_ENVELOPE = 11,     // enveloped events (JsonCtx::envelope): the value is not `[aggregateId] [payload]` and nothing else (sp_envelope_spans, state_parse.h)
   RS_KEY_MISMATCH = 12, // ... its aggregateId is not the aggregate id of the record's key
+  RS_BELOW = 13,        // below its section's floor (a consumer's start offset): passed over like RS_SKIP — not an error, never reported
   RS_COUNT,             // (how many there are: the host's text per status is checked against it, ingest_stage2.hip)
 };
 
@@ -54,6 +55,7 @@ struct ErrorCell {
   unsigned int reserved, n_f64_host;
   unsigned int lz4_bad;          // the first section whose LZ4 frame did not decode (~0 = none)
   unsigned int crc_bad;          // the first section whose bytes do not give the batch's CRC-32C (~0 = none; SURGE_INGEST_DEVICE_CRC)
+  unsigned int n_below, pad;     // records below their section's floor (RS_BELOW)
 };
 
 __device__ __forceinline__ void report(ErrorCell* err, int64_t rec, uint32_t status) {
@@ -219,9 +221,10 @@ Lz4ScratchBytes lz4_scratch_bytes(const Lz4Plan& plan);
 hipError_t launch_lz4(const Lz4Plan& plan, const uint8_t* bytes, uint8_t* area, const Lz4Block* d_blocks, Lz4Work w, Section* sections, ErrorCell* err, hipStream_t st);
 
 // ---- ingest_records.hip: meta / ev_tmp / f64_host_list per record ---------------------------------------------------------------
-// one workgroup per section, as wide as max_recs (the push's largest batch) needs
+// one workgroup per section, as wide as max_recs (the push's largest batch) needs; floors (nullable; events mode only): per section
+// the offset below which its records are passed over, INT64_MIN for none
 hipError_t launch_sections(const uint8_t* bytes, const Section* sections, int64_t n_sections, int32_t max_recs, uint64_t seed, JsonCtx jc, RecMeta* meta,
-                           uint4* ev_tmp, uint32_t* f64_host_list, ErrorCell* err, hipStream_t st);
+                           uint4* ev_tmp, uint32_t* f64_host_list, ErrorCell* err, const int64_t* floors, hipStream_t st);
 // records that arrive already framed: the bytes hold the keys first, the values from val_base on
 hipError_t launch_records(const uint8_t* bytes, const int64_t* key_off, const int64_t* val_off, const int64_t* offsets, int64_t val_base, int64_t n_rec,
                           uint64_t seed, JsonCtx jc, RecMeta* meta, uint4* ev_tmp, uint32_t* f64_host_list, ErrorCell* err, hipStream_t st);

@@ -182,7 +182,7 @@ int32_t surge_device_decoder_keep_strings(surge_device_decoder* d, int32_t on) {
 
 int32_t surge_device_decoder_state_strings(surge_device_decoder* d, int32_t column, const uint8_t** d_utf8, const int64_t** d_off, int64_t* n_agg) {
   if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
-  if (!d->states) return dfail(d, SURGE_E_STATE, "not a state decoder (surge_device_decoder_create_states): an events decoder holds no state values");
+  if (!d->states && !d->continued) return dfail(d, SURGE_E_STATE, "not a state decoder (surge_device_decoder_create_states): an events decoder holds no state values");
   if (column < 0 || column >= SURGE_JSON_STRING_COLUMNS) return dfail(d, E_INVALID, "string column out of range");
   const auto& col = d->str_cols[column];
   if (d_utf8) *d_utf8 = col.cur < 0 ? nullptr : (const uint8_t*)col.utf8[col.cur].p;

@@ -315,8 +315,12 @@ __device__ __forceinline__ uint32_t decode_enveloped_value(const JsonCtx& jc, P 
 
 // One record body [body, end) of a section that starts at `base` (absolute offset sec_off in the staged bytes); `valid` =
 // this lane has a record.  kEnvelope: the values are enveloped events (an instantiation of its own, see section_kernel).
-template <bool kEnvelope, typename P>
-__device__ __forceinline__ void decode_record(P base, int64_t sec_off, int64_t base_offset, bool valid, int32_t body, int32_t end, int64_t gi, uint64_t seed,
+// kFloor: the section straddles its partition's start offset (surge_ingest_set_start_offset): a well-formed record whose offset
+// lies below `floor` is RS_BELOW — what the host drain passes over: no key hashed, no value looked at (so none refused, none handed
+// back for its Double), not kept by stage 2; counted in ErrorCell::n_below.  A record that is malformed is malformed on either side
+// of the floor, as it is to the host framer, which parses every record of a batch it takes.
+template <bool kEnvelope, bool kFloor, typename P>
+__device__ __forceinline__ void decode_record(P base, int64_t sec_off, int64_t base_offset, int64_t floor, bool valid, int32_t body, int32_t end, int64_t gi, uint64_t seed,
                                               const JsonCtx& jc, RecMeta* __restrict__ meta, uint4* __restrict__ ev_tmp,
                                               uint32_t* __restrict__ f64_host_list, ErrorCell* err) {
   RecMeta m;
@@ -340,7 +344,9 @@ __device__ __forceinline__ void decode_record(P base, int64_t sec_off, int64_t b
     // (headers follow; the chain already knows where the record ends)
     if (q.ok && klen >= -1 && vlen >= -1 && klen < (1ll << 31) && vlen < (1ll << 31)) {
       m.offset = base_offset + offset_delta;
-      if (klen == 0 && vlen == 0) {
+      if (kFloor && m.offset < floor) {  // (kFloor is a constant: without it the test and its branch are not compiled at all)
+        m.status = RS_BELOW;
+      } else if (klen == 0 && vlen == 0) {
         m.status = RS_SKIP;  // KafkaProducerActorImpl.scala:322-329
       } else if (klen < 0 || vlen < 0) {
         m.status = RS_NULL;
@@ -379,7 +385,8 @@ __device__ __forceinline__ void decode_record(P base, int64_t sec_off, int64_t b
     m.status = st;
   }
   if (!valid) return;
-  if (m.status >= RS_NULL) report(err, gi, m.status);
+  if (kFloor && m.status == RS_BELOW) atomicAdd(&err->n_below, 1u);  // (at most one section per partition ever carries a floor)
+  else if (m.status >= RS_NULL) report(err, gi, m.status);
   meta[gi] = m;
   ev_tmp[gi] = e;
 }
@@ -626,10 +633,15 @@ __device__ bool chain_records_parallel(lds_ptr_t base, int32_t len, int32_t cnt,
 // pushed those into scratch memory).
 // kEnvelope: the same again for enveloped event values (JsonCtx::envelope, launch-uniform too): the envelope reader in front of
 // the JSON walk is an instantiation of its own, and the two above keep their instructions and registers.
-template <int kSecThreads, bool kStates, bool kEnvelope>
+// kFloor: and once more for a push that carries a floor (decode_record; events mode only — the state topic is read from its
+// beginning): floors[] holds one int64 per section, INT64_MIN where there is none.  Every other push launches the instantiations
+// without it, which never read the argument.
+template <int kSecThreads, bool kStates, bool kEnvelope, bool kFloor>
 __global__ void __launch_bounds__(kSecThreads) __attribute__((amdgpu_waves_per_eu(kSecThreads == 256 ? 5 : 6)))  // (four waves at 80 VGPRs spill)
 section_kernel(const uint8_t* __restrict__ bytes, const Section* __restrict__ sections, int64_t n_sections, int64_t lo_excl, int64_t cap, int32_t take_rest,
-               uint64_t seed, JsonCtx jc, RecMeta* __restrict__ meta, uint4* __restrict__ ev_tmp, uint32_t* __restrict__ f64_host_list, ErrorCell* err) {
+               uint64_t seed, JsonCtx jc, RecMeta* __restrict__ meta, uint4* __restrict__ ev_tmp, uint32_t* __restrict__ f64_host_list, ErrorCell* err,
+               const int64_t* __restrict__ floors) {
+  static_assert(!(kFloor && kStates), "the state topic has no floor");
   extern __shared__ __attribute__((aligned(16))) uint8_t sec_smem[];
   __shared__ int32_t s_pos, s_bad;
   __shared__ int32_t s_link[64];
@@ -664,12 +676,14 @@ section_kernel(const uint8_t* __restrict__ bytes, const Section* __restrict__ se
   if (len >= (1ll << 31)) {  // a section of 2 GiB: nothing writes one (a batch's length is an int32)
     for (int32_t i0 = 0; i0 < sec.n_records; i0 += kSecThreads) {
       if constexpr (kStates) decode_state_record(bytes, 0, 0, i0 + (int32_t)threadIdx.x < sec.n_records, -1, -1, sec.rec_first + i0 + threadIdx.x, seed, meta, err);
-      else decode_record<kEnvelope>(bytes, 0, 0, i0 + (int32_t)threadIdx.x < sec.n_records, -1, -1, sec.rec_first + i0 + threadIdx.x, seed, jc, meta, ev_tmp, f64_host_list, err);
+      else decode_record<kEnvelope, kFloor>(bytes, 0, 0, 0, i0 + (int32_t)threadIdx.x < sec.n_records, -1, -1, sec.rec_first + i0 + threadIdx.x, seed, jc, meta, ev_tmp, f64_host_list, err);
     }
     return;
   }
   const lds_ptr_t lbase = (lds_ptr_t)sec_smem + skew;
   const uint8_t* gbase = bytes + sec.byte_off;
+  int64_t floor = 0;
+  if constexpr (kFloor) floor = floors[blockIdx.x];
   for (int32_t r0 = 0; r0 < sec.n_records; r0 += kSecRecs) {
     const int32_t cnt = sec.n_records - r0 < kSecRecs ? sec.n_records - r0 : kSecRecs;
     int32_t chained = 0;
@@ -706,9 +720,9 @@ section_kernel(const uint8_t* __restrict__ bytes, const Section* __restrict__ se
         if (staged) decode_state_record(lbase, sec.byte_off, sec.base_offset, valid, body, end, sec.rec_first + r0 + i, seed, meta, err);
         else decode_state_record(gbase, sec.byte_off, sec.base_offset, valid, body, end, sec.rec_first + r0 + i, seed, meta, err);
       } else if (staged) {
-        decode_record<kEnvelope>(lbase, sec.byte_off, sec.base_offset, valid, body, end, sec.rec_first + r0 + i, seed, jc, meta, ev_tmp, f64_host_list, err);
+        decode_record<kEnvelope, kFloor>(lbase, sec.byte_off, sec.base_offset, floor, valid, body, end, sec.rec_first + r0 + i, seed, jc, meta, ev_tmp, f64_host_list, err);
       } else {
-        decode_record<kEnvelope>(gbase, sec.byte_off, sec.base_offset, valid, body, end, sec.rec_first + r0 + i, seed, jc, meta, ev_tmp, f64_host_list, err);
+        decode_record<kEnvelope, kFloor>(gbase, sec.byte_off, sec.base_offset, floor, valid, body, end, sec.rec_first + r0 + i, seed, jc, meta, ev_tmp, f64_host_list, err);
       }
     }
     __syncthreads();
@@ -770,8 +784,10 @@ __global__ void __launch_bounds__(256) records_kernel(const uint8_t* __restrict_
 // out of 18.3 KiB of LDS (8 workgroups per CU), the rest out of 66 KiB or, beyond 64 KiB, in place
 // (round 5: a third, 8 KiB class in front — a publisher that flushes every 64 events writes 7 KiB batches, and 10.4 KiB of LDS
 // instead of 18.3 lets a CU hold 15 of them; the workgroup is as wide as the push's largest batch needs)
+// floors: one int64 per section for a push that carries a floor (nullptr: none — the instantiations without kFloor)
 hipError_t launch_sections(const uint8_t* bytes, const Section* sections, int64_t n_sections, int32_t max_recs, uint64_t seed, JsonCtx jc, RecMeta* meta,
-                           uint4* ev_tmp, uint32_t* f64_host_list, ErrorCell* err, hipStream_t st) {
+                           uint4* ev_tmp, uint32_t* f64_host_list, ErrorCell* err, const int64_t* floors, hipStream_t st) {
+  if (floors && jc.states) return hipErrorInvalidValue;  // (stage 1 refuses it by name)
   const int64_t caps[3] = {8320, 16640, 65536};
   const int n_caps = 3;
 #ifdef SURGE_EXPERIMENTS
@@ -791,19 +807,22 @@ hipError_t launch_sections(const uint8_t* bytes, const Section* sections, int64_
     const size_t lds = (size_t)((caps[c] + 47) & ~15ll) + 2 * (size_t)kSecRecs * 4;
     const int64_t lo_excl = c == 0 ? -1 : caps[c - 1];
     const int32_t rest = c == n_caps - 1 ? 1 : 0;
-#define SURGE_SECTION_LAUNCH(T, S, E)                                                                                                                \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(section_kernel<T, S, E>), dim3((unsigned)n_sections), dim3(T), lds, st, bytes, sections, n_sections, lo_excl, caps[c], rest, seed, jc, meta, \
-                     ev_tmp, f64_host_list, err)
-#define SURGE_SECTION_WIDTH(S, E)                     \
-  do {                                                \
-    if (max_recs <= 64) SURGE_SECTION_LAUNCH(64, S, E);        \
-    else if (max_recs <= 128) SURGE_SECTION_LAUNCH(128, S, E); \
-    else if (max_recs <= 192) SURGE_SECTION_LAUNCH(192, S, E); \
-    else SURGE_SECTION_LAUNCH(256, S, E);                      \
+#define SURGE_SECTION_LAUNCH(T, S, E, F)                                                                                                             \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(section_kernel<T, S, E, F>), dim3((unsigned)n_sections), dim3(T), lds, st, bytes, sections, n_sections, lo_excl, caps[c], rest, seed, jc, meta, \
+                     ev_tmp, f64_host_list, err, floors)
+#define SURGE_SECTION_WIDTH(S, E, F)                     \
+  do {                                                   \
+    if (max_recs <= 64) SURGE_SECTION_LAUNCH(64, S, E, F);        \
+    else if (max_recs <= 128) SURGE_SECTION_LAUNCH(128, S, E, F); \
+    else if (max_recs <= 192) SURGE_SECTION_LAUNCH(192, S, E, F); \
+    else SURGE_SECTION_LAUNCH(256, S, E, F);                      \
   } while (0)
-    if (jc.states) SURGE_SECTION_WIDTH(true, false);
-    else if (jc.envelope && jc.tmpl) SURGE_SECTION_WIDTH(false, true);  // enveloped event values: an instantiation of their own
-    else SURGE_SECTION_WIDTH(false, false);
+    const bool enveloped = jc.envelope && jc.tmpl;  // enveloped event values: an instantiation of their own
+    if (jc.states) SURGE_SECTION_WIDTH(true, false, false);
+    else if (floors && enveloped) SURGE_SECTION_WIDTH(false, true, true);  // a push that carries a floor: likewise
+    else if (floors) SURGE_SECTION_WIDTH(false, false, true);
+    else if (enveloped) SURGE_SECTION_WIDTH(false, true, false);
+    else SURGE_SECTION_WIDTH(false, false, false);
 #undef SURGE_SECTION_WIDTH
 #undef SURGE_SECTION_LAUNCH
 #ifdef SURGE_EXPERIMENTS

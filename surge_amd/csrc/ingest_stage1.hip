@@ -17,7 +17,7 @@ int32_t slot_scratch(surge_device_decoder* d, PushSlot& s, int64_t n_rec) {
   DCHK(d, s.meta.reserve(R * sizeof(RecMeta), false, s.stream));
   if (!d->states) DCHK(d, s.ev_tmp.reserve(R * 16, false, s.stream));
   if (!d->states) DCHK(d, s.f64_list.reserve(R * 4, false, s.stream));
-  static const ErrorCell kZero{~0ull, 0u, 0u, ~0u, ~0u};  // (the source of an asynchronous copy: it must outlive the call)
+  static const ErrorCell kZero{~0ull, 0u, 0u, ~0u, ~0u, 0u, 0u};  // (the source of an asynchronous copy: it must outlive the call)
   DCHK(d, hipMemcpyAsync(s.d_err.p, &kZero, sizeof(kZero), hipMemcpyHostToDevice, s.stream));
   return OK;
 }
@@ -82,7 +82,7 @@ struct WireLayout {
 };
 
 struct SlotNeeds {  // what a slot's buffers have to hold for a push
-  size_t bytes, sections, crc_spans, pinned;
+  size_t bytes, sections, crc_spans, floors, pinned;
   int64_t n_rec;
   Lz4ScratchBytes lz4;
 };
@@ -188,7 +188,8 @@ SlotNeeds slot_needs(const PushSlot& s, const uint8_t* const* bytes, WireLayout&
   n.crc_spans = sizeof(CrcSpan) * s.h_crc.size();
   n.n_rec = L.n_rec;
   n.lz4 = lz4_scratch_bytes(s.lz4);
-  n.pinned = pad16(L.extra.size()) + n.sections + n.lz4.blocks + pad16(n.crc_spans) + 64;
+  n.floors = 8 * s.h_floors.size();
+  n.pinned = pad16(L.extra.size()) + n.sections + n.lz4.blocks + pad16(n.crc_spans) + pad16(n.floors) + 64;
   for (size_t p = 0; p < L.parts.size(); ++p) {
     WireLayout::Part& part = L.parts[p];
     if (part.len == 0) continue;
@@ -203,7 +204,7 @@ SlotNeeds slot_needs(const PushSlot& s, const uint8_t* const* bytes, WireLayout&
 int32_t size_slot(surge_device_decoder* d, PushSlot& t, const SlotNeeds& n) {
   const size_t per_event = d->states ? 0 : (size_t)n.n_rec;  // (a state decoder decodes no value)
   const std::pair<Buf*, size_t> device[] = {{&t.d_bytes, n.bytes}, {&t.d_sections, n.sections}, {&t.meta, (size_t)n.n_rec * sizeof(RecMeta)}, {&t.ev_tmp, per_event * 16},
-                                            {&t.f64_list, per_event * 4}, {&t.crc_spans, n.crc_spans}, {&t.lz4_blocks, n.lz4.blocks}, {&t.lz4_sizes, n.lz4.state},
+                                            {&t.f64_list, per_event * 4}, {&t.crc_spans, n.crc_spans}, {&t.d_floors, n.floors}, {&t.lz4_blocks, n.lz4.blocks}, {&t.lz4_sizes, n.lz4.state},
                                             {&t.lz4_nseq, n.lz4.n_seq}, {&t.lz4_seq, n.lz4.seq}, {&t.lz4_cls, n.lz4.cls}};
   for (const auto& b : device) DCHK(d, b.first->reserve(b.second, false, t.stream));
   return slot_pinned(d, t, n.pinned);
@@ -247,15 +248,36 @@ int32_t stage_and_copy(surge_device_decoder* d, PushSlot& s, const uint8_t* cons
   DCHK(d, hipMemcpyAsync(s.d_sections.p, stage(s.h_secs.data(), sec_bytes), sec_bytes, hipMemcpyHostToDevice, st));
   if (crc_bytes) DCHK(d, hipMemcpyAsync(s.crc_spans.p, stage(s.h_crc.data(), crc_bytes), crc_bytes, hipMemcpyHostToDevice, st));
   if (blk_bytes) DCHK(d, hipMemcpyAsync(s.lz4_blocks.p, stage(s.lz4.blocks.data(), blk_bytes), blk_bytes, hipMemcpyHostToDevice, st));
+  const size_t floor_bytes = 8 * s.h_floors.size();
+  if (floor_bytes) DCHK(d, hipMemcpyAsync(s.d_floors.p, stage(s.h_floors.data(), floor_bytes), floor_bytes, hipMemcpyHostToDevice, st));
+  return OK;
+}
+
+// the sparse floors list as the record stage reads it (s.h_floors): one int64 per section of the push, INT64_MIN where there is
+// none; empty for a push without floors.  `section` counts through the parts' sections in push order.
+int32_t expand_floors(surge_device_decoder* d, PushSlot& s, int64_t total_sections, int64_t n_floors, const surge_section_floor* floors) {
+  s.h_floors.clear();
+  if (n_floors == 0) return OK;
+  if (d->states) return dfail(d, SURGE_E_STATE, "a state decoder reads its topic from the beginning: floors belong to an events decoder");
+  try {
+    s.h_floors.assign((size_t)total_sections, INT64_MIN);
+  } catch (const std::bad_alloc&) {
+    return dfail(d, E_NOMEM, "out of host memory");
+  }
+  for (int64_t i = 0; i < n_floors; ++i) {
+    if (floors[i].section < 0 || floors[i].section >= total_sections) return dfail(d, E_INVALID, "a floor names section " + std::to_string(floors[i].section) + ": the push has " + std::to_string(total_sections));
+    int64_t& f = s.h_floors[(size_t)floors[i].section];
+    f = floors[i].first_offset > f ? floors[i].first_offset : f;
+  }
   return OK;
 }
 
 }  // namespace
 
 // Stage 1 of a wire push: the parts' records sections to the device, LZ4 blocks decoded, every record chained, parsed and
-// its value decoded.
+// its value decoded — records below their section's floor passed over (n_floors > 0: the floored instantiations of the record stage).
 int32_t surge::ingest::host::stage1_wire(surge_device_decoder* d, PushSlot& s, int32_t n_parts, const uint8_t* const* bytes, const surge_batch_section* const* sections,
-                    const int64_t* n_sections) {
+                    const int64_t* n_sections, int64_t n_floors, const surge_section_floor* floors) {
   Laps laps;
   const uint64_t seed = d->seed.load();
   WireLayout L;
@@ -265,9 +287,10 @@ int32_t surge::ingest::host::stage1_wire(surge_device_decoder* d, PushSlot& s, i
   }
   s.n_rec = 0;
   s.wire = true;
-  if (L.total_sections == 0) return OK;
   if (L.total_sections >= (1ll << 31)) return dfail(d, E_UNSUPPORTED, "more than 2^31 batches in one push");
-  int32_t rc = layout_sections(d, s, n_parts, sections, n_sections, L);
+  int32_t rc = expand_floors(d, s, L.total_sections, n_floors, floors);
+  if (rc != OK || L.total_sections == 0) return rc;
+  rc = layout_sections(d, s, n_parts, sections, n_sections, L);
   if (rc != OK || L.n_rec == 0) return rc;
   if (L.n_rec >= (1ll << 32) - 1) return dfail(d, E_UNSUPPORTED, "more than 2^32 - 2 records in one push: push fewer sections at a time");
   rc = plan_frames(d, s, n_parts, bytes, sections, n_sections, L);
@@ -291,7 +314,8 @@ int32_t surge::ingest::host::stage1_wire(surge_device_decoder* d, PushSlot& s, i
   DCHK(d, launch_lz4(s.lz4, dby, (uint8_t*)s.d_bytes.p + L.area_base(), (const Lz4Block*)s.lz4_blocks.p, w, dsec, derr, st));
   laps.lap("lz4 launches");
   const JsonCtx jc = json_ctx(d, dbg_decode() % 10);
-  DCHK(d, launch_sections(dby, dsec, L.total_sections, L.max_recs, seed, jc, (RecMeta*)s.meta.p, (uint4*)s.ev_tmp.p, (uint32_t*)s.f64_list.p, derr, st));
+  DCHK(d, launch_sections(dby, dsec, L.total_sections, L.max_recs, seed, jc, (RecMeta*)s.meta.p, (uint4*)s.ev_tmp.p, (uint32_t*)s.f64_list.p, derr,
+                          s.h_floors.empty() ? nullptr : (const int64_t*)s.d_floors.p, st));
   laps.lap("section launches");
   s.n_rec = L.n_rec;
   s.seed = seed;

@@ -15,7 +15,7 @@ const char* const kWhyBad[] = {"", "", "has a null key or value (not an event)",
                                "collides with another key on its 64-bit hash",
                                "has an empty, non-null value under a key (a state record carries a value or the null of a tombstone)",
                                "is not the protobuf Event envelope the event template names ([aggregateId] [payload] and nothing else)",
-                               "names another aggregateId in its envelope than the aggregate id of its key"};
+                               "names another aggregateId in its envelope than the aggregate id of its key", ""};
 static_assert(sizeof(kWhyBad) / sizeof(kWhyBad[0]) == RS_COUNT, "one text per record status");
 const char* why_bad(uint32_t status) { return status < RS_COUNT ? kWhyBad[status] : "is bad"; }
 
@@ -117,7 +117,7 @@ struct Stage2 {
         d->seed = (d->seed & ~(1ull << 63)) + 1;
         ++d->reseeds;
         launch_intern_reseed(dmeta, n_rec, dby, keys_of(d), d->seed, st);
-        s.h_err = ErrorCell{~0ull, 0u, ec.n_f64_host, ~0u, ~0u};
+        s.h_err = ErrorCell{~0ull, 0u, ec.n_f64_host, ~0u, ~0u, ec.n_below, 0u};
         PCHK(d, hipMemcpyAsync(derr, &s.h_err, sizeof(s.h_err), hipMemcpyHostToDevice, st));
         continue;
       }
@@ -226,7 +226,8 @@ struct Stage2 {
     d->chain_fallbacks += ec.reserved;
     d->n_records += kept;
     d->counters[1] += kept;
-    d->counters[2] += n_rec - kept;
+    d->counters[2] += n_rec - kept - ec.n_below;
+    d->below_floor += ec.n_below;
     ++d->pushes;
     if (wait) {
       PCHK(d, wait_stream(d, st));

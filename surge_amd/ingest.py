@@ -24,9 +24,14 @@ DEVICE_LZ4 = 0x200  # SURGE_INGEST_DEVICE_LZ4: ... and leave LZ4 frames for the 
 DEVICE_CRC = 0x400  # SURGE_INGEST_DEVICE_CRC: ... and finish a data batch's CRC-32C on the GPU (the host checksums its 40 header bytes only)
 SECTION_CRC_PENDING = 0x100  # in a section's codec: {crc, register after the 40 covered header bytes} lie in front of the section
 SECTION_CRC_WIRE = 0x200  # ... (in-place framing) the batch's own crc field and the 40 header bytes it covers do: the device runs the whole CRC
+SECTION_FLOORED = 0x400  # ... the section straddles the framer's start offset: the floors list names it
 
 SECTION_DTYPE = np.dtype([("byte_off", "<i8"), ("byte_len", "<i8"), ("base_offset", "<i8"), ("n_records", "<i4"), ("codec", "<i4")])
 assert SECTION_DTYPE.itemsize == 32
+
+FLOOR_DTYPE = np.dtype([("part", "<i4"), ("reserved", "<i4"), ("section", "<i8"), ("first_offset", "<i8")])  # surge_section_floor
+assert FLOOR_DTYPE.itemsize == 24
+NO_FLOORS = np.zeros(0, dtype=FLOOR_DTYPE)
 
 RECORD_DTYPE = np.dtype([("offset", "<i8"), ("agg_idx", "<i8"), ("key_off", "<i8"), ("key_len", "<i4"),
                          ("value_len", "<i4"), ("value_off", "<i8")])
@@ -102,8 +107,24 @@ class IngestError(RuntimeError):
         self.status = status
 
 
+class Framed(tuple):
+    """What a framer with start offsets yields per fetch: the ``(sections, arena_address)`` pair it always yielded — it
+    destructures and indexes as that — with ``floors`` (``FLOOR_DTYPE`` records naming the sections that straddle a start offset:
+    what ``DeviceDecoder.push`` / ``push_async`` take beside the sections) and ``positions`` (the offset each partition would
+    resume from behind this fetch: ``surge_ingest_position``)."""
+
+    def __new__(cls, sections, address, floors=NO_FLOORS, positions=()):
+        self = super().__new__(cls, (sections, address))
+        self.floors, self.positions = floors, tuple(positions)
+        return self
+
+
 class EventsTopicIngest:
-    def __init__(self, isolation_level: int = READ_COMMITTED, frames: bool = False, device_lz4: bool = False, threads: int = 1, device_crc: bool = False):
+    """``start_offset``: the offset a consumer that sought into the partition begins at (``surge_ingest_set_start_offset``): records
+    below it are not delivered, transactions are read as ever; ``None`` / ``<= 0``: from the beginning."""
+
+    def __init__(self, isolation_level: int = READ_COMMITTED, frames: bool = False, device_lz4: bool = False, threads: int = 1, device_crc: bool = False,
+                 start_offset: Optional[int] = None):
         self._lib = _native.load()
         self._h = ctypes.c_void_p()
         self.frames = frames
@@ -116,6 +137,8 @@ class EventsTopicIngest:
             self._lib.surge_ingest_use_pinned_arena(self._h)
         if threads != 1:  # host threads verifying the batches' CRC-32C of one feed (surge_ingest_set_threads)
             self._check(self._lib.surge_ingest_set_threads(self._h, int(threads)))
+        if start_offset is not None:
+            self.set_start_offset(start_offset)
         self._tail = b""
 
     def close(self):
@@ -148,6 +171,30 @@ class EventsTopicIngest:
     @property
     def ready(self) -> int:
         return int(self._lib.surge_ingest_ready(self._h))
+
+    def set_start_offset(self, first_offset: int) -> None:
+        """Before the first feed (``IngestError`` STATE afterwards)."""
+        self._check(self._lib.surge_ingest_set_start_offset(self._h, int(first_offset)))
+
+    def position(self) -> int:
+        """The offset a consumer would resume from: behind the last batch decided, in front of an open transaction and of
+        anything not drained yet, never below the start — what a publisher commits with a snapshot."""
+        return int(self._lib.surge_ingest_position(self._h))
+
+    def positions(self) -> List[int]:
+        return [self.position()]
+
+    def take_floors(self) -> np.ndarray:
+        """``FLOOR_DTYPE`` records for the sections the last ``drain_sections`` handed out (at most one, once per framer)."""
+        out = np.zeros(1, dtype=FLOOR_DTYPE)
+        got = ctypes.c_int64(0)
+        self._check(self._lib.surge_ingest_take_floors(self._h, 1, out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(got)))
+        return out[: got.value]
+
+    def below_start(self) -> dict:
+        c = (ctypes.c_int64 * 2)()
+        self._check(self._lib.surge_ingest_below_start(self._h, ctypes.byref(c)))
+        return {"batches_discarded": int(c[0]), "records_dropped": int(c[1])}
 
     def counters(self) -> dict:
         c = (ctypes.c_int64 * 8)()
@@ -232,14 +279,16 @@ class FramedFetches:
     one thread)."""
 
     def __init__(self, fetches, isolation_level: int = READ_COMMITTED, device_lz4: bool = True, overlap: bool = True, threads: int = 1, hold: int = 1,
-                 device_crc: bool = True):
+                 device_crc: bool = True, start_offset: Optional[int] = None):
         import queue
         import threading
 
         if not 1 <= hold <= 5:
             raise ValueError("hold must be 1 .. 5 (the framer has six arenas)")
         # device_crc needs the sections as they are on the wire: with host-side LZ4 (device_lz4=False) the host has the bytes in hand anyway
-        self._g = EventsTopicIngest(isolation_level, frames=True, device_lz4=device_lz4, threads=threads, device_crc=device_crc and device_lz4)
+        self._g = EventsTopicIngest(isolation_level, frames=True, device_lz4=device_lz4, threads=threads, device_crc=device_crc and device_lz4,
+                                    start_offset=start_offset)
+        self._started = start_offset is not None  # with a start every item is a Framed: the pair, its floors, the position behind it
         self._fetches = iter(fetches)
         self._overlap = overlap
         self._hold = hold
@@ -258,6 +307,8 @@ class FramedFetches:
         t0 = time.perf_counter()
         self._g.feed(data)
         item = self._g.drain_sections()
+        if self._started:
+            item = Framed(item[0], item[1], self._g.take_floors(), self._g.positions())
         self.framing_seconds.append(time.perf_counter() - t0)
         return item
 
@@ -296,6 +347,13 @@ class FramedFetches:
         """The ingest counters; call it when the iteration has ended (the handle belongs to the framing thread)."""
         return self._g.counters()
 
+    def positions(self) -> List[int]:
+        """Where the partition would be resumed from (``EventsTopicIngest.position``); when the iteration has ended, like ``counters``."""
+        return self._g.positions()
+
+    def below_start(self) -> dict:
+        return self._g.below_start()
+
     def close(self):
         self._stop = True
         if self._thread:
@@ -323,12 +381,14 @@ class PartitionedFramedFetches:
     (the group rotates through six slabs)."""
 
     def __init__(self, fetches, n_partitions: int, threads: int = 8, hold: int = 3, isolation_level: int = READ_COMMITTED, device_lz4: bool = True,
-                 overlap: bool = True, device_crc: bool = True, in_place: bool = False):
+                 overlap: bool = True, device_crc: bool = True, in_place: bool = False, start_offsets=None):
         import queue
         import threading
 
         if not 1 <= hold <= 5:
             raise ValueError("hold must be 1 .. 5 (the group has six slabs)")
+        if start_offsets is not None and len(start_offsets) != n_partitions:
+            raise ValueError(f"start_offsets holds {len(start_offsets)} entries for {n_partitions} partitions (<= 0: a partition without a start)")
         self._lib = _native.load()
         self._h = ctypes.c_void_p()
         rc = self._lib.surge_ingest_group_create(n_partitions, isolation_level | (DEVICE_LZ4 if device_lz4 else 0) | (DEVICE_CRC if device_crc and device_lz4 else 0),
@@ -337,6 +397,11 @@ class PartitionedFramedFetches:
             raise IngestError(rc, (self._lib.surge_ingest_group_last_error(None) or b"").decode())
         if os.environ.get("SURGE_INGEST_PAGEABLE_ARENA") != "1":
             self._lib.surge_ingest_group_use_pinned_slabs(self._h)  # (fails without a GPU: the slabs stay pageable, which works too)
+        self._started = start_offsets is not None
+        if self._started:
+            rc = self._lib.surge_ingest_group_set_start_offsets(self._h, (ctypes.c_int64 * n_partitions)(*[int(o) for o in start_offsets]))
+            if rc != 0:
+                raise IngestError(rc, (self._lib.surge_ingest_group_last_error(self._h) or b"").decode())
         self._threads = max(1, min(threads, n_partitions))
         # in_place: the fetch response is RECEIVED into the group's next page-locked slab (surge_ingest_group_receive_copy: one copy out of
         # the bytes objects on the framing threads, standing in for the socket reads a consumer would aim there) and framed
@@ -402,8 +467,14 @@ class PartitionedFramedFetches:
         if rc != 0:  # all or nothing: the group is what it was before the call (the tails too)
             raise IngestError(rc, (self._lib.surge_ingest_group_last_error(self._h) or b"").decode())
         self._tails = [bufs[p][consumed[p]:] for p in range(n)]
+        item = secs[: n_sec.value], int(slab.value or 0)
+        if self._started:
+            floors = np.zeros(n, dtype=FLOOR_DTYPE)  # (at most one per partition over the group's life)
+            got = ctypes.c_int64(0)
+            self._lib.surge_ingest_group_take_floors(self._h, n, floors.ctypes.data_as(ctypes.c_void_p), ctypes.byref(got))
+            item = Framed(item[0], item[1], floors[: got.value], self.positions())
         self.framing_seconds.append(time.perf_counter() - t0)
-        return secs[: n_sec.value], int(slab.value or 0)
+        return item
 
     _run = FramedFetches._run
     __iter__ = FramedFetches.__iter__
@@ -414,6 +485,18 @@ class PartitionedFramedFetches:
         b, c = ctypes.c_int64(), ctypes.c_int32()
         self._lib.surge_ingest_group_slab_bytes(self._h, ctypes.byref(b), ctypes.byref(c))
         return int(b.value), bool(c.value)
+
+    def positions(self) -> List[int]:
+        """Per partition the offset a consumer would resume from (``surge_ingest_group_positions``); when the iteration has
+        ended, like ``counters`` — or read ``Framed.positions`` of the items of a framer with ``start_offsets``."""
+        out = (ctypes.c_int64 * self._n)()
+        self._lib.surge_ingest_group_positions(self._h, out)
+        return [int(x) for x in out]
+
+    def below_start(self) -> dict:
+        c = (ctypes.c_int64 * 2)()
+        self._lib.surge_ingest_group_below_start(self._h, ctypes.byref(c))
+        return {"batches_discarded": int(c[0]), "records_dropped": int(c[1])}
 
     def cpu_seconds(self):
         """``(receive copy, framing)``: thread CPU seconds the group's host threads have spent so far (``surge_ingest_group_cpu_seconds``)."""
@@ -587,25 +670,41 @@ class DeviceDecoder:
         if rc != 0:
             raise IngestError(rc, (self._lib.surge_device_decoder_last_error(self._h) or b"").decode())
 
-    def push(self, sections: np.ndarray, arena_address: int) -> None:
+    def push(self, sections: np.ndarray, arena_address: int, floors=None) -> None:
+        """``floors``: the ``FLOOR_DTYPE`` records of these sections (``take_floors`` / ``Framed.floors``): records below a
+        section's floor are passed over on the device (``surge_device_decoder_push_floored``)."""
         sections = np.ascontiguousarray(sections, dtype=SECTION_DTYPE)
-        self._check(self._lib.surge_device_decoder_push(self._h, ctypes.c_void_p(arena_address), sections.ctypes.data_as(ctypes.c_void_p),
-                                                        sections.shape[0]))
+        floors = NO_FLOORS if floors is None else np.ascontiguousarray(floors, dtype=FLOOR_DTYPE)
+        self._check(self._lib.surge_device_decoder_push_floored(self._h, ctypes.c_void_p(arena_address), sections.ctypes.data_as(ctypes.c_void_p),
+                                                                sections.shape[0], floors.shape[0], floors.ctypes.data_as(ctypes.c_void_p)))
 
-    def push_async(self, parts) -> None:
+    def push_async(self, parts, floors=None) -> None:
         """Stage 1 of a push — copy, LZ4, record parsing, value decode — enqueued on a stream of its own; ``parts`` is one
         ``(sections, arena_address)`` pair or a list of them (e.g. one per partition of a fetch response: one push, records
         delivered part after part).  The arenas must stay as they are until the matching ``finish()``; up to five pushes
-        may be in flight."""
+        may be in flight.  A part that is a ``Framed`` brings its floors along; ``floors`` gives them for plain pairs, their
+        ``section`` counting through the parts' sections in order."""
         if isinstance(parts, tuple):
             parts = [parts]
         secs = [np.ascontiguousarray(s, dtype=SECTION_DTYPE) for s, _ in parts]
         n = len(parts)
+        if floors is None:  # each Framed part's floors, its section indices moved behind the parts in front of it
+            moved, first = [], 0
+            for part, s in zip(parts, secs):
+                f = getattr(part, "floors", NO_FLOORS)
+                if f.shape[0]:
+                    f = f.copy()
+                    f["section"] += first
+                    moved.append(f)
+                first += s.shape[0]
+            floors = np.concatenate(moved) if moved else NO_FLOORS
+        floors = np.ascontiguousarray(floors, dtype=FLOOR_DTYPE)
         bytes_arr = (ctypes.c_void_p * n)(*[ctypes.c_void_p(a) for _, a in parts])
         secs_arr = (ctypes.c_void_p * n)(*[s.ctypes.data_as(ctypes.c_void_p) for s in secs])
         cnt = (ctypes.c_int64 * n)(*[s.shape[0] for s in secs])
-        self._check(self._lib.surge_device_decoder_push_parts_async(self._h, n, bytes_arr, secs_arr, cnt))
-        self._inflight.append((secs, bytes_arr, secs_arr, cnt))  # (kept until finish(); list.append / pop are atomic: a pushing and a finishing thread share it)
+        self._check(self._lib.surge_device_decoder_push_parts_floored_async(self._h, n, bytes_arr, secs_arr, cnt, floors.shape[0],
+                                                                            floors.ctypes.data_as(ctypes.c_void_p)))
+        self._inflight.append((secs, bytes_arr, secs_arr, cnt, floors))  # (kept until finish(); list.append / pop are atomic: a pushing and a finishing thread share it)
 
     def finish(self, wait: bool = True) -> None:
         """Stage 2 of the oldest unfinished push: key interning, append to the result (``result()``).  ``wait=False``
@@ -674,7 +773,7 @@ class DeviceDecoder:
         """Everything ``ingest`` (created with ``frames=True``) can deliver now; returns the number of batches."""
         sections, arena = ingest.drain_sections()
         if sections.shape[0]:
-            self.push(sections, arena)
+            self.push(sections, arena, ingest.take_floors())
         return int(sections.shape[0])
 
     def result(self):
@@ -771,6 +870,22 @@ class DeviceDecoder:
 
     def clear(self) -> None:
         self._check(self._lib.surge_device_decoder_clear(self._h))
+
+    def continue_as_events(self, template: Optional[EventJsonTemplate] = None) -> None:
+        """A state decoder that has loaded its topic goes on as the events decoder of the same aggregates
+        (``surge_device_decoder_continue_as_events``): the key table stays — the ids it interned are the resident state's rows —
+        and from here on the decoder reads events (``template`` as in the constructor), numbering new ids behind the known
+        ones.  Needs every push finished and every record loaded or cleared; one-way.  Kept string columns stay readable
+        (``state_strings``)."""
+        c = template.to_c() if template is not None else None
+        self._check(self._lib.surge_device_decoder_continue_as_events(self._h, ctypes.byref(c) if c is not None else None))
+        self.states = False
+
+    def below_floor(self) -> int:
+        """Records passed over below a section's floor so far (``surge_device_decoder_below_floor``)."""
+        n = ctypes.c_int64()
+        self._check(self._lib.surge_device_decoder_below_floor(self._h, ctypes.byref(n)))
+        return int(n.value)
 
     def keys(self) -> List[str]:
         n, nb = ctypes.c_int64(), ctypes.c_int64()

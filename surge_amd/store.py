@@ -156,13 +156,57 @@ class GpuReplayStateStore:
         (``SurgeStateStoreConsumer.scala:57-76``).
         Needs values the device decoder reads (16-byte fixed events, or JSON with the model's
         ``event_json_template``); returns the ingest + decoder counters."""
-        from .ingest import DeviceDecoder, FramedFetches, PartitionedFramedFetches, PushPipeline
+        from .ingest import DeviceDecoder
         from .log import KeyTable
+        from .schema import EVENT_DTYPE
+
+        made = []  # the decoder, made for the first fetch with a record in it
+
+        def new_decoder(template):
+            made.append(DeviceDecoder(template, device=self.engine.device))
+            return made[0]
+
+        try:
+            counters, n_agg = self._fold_fetches(fetches, new_decoder, -1, capacity=capacity, overlap=overlap, n_partitions=n_partitions, framing_threads=framing_threads,
+                                                 consumer_threads=consumer_threads, bound_log=bound_log, device_crc=device_crc, in_place=in_place)
+            d = made[0] if made else None
+            if bound_log and d is not None:
+                n_agg = max(n_agg, capacity, d.n_keys)
+                self.engine.pack_staged(n_agg)  # decoded fetches -> ONE bound CSR log
+                self.engine.fold(algo)
+                self.engine.synchronize()
+            elif n_agg < 0:  # nothing deliverable in the whole topic
+                n_agg = capacity
+                self.engine.load_csr(np.zeros(n_agg + 1, dtype=np.int64), np.zeros(0, dtype=EVENT_DTYPE))
+                self.engine.fold()
+            keys = KeyTable()
+            if d is not None:
+                for k in d.keys():
+                    keys.intern(k)
+                counters.update(d.counters())
+            self.keys = keys
+        finally:
+            if made:
+                made[0].close()
+        self.engine.snapshot()  # publishes the host mirror that serves point reads
+        self._restored = True
+        return counters
+
+    def _fold_fetches(self, fetches, decoder_for, n_agg: int, *, capacity: int = 0, overlap: bool = True, n_partitions: int = 0, framing_threads: int = 8,
+                      consumer_threads: int = 1, bound_log: bool = False, device_crc: bool = True, in_place: bool = True, start_offsets=None):
+        """The loop of ``restore_from_fetches``, shared with the tail of ``restore_from_state_topic``: the fetches framed ahead,
+        up to four pushes in flight, the oldest finished and folded (or staged) without a host wait behind the fold.
+        ``decoder_for(template_or_None)`` answers the decoder when the first fetch with a record in it says what the values
+        are (a new events decoder; a state decoder that continues as one) — the caller owns and closes it.  ``n_agg``: the
+        resident state's aggregate count, ``-1`` while nothing is bound (the first fold then binds ``capacity`` aggregates,
+        all None).  ``start_offsets``: per partition (a single int without ``n_partitions``) where the consumer begins
+        (``surge_ingest_set_start_offset``): the framers drop what lies below, the floors of the straddling batches travel
+        with the pushes.  Returns ``(the framer's counters, n_agg)``."""
+        from .ingest import FramedFetches, PartitionedFramedFetches, PushPipeline
         from .schema import EVENT_DTYPE
 
         template = self.model.event_json_template()
         d = None
-        n_agg = -1
         # pushes in flight (measured on the 10 M-aggregate topic: 2 / 3 / 4 / 5 in flight = 4.1 / 4.3 / 4.65 / 4.7e8 events/s on
         # one box): stage 1 of the next fetches runs while this one is interned and folded
         depth = 4 if overlap else 1
@@ -171,7 +215,7 @@ class GpuReplayStateStore:
             """(the pipeline's worker thread) stage 1 of one fetch; the decoder is made for the first fetch with a record in it"""
             nonlocal d
             parts = item if isinstance(item, list) else [item]
-            parts = [(sec, arena) for sec, arena in parts if sec.shape[0]]
+            parts = [part for part in parts if part[0].shape[0]]  # (a Framed part keeps its floors)
             if not parts and d is None:
                 return False  # (nothing pushed yet: nothing in flight that the framer could overtake)
             if d is None:
@@ -180,7 +224,7 @@ class GpuReplayStateStore:
                     kind = kind or _sniff_value_kind(sec, arena)  # "fixed16", "json" or None (no deliverable record)
                 if kind == "json" and template is None:
                     raise _NotDeviceDecodable("JSON event values need the model's event_json_template")
-                d = DeviceDecoder(template if kind == "json" else None, device=self.engine.device)
+                d = decoder_for(template if kind == "json" else None)
             d.push_async(parts)
             return True
 
@@ -206,71 +250,53 @@ class GpuReplayStateStore:
             if n_keys > n_agg:
                 self.engine.n_agg = n_agg = n_keys  # (grown inside the call)
 
-        try:
-            # device_crc: the batches' CRC-32C is finished on the GPU where their bytes go anyway (SURGE_INGEST_DEVICE_CRC): the framing
-            # threads touch a batch's header, not its bytes
-            # in_place: a fetch response is received into the framer's page-locked slab and framed where it lies (no copy of the sections)
-            framer = (PartitionedFramedFetches(fetches, n_partitions, threads=framing_threads, hold=depth, overlap=overlap, device_crc=device_crc, in_place=in_place)
-                      if n_partitions
-                      else FramedFetches(fetches, overlap=overlap, hold=depth, device_crc=device_crc))
-            with framer as framed, (self.engine.on_own_stream() if two_threads else contextlib.nullcontext()):
-                try:
-                    if two_threads:
-                        # the framer's thread (headers, CRC-32C, transactions of the next fetch), the pipeline's worker (stage 1 of
-                        # up to `depth` fetches ahead) and this one (interning + fold of the oldest push).  The worker asks for
-                        # fetch i + depth only after push i is finished: asking tells the framer that fetch i's arena / slab may
-                        # be framed into again, and a push reads its bytes until then.
-                        with PushPipeline(framed, push, depth) as pipe:
-                            for _ in pipe:
-                                finish_one()
-                                pipe.done()
-                    else:
-                        pending = 0
-                        fetch_iter = iter(framed)
-                        while True:
-                            # the oldest push is finished BEFORE the next fetch is asked for (see above)
-                            if pending == depth:
-                                finish_one()
-                                pending -= 1
-                            item = next(fetch_iter, None)
-                            if item is None:
-                                break
-                            if push(item):
-                                pending += 1
-                        while pending:
+        # device_crc: the batches' CRC-32C is finished on the GPU where their bytes go anyway (SURGE_INGEST_DEVICE_CRC): the framing
+        # threads touch a batch's header, not its bytes
+        # in_place: a fetch response is received into the framer's page-locked slab and framed where it lies (no copy of the sections)
+        framer = (PartitionedFramedFetches(fetches, n_partitions, threads=framing_threads, hold=depth, overlap=overlap, device_crc=device_crc, in_place=in_place,
+                                           start_offsets=start_offsets)
+                  if n_partitions
+                  else FramedFetches(fetches, overlap=overlap, hold=depth, device_crc=device_crc, start_offset=start_offsets))
+        with framer as framed, (self.engine.on_own_stream() if two_threads else contextlib.nullcontext()):
+            try:
+                if two_threads:
+                    # the framer's thread (headers, CRC-32C, transactions of the next fetch), the pipeline's worker (stage 1 of
+                    # up to `depth` fetches ahead) and this one (interning + fold of the oldest push).  The worker asks for
+                    # fetch i + depth only after push i is finished: asking tells the framer that fetch i's arena / slab may
+                    # be framed into again, and a push reads its bytes until then.
+                    with PushPipeline(framed, push, depth) as pipe:
+                        for _ in pipe:
+                            finish_one()
+                            pipe.done()
+                else:
+                    pending = 0
+                    fetch_iter = iter(framed)
+                    while True:
+                        # the oldest push is finished BEFORE the next fetch is asked for (see above)
+                        if pending == depth:
                             finish_one()
                             pending -= 1
-                finally:
-                    if d is not None:  # (an error path: pushes that are enqueued read the framer's slabs until they are finished)
-                        while d.pending:
-                            try:
-                                d.finish()
-                            except Exception:
-                                pass
-                if d is not None:
-                    self.engine.synchronize()
-                counters = framed.counters()
-            if bound_log and d is not None:
-                n_agg = max(n_agg, capacity, d.n_keys)
-                self.engine.pack_staged(n_agg)  # decoded fetches -> ONE bound CSR log
-                self.engine.fold(algo)
+                        item = next(fetch_iter, None)
+                        if item is None:
+                            break
+                        if push(item):
+                            pending += 1
+                    while pending:
+                        finish_one()
+                        pending -= 1
+            finally:
+                if d is not None:  # (an error path: pushes that are enqueued read the framer's slabs until they are finished)
+                    while d.pending:
+                        try:
+                            d.finish()
+                        except Exception:
+                            pass
+            if d is not None:
                 self.engine.synchronize()
-            elif n_agg < 0:  # nothing deliverable in the whole topic
-                n_agg = capacity
-                self.engine.load_csr(np.zeros(n_agg + 1, dtype=np.int64), np.zeros(0, dtype=EVENT_DTYPE))
-                self.engine.fold()
-            keys = KeyTable()
-            if d is not None:
-                for k in d.keys():
-                    keys.intern(k)
-                counters.update(d.counters())
-            self.keys = keys
-        finally:
-            if d is not None:
-                d.close()
-        self.engine.snapshot()  # publishes the host mirror that serves point reads
-        self._restored = True
-        return counters
+            counters = framed.counters()
+            if start_offsets is not None:
+                counters.update(framed.below_start())
+        return counters, n_agg
 
     def restore_from_state_records(self, records, events_tail: Sequence = (), template=None, envelope: str = "none") -> dict:
         """Resume from the compacted *state* topic instead of replaying every event — what the reference's restore does
@@ -343,7 +369,8 @@ class GpuReplayStateStore:
         return {"rows_written": counts[0], "tombstones": counts[1], "refused": counts[2], "reparsed_on_host": counts[3]}
 
     def restore_from_state_topic(self, fetches, n_partitions: int = 0, template=None, events_tail: Sequence = (), framing_threads: int = 4,
-                                 device_crc: bool = True, in_place: bool = True, envelope: str = "none") -> dict:
+                                 device_crc: bool = True, in_place: bool = True, envelope: str = "none", events_fetches=None, events_from=None,
+                                 events_partitions: int = 0) -> dict:
         """``restore_from_state_records`` from what a consumer of the state topic actually receives: ``fetches`` yields the
         topic's bytes — message-format-v2 record batches, LZ4 or uncompressed, transactional, with the producer's flush
         records, tombstones as null values and the offset gaps log compaction leaves — one ``bytes`` per fetch, or with
@@ -351,8 +378,18 @@ class GpuReplayStateStore:
         ``restore_from_fetches``' (``FramedFetches`` / ``PartitionedFramedFetches``, ``read_committed``); a state-mode
         ``DeviceDecoder`` finds the records and interns the ids on the device (up to four pushes in flight; the oldest is
         finished, then loaded: ``load_states_into``) — no per-record work in Python.  The loaded states become the snapshot
-        baseline, then ``events_tail`` is folded on top, exactly as ``restore_from_state_records`` does (``envelope`` as there).  Returns the
-        framer's and the decoder's counters plus the summed decode counts."""
+        baseline, then ``events_tail`` is folded on top, exactly as ``restore_from_state_records`` does (``envelope`` as there).
+        ``events_fetches`` (instead of a non-empty ``events_tail``: both raise ``ValueError``) is the tail as BYTES — what a
+        consumer of the events topic that seeks to ``events_from`` is sent, fetch by fetch, from the batch that contains each
+        first offset on (``events_partitions`` as ``n_partitions``; ``events_from``: one first offset per events partition, or
+        one int, the positions committed with the snapshot — ``PartitionedFramedFetches.positions``).  The state decoder then
+        CONTINUES as the events decoder (``DeviceDecoder.continue_as_events`` with the model's ``event_json_template``, or
+        16-byte fixed events when the values are those): the ids it interned are the resident state's rows, so the tail's
+        events find their aggregates, and new ids are numbered behind them.  The tail runs through ``restore_from_fetches``'
+        loop with the framers started at ``events_from``: records below a first offset are dropped where records are parsed,
+        on the device.  Aggregates that first appear in the tail have the strings ``restore_from_fetches`` gives them (none).
+        Returns the framer's and the decoder's counters plus the summed decode counts; with ``events_fetches`` the tail's own
+        under ``tail_*`` names."""
         import ctypes
 
         import torch
@@ -364,6 +401,16 @@ class GpuReplayStateStore:
         from .schema import EVENT_DTYPE
 
         check_envelope(envelope)
+        if events_fetches is not None and len(events_tail):
+            raise ValueError("events_tail (decoded events) and events_fetches (the tail's bytes) are two ways to hand over the same tail: give one")
+        if events_fetches is None and (events_from is not None or events_partitions):
+            raise ValueError("events_from / events_partitions describe events_fetches: there is none")
+        if events_fetches is not None and events_partitions:
+            events_from = [0] * events_partitions if events_from is None else ([int(events_from)] * events_partitions if np.isscalar(events_from) else list(events_from))
+        elif events_fetches is not None and events_from is not None and not np.isscalar(events_from):
+            if len(events_from) != 1:
+                raise ValueError("one events partition (events_partitions=0) takes one first offset")
+            events_from = int(events_from[0])
         template = template or JsonTemplate.counter()
         eng, lib = self.engine, _native.load()
         eng.load_csr(np.zeros(1, dtype=np.int64), np.zeros(0, dtype=EVENT_DTYPE))
@@ -411,21 +458,34 @@ class GpuReplayStateStore:
                         except Exception:
                             pass
                 counters = framed.counters()
+            counters.update(d.counters())
+            n_agg = d.n_keys
+            if n_agg:  # the loaded states are the snapshot baseline: a publish right after the load has nothing to say
+                d_kind = torch.zeros(n_agg, dtype=torch.uint8, device=torch.device("cuda", eng.device))
+                nv, nt = ctypes.c_int64(), ctypes.c_int64()
+                eng._check(lib.surge_replay_snapshot_delta(eng._h, ctypes.c_void_p(d_kind.data_ptr()), ctypes.byref(nv), ctypes.byref(nt), 1))
+            if events_fetches is not None:  # fold(prev snapshot, new events): the same decoder reads the events behind the snapshot
+                def as_events_decoder(event_template):
+                    d.continue_as_events(event_template)
+                    return d
+
+                state_counts, below_before = d.counters(), d.below_floor()
+                tail, _ = self._fold_fetches(events_fetches, as_events_decoder, n_agg, n_partitions=events_partitions, framing_threads=framing_threads,
+                                             device_crc=device_crc, in_place=in_place, start_offsets=events_from)
+                after = d.counters()
+                tail.update({k: after[k] - state_counts[k] for k in after})
+                tail["below_floor"] = d.below_floor() - below_before
+                tail["records_decoded"] -= tail["below_floor"]  # (the framer counts a floored section's whole recordCount: what the device passed over is neither decoded nor delivered)
+                counters.update({"tail_" + k: v for k, v in tail.items()})
+            if keep:  # (the decoder's buffers go with it — a decoder that went on as an events decoder still has them: the columns are cloned out)
+                self.state_strings = [None if col is None else (col[0].clone(), col[1].clone()) for col in d.state_strings()]
             keys = KeyTable()
             for k in d.keys():
                 keys.intern(k)
-            counters.update(d.counters())
             self.keys = keys
-            if keep:  # (the decoder's buffers go with it: the columns are cloned out)
-                self.state_strings = [None if col is None else (col[0].clone(), col[1].clone()) for col in d.state_strings()]
         finally:
             eng._check(lib.surge_replay_set_decode_base(eng._h, None))
             d.close()
-        n_agg = len(self.keys)
-        if n_agg:
-            d_kind = torch.zeros(n_agg, dtype=torch.uint8, device=torch.device("cuda", eng.device))
-            nv, nt = ctypes.c_int64(), ctypes.c_int64()
-            eng._check(lib.surge_replay_snapshot_delta(eng._h, ctypes.c_void_p(d_kind.data_ptr()), ctypes.byref(nv), ctypes.byref(nt), 1))
         self._restored = True
         if len(events_tail):
             self.apply_events(events_tail)
