@@ -38,6 +38,9 @@ RECORD_DTYPE = np.dtype([("offset", "<i8"), ("agg_idx", "<i8"), ("key_off", "<i8
 assert RECORD_DTYPE.itemsize == 40
 
 
+COUNTER_NAMES = ("batches", "records_decoded", "records_delivered", "records_aborted", "control_batches",
+                 "flush_records_skipped", "bytes_decompressed", "open_transactions")  # surge_ingest_counters / surge_ingest_group_counters
+
 EVJ_NAME, EVJ_MAX_TYPES = 64, 16
 ARG_NONE, ARG_I32, ARG_F64 = 0, 1, 2
 EVJ_ENVELOPES = {"none": 0, "protobuf_event": 1}  # SURGE_EVJ_ENVELOPE_*
@@ -199,9 +202,7 @@ class EventsTopicIngest:
     def counters(self) -> dict:
         c = (ctypes.c_int64 * 8)()
         self._check(self._lib.surge_ingest_counters(self._h, ctypes.byref(c)))
-        names = ["batches", "records_decoded", "records_delivered", "records_aborted", "control_batches",
-                 "flush_records_skipped", "bytes_decompressed", "open_transactions"]
-        return dict(zip(names, [int(x) for x in c]))
+        return dict(zip(COUNTER_NAMES, [int(x) for x in c]))
 
     def drain_sections(self, max_sections: int = 1 << 30) -> Tuple[np.ndarray, int]:
         """FRAMES mode: the records sections of the deliverable batches (``SECTION_DTYPE`` records whose spans point into
@@ -211,30 +212,23 @@ class EventsTopicIngest:
         self._check(self._lib.surge_ingest_drain_sections(self._h, out.shape[0], out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(got)))
         return out[: got.value], int(self._lib.surge_ingest_arena(self._h) or 0)
 
-    def drain_fixed16(self, max_records: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    def _drain_events(self, max_records: Optional[int], drain) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``(agg_idx, events, offsets)`` of up to ``max_records`` ready records: ``drain(n, agg, ev, off, got)`` is the library
+        call that fills the three arrays and says how many records it wrote."""
         n = self.ready if max_records is None else min(self.ready, max_records)
-        agg = np.zeros(n, dtype=np.int64)
-        ev = np.zeros(n, dtype=EVENT_DTYPE)
-        off = np.zeros(n, dtype=np.int64)
+        out = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=EVENT_DTYPE), np.zeros(n, dtype=np.int64)
         got = ctypes.c_int64(0)
-        self._check(self._lib.surge_ingest_drain_fixed16(
-            self._h, n, agg.ctypes.data_as(ctypes.c_void_p), ev.ctypes.data_as(ctypes.c_void_p),
-            off.ctypes.data_as(ctypes.c_void_p), ctypes.byref(got)))
-        return agg[: got.value], ev[: got.value], off[: got.value]
+        self._check(drain(n, *(a.ctypes.data_as(ctypes.c_void_p) for a in out), ctypes.byref(got)))
+        return tuple(a[: got.value] for a in out)
+
+    def drain_fixed16(self, max_records: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        return self._drain_events(max_records, lambda n, *arrays: self._lib.surge_ingest_drain_fixed16(self._h, n, *arrays))
 
     def drain_json(self, template: EventJsonTemplate, max_records: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """``(agg_idx, events, offsets)`` for topics whose record values are JSON events, decoded in the library through the
         model's template (``surge_ingest_drain_json``): no per-record Python."""
-        n = self.ready if max_records is None else min(self.ready, max_records)
-        agg = np.zeros(n, dtype=np.int64)
-        ev = np.zeros(n, dtype=EVENT_DTYPE)
-        off = np.zeros(n, dtype=np.int64)
-        got = ctypes.c_int64(0)
         c = template.to_c()
-        self._check(self._lib.surge_ingest_drain_json(
-            self._h, n, ctypes.byref(c), agg.ctypes.data_as(ctypes.c_void_p), ev.ctypes.data_as(ctypes.c_void_p),
-            off.ctypes.data_as(ctypes.c_void_p), ctypes.byref(got)))
-        return agg[: got.value], ev[: got.value], off[: got.value]
+        return self._drain_events(max_records, lambda n, *arrays: self._lib.surge_ingest_drain_json(self._h, n, ctypes.byref(c), *arrays))
 
     def drain_records(self, max_records: Optional[int] = None) -> List[Tuple[int, int, Optional[bytes], Optional[bytes]]]:
         """``(offset, agg_idx, key, value)`` per record (``None`` for null key / value)."""
@@ -263,54 +257,41 @@ class EventsTopicIngest:
         return kt
 
 
-class FramedFetches:
-    """Frames a sequence of fetches ONE FETCH AHEAD of whoever consumes them: a worker thread runs the host stage
-    (``feed`` = batch headers, CRC-32C, ``read_committed`` — and the fetch itself, when ``fetches`` is a generator that
-    polls) while the caller's thread keeps the device busy with the previous fetch (``DeviceDecoder.push`` + the
-    fold).  One ``EventsTopicIngest`` in FRAMES mode does all the framing, so transactions and partial batches carry
-    from fetch to fetch; its six rotating arenas (``surge_ingest_drain_sections`` in ``surge_ingest.h``) are what
-    makes the overlap safe: the sections of fetch i stay where they are while fetches i + 1 .. i + ``hold`` are framed,
-    and the next one is not started before the consumer has asked for fetch i + ``hold`` (= is done with fetch i).
-    ``hold`` (1 .. 5) is how many fetches the consumer keeps alive at a time: 1 for push-then-fold, 2 .. 5 when it keeps
-    that many ``DeviceDecoder.push_async`` in flight.  ASKING for the next fetch while ``hold`` are held releases the
-    oldest one: a consumer with pushes in flight finishes the oldest push first, then asks (``store.restore_from_fetches``).
+class _FramingAhead:
+    """The one-fetch-ahead protocol both framers keep, written once.  A worker thread takes the items of ``fetches`` and
+    frames them (``_frame(item)``, the subclass's host stage — and the fetch itself, when ``fetches`` is a generator that
+    polls) ONE FETCH AHEAD of whoever iterates.  The native framer rotates through six arenas / slabs, so what fetch i's
+    sections point to stays as it is while fetches i + 1 .. i + ``hold`` are framed: ``hold`` (1 .. 5) is how many fetches
+    the consumer keeps alive at a time, and the worker holds a slot for each of them plus the one it frames.  ASKING for the
+    next fetch while ``hold`` are held is what releases the oldest one's slot — nothing else does: a consumer with pushes in
+    flight finishes the oldest push first, then asks (``pushes_in_flight``, ``PushPipeline``).  The worker's exception is
+    handed over and re-raised in the consumer's thread; ``None`` marks the end and is put back, so a repeated ``next()``
+    raises ``StopIteration`` again.  ``overlap=False`` frames inline (same results, one thread).
 
-    Iterating yields ``(sections, arena_address)`` per fetch, in order.  ``overlap=False`` frames inline (same results,
-    one thread)."""
+    A subclass names its thread (``_thread_name``) and what there are six of (``_six_of``), creates its native handle
+    after ``super().__init__`` and calls ``_start()`` when it is ready to frame; it supplies ``_frame``, ``_close_handle``,
+    ``counters``, ``positions`` and ``below_start``."""
 
-    def __init__(self, fetches, isolation_level: int = READ_COMMITTED, device_lz4: bool = True, overlap: bool = True, threads: int = 1, hold: int = 1,
-                 device_crc: bool = True, start_offset: Optional[int] = None):
+    _thread_name = _six_of = None
+
+    def __init__(self, fetches, overlap: bool, hold: int):
         import queue
         import threading
 
         if not 1 <= hold <= 5:
-            raise ValueError("hold must be 1 .. 5 (the framer has six arenas)")
-        # device_crc needs the sections as they are on the wire: with host-side LZ4 (device_lz4=False) the host has the bytes in hand anyway
-        self._g = EventsTopicIngest(isolation_level, frames=True, device_lz4=device_lz4, threads=threads, device_crc=device_crc and device_lz4,
-                                    start_offset=start_offset)
-        self._started = start_offset is not None  # with a start every item is a Framed: the pair, its floors, the position behind it
+            raise ValueError(f"hold must be 1 .. 5 ({self._six_of})")
         self._fetches = iter(fetches)
-        self._overlap = overlap
-        self._hold = hold
+        self._overlap, self._hold = overlap, hold
         self.framing_seconds: List[float] = []
         self._q: "queue.Queue" = queue.Queue()
         self._slots = threading.Semaphore(hold + 1)  # framed fetches alive at once: the ones being read + the one being framed
         self._stop = False
         self._held = 0
-        self._thread = threading.Thread(target=self._run, name="surge-framing", daemon=True) if overlap else None
+        self._thread = threading.Thread(target=self._run, name=self._thread_name, daemon=True) if overlap else None
+
+    def _start(self):
         if self._thread:
             self._thread.start()
-
-    def _frame(self, data):
-        import time
-
-        t0 = time.perf_counter()
-        self._g.feed(data)
-        item = self._g.drain_sections()
-        if self._started:
-            item = Framed(item[0], item[1], self._g.take_floors(), self._g.positions())
-        self.framing_seconds.append(time.perf_counter() - t0)
-        return item
 
     def _run(self):
         try:
@@ -343,6 +324,58 @@ class FramedFetches:
         self._held += 1
         return item
 
+    def close(self):
+        self._stop = True
+        if self._thread:
+            for _ in range(self._hold + 1):
+                self._slots.release()
+            self._thread.join()
+            self._thread = None
+        self._close_handle()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class FramedFetches(_FramingAhead):
+    """Frames a sequence of fetches one fetch ahead of whoever consumes them (:class:`_FramingAhead`): the worker thread runs
+    the host stage (``feed`` = batch headers, CRC-32C, ``read_committed``) while the caller's thread keeps the device busy
+    with the previous fetch (``DeviceDecoder.push`` + the fold).  One ``EventsTopicIngest`` in FRAMES mode does all the
+    framing, so transactions and partial batches carry from fetch to fetch; its six rotating arenas
+    (``surge_ingest_drain_sections`` in ``surge_ingest.h``) are what makes the overlap safe.  ``hold``: 1 for
+    push-then-fold, 2 .. 5 when the consumer keeps that many ``DeviceDecoder.push_async`` in flight
+    (``store.restore_from_fetches``).
+
+    Iterating yields ``(sections, arena_address)`` per fetch, in order."""
+
+    _thread_name, _six_of = "surge-framing", "the framer has six arenas"
+
+    def __init__(self, fetches, isolation_level: int = READ_COMMITTED, device_lz4: bool = True, overlap: bool = True, threads: int = 1, hold: int = 1,
+                 device_crc: bool = True, start_offset: Optional[int] = None):
+        super().__init__(fetches, overlap, hold)
+        # device_crc needs the sections as they are on the wire: with host-side LZ4 (device_lz4=False) the host has the bytes in hand anyway
+        self._g = EventsTopicIngest(isolation_level, frames=True, device_lz4=device_lz4, threads=threads, device_crc=device_crc and device_lz4,
+                                    start_offset=start_offset)
+        self._started = start_offset is not None  # with a start every item is a Framed: the pair, its floors, the position behind it
+        self._start()
+
+    def _frame(self, data):
+        import time
+
+        t0 = time.perf_counter()
+        self._g.feed(data)
+        item = self._g.drain_sections()
+        if self._started:
+            item = Framed(item[0], item[1], self._g.take_floors(), self._g.positions())
+        self.framing_seconds.append(time.perf_counter() - t0)
+        return item
+
+    def _close_handle(self):
+        self._g.close()
+
     def counters(self) -> dict:
         """The ingest counters; call it when the iteration has ended (the handle belongs to the framing thread)."""
         return self._g.counters()
@@ -354,23 +387,8 @@ class FramedFetches:
     def below_start(self) -> dict:
         return self._g.below_start()
 
-    def close(self):
-        self._stop = True
-        if self._thread:
-            for _ in range(self._hold + 1):
-                self._slots.release()
-            self._thread.join()
-            self._thread = None
-        self._g.close()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-
-class PartitionedFramedFetches:
+class PartitionedFramedFetches(_FramingAhead):
     """The same one-fetch-ahead framing for a consumer that is assigned several partitions: ``fetches`` yields, per fetch
     response, the next bytes of every partition (a sequence of ``bytes`` / ``None``, always in the same partition order).
     A ``surge_ingest_group`` frames them: one framer per partition — transactions, last stable offsets and cut batches are
@@ -380,28 +398,22 @@ class PartitionedFramedFetches:
     inside a partition: one ``DeviceDecoder.push_async``, one host-to-device copy.  ``hold`` as in :class:`FramedFetches`
     (the group rotates through six slabs)."""
 
+    _thread_name, _six_of = "surge-framing-driver", "the group has six slabs"
+
     def __init__(self, fetches, n_partitions: int, threads: int = 8, hold: int = 3, isolation_level: int = READ_COMMITTED, device_lz4: bool = True,
                  overlap: bool = True, device_crc: bool = True, in_place: bool = False, start_offsets=None):
-        import queue
-        import threading
-
-        if not 1 <= hold <= 5:
-            raise ValueError("hold must be 1 .. 5 (the group has six slabs)")
+        super().__init__(fetches, overlap, hold)
         if start_offsets is not None and len(start_offsets) != n_partitions:
             raise ValueError(f"start_offsets holds {len(start_offsets)} entries for {n_partitions} partitions (<= 0: a partition without a start)")
         self._lib = _native.load()
         self._h = ctypes.c_void_p()
-        rc = self._lib.surge_ingest_group_create(n_partitions, isolation_level | (DEVICE_LZ4 if device_lz4 else 0) | (DEVICE_CRC if device_crc and device_lz4 else 0),
-                                                 ctypes.byref(self._h))
-        if rc != 0:
-            raise IngestError(rc, (self._lib.surge_ingest_group_last_error(None) or b"").decode())
+        self._check(self._lib.surge_ingest_group_create(n_partitions, isolation_level | (DEVICE_LZ4 if device_lz4 else 0) | (DEVICE_CRC if device_crc and device_lz4 else 0),
+                                                        ctypes.byref(self._h)))
         if os.environ.get("SURGE_INGEST_PAGEABLE_ARENA") != "1":
             self._lib.surge_ingest_group_use_pinned_slabs(self._h)  # (fails without a GPU: the slabs stay pageable, which works too)
         self._started = start_offsets is not None
         if self._started:
-            rc = self._lib.surge_ingest_group_set_start_offsets(self._h, (ctypes.c_int64 * n_partitions)(*[int(o) for o in start_offsets]))
-            if rc != 0:
-                raise IngestError(rc, (self._lib.surge_ingest_group_last_error(self._h) or b"").decode())
+            self._check(self._lib.surge_ingest_group_set_start_offsets(self._h, (ctypes.c_int64 * n_partitions)(*[int(o) for o in start_offsets])))
         self._threads = max(1, min(threads, n_partitions))
         # in_place: the fetch response is RECEIVED into the group's next page-locked slab (surge_ingest_group_receive_copy: one copy out of
         # the bytes objects on the framing threads, standing in for the socket reads a consumer would aim there) and framed
@@ -410,17 +422,12 @@ class PartitionedFramedFetches:
         self.receive_seconds: List[float] = []      # wall time of that stand-in receive copy, per fetch
         self._n = n_partitions
         self._tails = [b""] * n_partitions
-        self._fetches = iter(fetches)
-        self._overlap, self._hold = overlap, hold
-        self.framing_seconds: List[float] = []
         self._ring = [None] * (hold + 2)  # section tables, reused (the consumer keeps `hold` fetches alive while the next is framed)
-        self._q: "queue.Queue" = queue.Queue()
-        self._slots = threading.Semaphore(hold + 1)
-        self._stop = False
-        self._held = 0
-        self._thread = threading.Thread(target=self._run, name="surge-framing-driver", daemon=True) if overlap else None
-        if self._thread:
-            self._thread.start()
+        self._start()
+
+    def _check(self, rc: int):
+        if rc != 0:  # (a group that was not created has a null handle: the library's message of the failed create)
+            raise IngestError(rc, (self._lib.surge_ingest_group_last_error(self._h) or b"").decode())
 
     def _frame(self, fetch):
         """One library call per fetch (``surge_ingest_group_feed``): no per-partition Python."""
@@ -440,9 +447,7 @@ class PartitionedFramedFetches:
             tr = time.perf_counter()
             src_arr = (ctypes.c_void_p * n)(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) if b else None for b in bufs])
             data_arr = (ctypes.c_void_p * n)()
-            rc = self._lib.surge_ingest_group_receive_copy(self._h, src_arr, len_arr, self._threads, data_arr)
-            if rc != 0:
-                raise IngestError(rc, (self._lib.surge_ingest_group_last_error(self._h) or b"").decode())
+            self._check(self._lib.surge_ingest_group_receive_copy(self._h, src_arr, len_arr, self._threads, data_arr))
             self.receive_seconds.append(time.perf_counter() - tr)
             t0 = time.perf_counter()  # (framing_seconds: the framing proper)
         else:
@@ -464,8 +469,7 @@ class PartitionedFramedFetches:
                 max_sec = int(n_sec.value)
                 continue
             break
-        if rc != 0:  # all or nothing: the group is what it was before the call (the tails too)
-            raise IngestError(rc, (self._lib.surge_ingest_group_last_error(self._h) or b"").decode())
+        self._check(rc)  # all or nothing: the group is what it was before the call (the tails too)
         self._tails = [bufs[p][consumed[p]:] for p in range(n)]
         item = secs[: n_sec.value], int(slab.value or 0)
         if self._started:
@@ -475,10 +479,6 @@ class PartitionedFramedFetches:
             item = Framed(item[0], item[1], floors[: got.value], self.positions())
         self.framing_seconds.append(time.perf_counter() - t0)
         return item
-
-    _run = FramedFetches._run
-    __iter__ = FramedFetches.__iter__
-    __next__ = FramedFetches.__next__
 
     def slab_bytes(self):
         """``(bytes, page_locked)``: what the group's six slabs take (``surge_ingest_group_slab_bytes``)."""
@@ -508,26 +508,35 @@ class PartitionedFramedFetches:
         """The partitions' ingest counters, summed; call it when the iteration has ended."""
         c = (ctypes.c_int64 * 8)()
         self._lib.surge_ingest_group_counters(self._h, ctypes.byref(c))
-        names = ["batches", "records_decoded", "records_delivered", "records_aborted", "control_batches",
-                 "flush_records_skipped", "bytes_decompressed", "open_transactions"]
-        return dict(zip(names, [int(x) for x in c]))
+        return dict(zip(COUNTER_NAMES, [int(x) for x in c]))
 
-    def close(self):
-        self._stop = True
-        if self._thread:
-            for _ in range(self._hold + 1):
-                self._slots.release()
-            self._thread.join()
-            self._thread = None
+    def _close_handle(self):
         if self._h:
             self._lib.surge_ingest_group_destroy(self._h)
             self._h = ctypes.c_void_p()
 
-    def __enter__(self):
-        return self
 
-    def __exit__(self, *exc):
-        self.close()
+def pushes_in_flight(framed, push, depth: int):
+    """The one-thread way to keep up to ``depth`` pushes in flight over a framer made with ``hold=depth``: ``push(item)`` is
+    called for every fetch of ``framed`` (a falsy return = nothing was pushed for that fetch: it takes no slot), and the
+    generator yields each time the caller has to finish the OLDEST push — before it asks ``framed`` for the next fetch when
+    ``depth`` are pending (asking is what lets the framer reuse the oldest fetch's slab, and a push reads its bytes until it is
+    finished), and once per push still pending at the end: ``for _ in pushes_in_flight(framed, push, depth): finish_one()``.
+    ``PushPipeline`` is the same protocol with the pushes on a worker thread."""
+    pending = 0
+    fetches = iter(framed)
+    while True:
+        if pending == depth:
+            yield
+            pending -= 1
+        item = next(fetches, None)
+        if item is None:
+            break
+        if push(item):
+            pending += 1
+    while pending:
+        yield
+        pending -= 1
 
 
 class PushPipeline:
@@ -537,7 +546,8 @@ class PushPipeline:
     while the caller's thread finishes the oldest push and folds it.  Iterating yields once per enqueued push (whatever
     ``push`` returned; a falsy return = nothing was pushed for that fetch, nothing is yielded); the caller finishes that
     push and calls ``done()``.  The worker asks ``source`` for fetch i + depth only after ``done()`` for fetch i — asking is
-    what lets the framer reuse fetch i's slab.  ``threaded=False``: the same protocol inline, one push at a time."""
+    what lets the framer reuse fetch i's slab.  ``threaded=False``: the same protocol inline on the caller's thread — every
+    ``next()`` takes one of the ``depth`` permits (``RuntimeError`` when none is left) and every ``done()`` returns one."""
 
     def __init__(self, source, push, depth: int, threaded: bool = True):
         import queue
@@ -621,6 +631,15 @@ class PushPipeline:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def _device_view(ptr, shape, typestr: str, dev):
+    """A CUDA tensor over ``shape`` elements of ``typestr`` at the device address ``ptr`` holds (``__cuda_array_interface__``:
+    no copy, the memory stays its owner's)."""
+    import torch
+
+    iface = {"shape": shape, "typestr": typestr, "data": (ptr.value, False), "version": 2}
+    return torch.as_tensor(type("_Span", (), {"__cuda_array_interface__": iface})(), device=dev)
 
 
 class DeviceDecoder:
@@ -788,13 +807,7 @@ class DeviceDecoder:
         if n.value == 0:
             z = torch.zeros(0, dtype=torch.int64, device=dev)
             return z, torch.zeros((0, 2), dtype=torch.int64, device=dev), z.clone(), nk.value
-
-        def view(ptr, count, cols):
-            iface = {"shape": (count, cols) if cols > 1 else (count,), "typestr": "<i8", "data": (ptr.value, False), "version": 2}
-            holder = type("_Span", (), {"__cuda_array_interface__": iface})()
-            return torch.as_tensor(holder, device=dev)
-
-        return view(pa, n.value, 1), view(pe, n.value, 2), view(po, n.value, 1), nk.value
+        return _device_view(pa, (n.value,), "<i8", dev), _device_view(pe, (n.value, 2), "<i8", dev), _device_view(po, (n.value,), "<i8", dev), nk.value
 
     def state_result(self):
         """A state decoder's records since the last clear: ``(agg_idx, values, value_off, offsets, n_keys)`` — CUDA tensors
@@ -811,16 +824,11 @@ class DeviceDecoder:
         z = torch.zeros(0, dtype=torch.int64, device=dev)
         if n.value == 0:
             return z, torch.zeros(0, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int64, device=dev), z.clone(), nk.value
-
-        def view(ptr, count, typestr):
-            iface = {"shape": (count,), "typestr": typestr, "data": (ptr.value, False), "version": 2}
-            return torch.as_tensor(type("_Span", (), {"__cuda_array_interface__": iface})(), device=dev)
-
         torch.cuda.synchronize(dev)  # (a finish(wait=False) leaves the arrays complete in stream order only)
-        value_off = view(pvo, n.value + 1, "<i8")
+        value_off = _device_view(pvo, (n.value + 1,), "<i8", dev)
         total = int(value_off[-1].item())
-        values = view(pv, total, "|u1") if total else torch.zeros(0, dtype=torch.uint8, device=dev)
-        return view(pa, n.value, "<i8"), values, value_off, view(po, n.value, "<i8"), nk.value
+        values = _device_view(pv, (total,), "|u1", dev) if total else torch.zeros(0, dtype=torch.uint8, device=dev)
+        return _device_view(pa, (n.value,), "<i8", dev), values, value_off, _device_view(po, (n.value,), "<i8", dev), nk.value
 
     def load_states_into(self, engine, template, envelope: str = "none"):
         """A state decoder's hand-over (``surge_device_decoder_load_states``; ``envelope="protobuf_state"``:
@@ -851,11 +859,6 @@ class DeviceDecoder:
         from .encode import STRING_COLUMNS
 
         dev = torch.device("cuda", self.device)
-
-        def view(ptr, count, typestr):
-            iface = {"shape": (count,), "typestr": typestr, "data": (ptr.value, False), "version": 2}
-            return torch.as_tensor(type("_Span", (), {"__cuda_array_interface__": iface})(), device=dev)
-
         cols = []
         for c in range(STRING_COLUMNS):
             pu, po, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64()
@@ -863,9 +866,9 @@ class DeviceDecoder:
             if not po.value:
                 cols.append(None)
                 continue
-            d_off = view(po, n.value + 1, "<i8")
+            d_off = _device_view(po, (n.value + 1,), "<i8", dev)
             total = int(d_off[-1].item())
-            cols.append((view(pu, total, "|u1") if total else torch.zeros(0, dtype=torch.uint8, device=dev), d_off))
+            cols.append((_device_view(pu, (total,), "|u1", dev) if total else torch.zeros(0, dtype=torch.uint8, device=dev), d_off))
         return cols
 
     def clear(self) -> None:

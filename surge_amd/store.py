@@ -54,6 +54,46 @@ class GpuReplayStateStore:
     def close(self):
         self.engine.close()
 
+    def _bind_all_none(self, n_agg: int) -> None:
+        """The resident state becomes ``n_agg`` aggregates, every one None (an empty log, folded)."""
+        from .schema import EVENT_DTYPE
+
+        self.engine.load_csr(np.zeros(n_agg + 1, dtype=np.int64), np.zeros(0, dtype=EVENT_DTYPE))
+        self.engine.fold()
+
+    def _loaded_is_baseline(self, n_agg: int) -> None:
+        """What was loaded is the snapshot baseline: a publish right after the load has nothing to say."""
+        import ctypes
+
+        import torch
+
+        if n_agg:
+            eng = self.engine
+            d_kind = torch.zeros(n_agg, dtype=torch.uint8, device=torch.device("cuda", eng.device))
+            nv, nt = ctypes.c_int64(), ctypes.c_int64()
+            eng._check(eng._lib.surge_replay_snapshot_delta(eng._h, ctypes.c_void_p(d_kind.data_ptr()), ctypes.byref(nv), ctypes.byref(nt), 1))
+
+    def _adopt_keys_of(self, decoder) -> None:
+        """The host key table is the device decoder's (``None``: no decoder was made, no id was met)."""
+        keys = KeyTable()
+        for k in (decoder.keys() if decoder is not None else ()):
+            keys.intern(k)
+        self.keys = keys
+
+    @contextlib.contextmanager
+    def _decoding_onto_the_defaults(self):
+        """Inside the block the bytes a decoded state's template does not name are the algebra's defaults
+        (``surge_replay_set_decode_base``); zeros again on the way out."""
+        import ctypes
+
+        eng = self.engine
+        defaults = self.model.event_algebra().to_c().default_state
+        eng._check(eng._lib.surge_replay_set_decode_base(eng._h, ctypes.byref(defaults)))
+        try:
+            yield
+        finally:
+            eng._check(eng._lib.surge_replay_set_decode_base(eng._h, None))
+
     # -- recovery ---------------------------------------------------------------------------
     def restore(self, events_in_offset_order: Sequence, prior: Optional[Dict[str, object]] = None,
                 capacity: int = 0, algo: int = ALGO_AUTO) -> None:
@@ -124,8 +164,7 @@ class GpuReplayStateStore:
         # host-side sort of the whole topic.
         n_agg = max(len(keys), capacity)
         self.keys = keys
-        self.engine.load_csr(np.zeros(n_agg + 1, dtype=np.int64), np.zeros(0, dtype=EVENT_DTYPE))
-        self.engine.fold()  # every aggregate None; `algo` only names kernels for bound logs (restore / restore_log)
+        self._bind_all_none(n_agg)  # `algo` only names kernels for bound logs (restore / restore_log)
         if events.shape[0]:
             self.engine.append_events(agg_idx, events)
         self.engine.snapshot()  # publishes the host mirror that serves point reads
@@ -157,8 +196,6 @@ class GpuReplayStateStore:
         Needs values the device decoder reads (16-byte fixed events, or JSON with the model's
         ``event_json_template``); returns the ingest + decoder counters."""
         from .ingest import DeviceDecoder
-        from .log import KeyTable
-        from .schema import EVENT_DTYPE
 
         made = []  # the decoder, made for the first fetch with a record in it
 
@@ -176,15 +213,10 @@ class GpuReplayStateStore:
                 self.engine.fold(algo)
                 self.engine.synchronize()
             elif n_agg < 0:  # nothing deliverable in the whole topic
-                n_agg = capacity
-                self.engine.load_csr(np.zeros(n_agg + 1, dtype=np.int64), np.zeros(0, dtype=EVENT_DTYPE))
-                self.engine.fold()
-            keys = KeyTable()
+                self._bind_all_none(capacity)
+            self._adopt_keys_of(d)
             if d is not None:
-                for k in d.keys():
-                    keys.intern(k)
                 counters.update(d.counters())
-            self.keys = keys
         finally:
             if made:
                 made[0].close()
@@ -202,8 +234,7 @@ class GpuReplayStateStore:
         all None).  ``start_offsets``: per partition (a single int without ``n_partitions``) where the consumer begins
         (``surge_ingest_set_start_offset``): the framers drop what lies below, the floors of the straddling batches travel
         with the pushes.  Returns ``(the framer's counters, n_agg)``."""
-        from .ingest import FramedFetches, PartitionedFramedFetches, PushPipeline
-        from .schema import EVENT_DTYPE
+        from .ingest import PushPipeline, pushes_in_flight
 
         template = self.model.event_json_template()
         d = None
@@ -239,8 +270,7 @@ class GpuReplayStateStore:
                 return
             if n_agg < 0:
                 n_agg = capacity
-                self.engine.load_csr(np.zeros(n_agg + 1, dtype=np.int64), np.zeros(0, dtype=EVENT_DTYPE))
-                self.engine.fold()  # every aggregate None
+                self._bind_all_none(n_agg)
             # No host wait behind the fold: the decoder's stream and the engine's are ordered by events, so the next push is
             # enqueued — and, with two threads (no wait behind the interning either), the next fetch interned — beside this
             # one's group-by and fold (one thread: 7.7 -> 8.7e8 events/s, profiles/r06_e2e_consumer_waits_queues2.txt).  What a
@@ -250,15 +280,9 @@ class GpuReplayStateStore:
             if n_keys > n_agg:
                 self.engine.n_agg = n_agg = n_keys  # (grown inside the call)
 
-        # device_crc: the batches' CRC-32C is finished on the GPU where their bytes go anyway (SURGE_INGEST_DEVICE_CRC): the framing
-        # threads touch a batch's header, not its bytes
-        # in_place: a fetch response is received into the framer's page-locked slab and framed where it lies (no copy of the sections)
-        framer = (PartitionedFramedFetches(fetches, n_partitions, threads=framing_threads, hold=depth, overlap=overlap, device_crc=device_crc, in_place=in_place,
-                                           start_offsets=start_offsets)
-                  if n_partitions
-                  else FramedFetches(fetches, overlap=overlap, hold=depth, device_crc=device_crc, start_offset=start_offsets))
+        framer = _framer(fetches, n_partitions, framing_threads, depth, overlap, device_crc, in_place, start_offsets)
         with framer as framed, (self.engine.on_own_stream() if two_threads else contextlib.nullcontext()):
-            try:
+            with _pushes_finished_on_the_way_out(lambda: d):
                 if two_threads:
                     # the framer's thread (headers, CRC-32C, transactions of the next fetch), the pipeline's worker (stage 1 of
                     # up to `depth` fetches ahead) and this one (interning + fold of the oldest push).  The worker asks for
@@ -268,29 +292,9 @@ class GpuReplayStateStore:
                         for _ in pipe:
                             finish_one()
                             pipe.done()
-                else:
-                    pending = 0
-                    fetch_iter = iter(framed)
-                    while True:
-                        # the oldest push is finished BEFORE the next fetch is asked for (see above)
-                        if pending == depth:
-                            finish_one()
-                            pending -= 1
-                        item = next(fetch_iter, None)
-                        if item is None:
-                            break
-                        if push(item):
-                            pending += 1
-                    while pending:
+                else:  # the same on one thread: the oldest push is finished BEFORE the next fetch is asked for
+                    for _ in pushes_in_flight(framed, push, depth):
                         finish_one()
-                        pending -= 1
-            finally:
-                if d is not None:  # (an error path: pushes that are enqueued read the framer's slabs until they are finished)
-                    while d.pending:
-                        try:
-                            d.finish()
-                        except Exception:
-                            pass
             if d is not None:
                 self.engine.synchronize()
             counters = framed.counters()
@@ -311,13 +315,9 @@ class GpuReplayStateStore:
         ``envelope="protobuf_state"``: the values are what a multilanguage (SDK) application stores, the protobuf
         ``State{aggregateId, payload}`` message around the template's text (``GenericSurgeCommandBusinessLogic.scala:25-27,
         36-39``); any other field, order or repetition is refused, not skipped.  Returns the decoder's counts."""
-        import ctypes
-
         import torch
 
-        from . import _native
         from .encode import STRING_COLUMNS, JsonTemplate, check_envelope, decode_states, key_table_utf8, merge_state_strings
-        from .schema import EVENT_DTYPE
 
         check_envelope(envelope)
         template = template or JsonTemplate.counter()
@@ -331,9 +331,8 @@ class GpuReplayStateStore:
             values.append(value)
             lens.append(len(value))
         n_agg, n_rec = len(self.keys), len(agg_idx)
-        eng, lib = self.engine, _native.load()
-        eng.load_csr(np.zeros(1, dtype=np.int64), np.zeros(0, dtype=EVENT_DTYPE))
-        eng.fold()  # no aggregate yet ...
+        eng = self.engine
+        self._bind_all_none(0)  # no aggregate yet ...
         eng.grow(n_agg)  # ... then every interned id, None
         counts = (0, 0, 0, 0)
         dev = torch.device("cuda", eng.device)
@@ -343,24 +342,17 @@ class GpuReplayStateStore:
             data, key_off = key_table_utf8(self.keys.keys)
             to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
             d_values = to_dev(np.frombuffer(b"".join(values), dtype=np.uint8).copy()) if off[-1] else torch.zeros(0, dtype=torch.uint8, device=dev)
-            defaults = self.model.event_algebra().to_c().default_state
-            eng._check(lib.surge_replay_set_decode_base(eng._h, ctypes.byref(defaults)))
             d_off, d_agg = to_dev(off), to_dev(np.asarray(agg_idx, dtype=np.int64))
-            try:
+            with self._decoding_onto_the_defaults():
                 res = decode_states(eng, template, d_values, d_off, to_dev(data), to_dev(key_off), d_agg,
                                     out=eng.device_state(), want_spans=bool(str_columns), raise_on_refused=True, envelope=envelope)
-            finally:
-                eng._check(lib.surge_replay_set_decode_base(eng._h, None))
             counts = res[2]
             if str_columns:  # the STR fields the values carry, kept beside the rows
                 self.state_strings = [merge_state_strings(eng, c, d_values, d_off, d_agg, res[1], res.spans, n_agg=n_agg) if c in str_columns else None
                                       for c in range(STRING_COLUMNS)]
         if str_columns and self.state_strings is None:
             self.state_strings = [merge_state_strings(eng, c, n_agg=n_agg) if c in str_columns else None for c in range(STRING_COLUMNS)]
-        if n_agg:
-            d_kind = torch.zeros(n_agg, dtype=torch.uint8, device=dev)
-            nv, nt = ctypes.c_int64(), ctypes.c_int64()
-            eng._check(lib.surge_replay_snapshot_delta(eng._h, ctypes.c_void_p(d_kind.data_ptr()), ctypes.byref(nv), ctypes.byref(nt), 1))
+        self._loaded_is_baseline(n_agg)
         self._restored = True
         if len(events_tail):
             self.apply_events(events_tail)  # grows for new ids, group-by + fold on the device, refreshes the mirror
@@ -390,15 +382,8 @@ class GpuReplayStateStore:
         on the device.  Aggregates that first appear in the tail have the strings ``restore_from_fetches`` gives them (none).
         Returns the framer's and the decoder's counters plus the summed decode counts; with ``events_fetches`` the tail's own
         under ``tail_*`` names."""
-        import ctypes
-
-        import torch
-
-        from . import _native
         from .encode import JsonTemplate, check_envelope
-        from .ingest import DeviceDecoder, FramedFetches, PartitionedFramedFetches
-        from .log import KeyTable
-        from .schema import EVENT_DTYPE
+        from .ingest import DeviceDecoder, pushes_in_flight
 
         check_envelope(envelope)
         if events_fetches is not None and len(events_tail):
@@ -412,58 +397,32 @@ class GpuReplayStateStore:
                 raise ValueError("one events partition (events_partitions=0) takes one first offset")
             events_from = int(events_from[0])
         template = template or JsonTemplate.counter()
-        eng, lib = self.engine, _native.load()
-        eng.load_csr(np.zeros(1, dtype=np.int64), np.zeros(0, dtype=EVENT_DTYPE))
-        eng.fold()  # no aggregate yet: the loads grow the state for the ids they meet
+        eng = self.engine
+        self._bind_all_none(0)  # no aggregate yet: the loads grow the state for the ids they meet
         depth = 4
         totals = [0, 0, 0, 0]
         self.state_strings = None
         keep = bool(_str_columns(template))  # the STR fields the values carry are kept beside the rows (a template without them pays nothing)
-        d = DeviceDecoder(states=True, device=eng.device, keep_strings=keep)
-        defaults = self.model.event_algebra().to_c().default_state
-        try:
-            eng._check(lib.surge_replay_set_decode_base(eng._h, ctypes.byref(defaults)))
+        with DeviceDecoder(states=True, device=eng.device, keep_strings=keep) as d, self._decoding_onto_the_defaults():
+            def push(item):
+                parts = [(sec, arena) for sec, arena in (item if isinstance(item, list) else [item]) if sec.shape[0]]
+                if parts:
+                    d.push_async(parts)
+                return bool(parts)
 
             def finish_one():
                 d.finish()
                 for i, c in enumerate(d.load_states_into(eng, template, envelope=envelope)):
                     totals[i] += c
 
-            framer = (PartitionedFramedFetches(fetches, n_partitions, threads=framing_threads, hold=depth, overlap=True, device_crc=device_crc, in_place=in_place)
-                      if n_partitions
-                      else FramedFetches(fetches, overlap=True, hold=depth, device_crc=device_crc))
-            with framer as framed:
-                try:
-                    pending = 0
-                    fetch_iter = iter(framed)
-                    while True:
-                        if pending == depth:  # the oldest push is finished BEFORE the next fetch is asked for (its slab is framed into again)
-                            finish_one()
-                            pending -= 1
-                        item = next(fetch_iter, None)
-                        if item is None:
-                            break
-                        parts = item if isinstance(item, list) else [item]
-                        parts = [(sec, arena) for sec, arena in parts if sec.shape[0]]
-                        if parts:
-                            d.push_async(parts)
-                            pending += 1
-                    while pending:
+            with _framer(fetches, n_partitions, framing_threads, depth, True, device_crc, in_place) as framed:
+                with _pushes_finished_on_the_way_out(lambda: d):
+                    for _ in pushes_in_flight(framed, push, depth):  # the oldest push is finished, then loaded, BEFORE the next fetch is asked for
                         finish_one()
-                        pending -= 1
-                finally:
-                    while d.pending:  # (an error path: pushes that are enqueued read the framer's slabs until they are finished)
-                        try:
-                            d.finish()
-                        except Exception:
-                            pass
                 counters = framed.counters()
             counters.update(d.counters())
             n_agg = d.n_keys
-            if n_agg:  # the loaded states are the snapshot baseline: a publish right after the load has nothing to say
-                d_kind = torch.zeros(n_agg, dtype=torch.uint8, device=torch.device("cuda", eng.device))
-                nv, nt = ctypes.c_int64(), ctypes.c_int64()
-                eng._check(lib.surge_replay_snapshot_delta(eng._h, ctypes.c_void_p(d_kind.data_ptr()), ctypes.byref(nv), ctypes.byref(nt), 1))
+            self._loaded_is_baseline(n_agg)
             if events_fetches is not None:  # fold(prev snapshot, new events): the same decoder reads the events behind the snapshot
                 def as_events_decoder(event_template):
                     d.continue_as_events(event_template)
@@ -479,13 +438,7 @@ class GpuReplayStateStore:
                 counters.update({"tail_" + k: v for k, v in tail.items()})
             if keep:  # (the decoder's buffers go with it — a decoder that went on as an events decoder still has them: the columns are cloned out)
                 self.state_strings = [None if col is None else (col[0].clone(), col[1].clone()) for col in d.state_strings()]
-            keys = KeyTable()
-            for k in d.keys():
-                keys.intern(k)
-            self.keys = keys
-        finally:
-            eng._check(lib.surge_replay_set_decode_base(eng._h, None))
-            d.close()
+            self._adopt_keys_of(d)
         self._restored = True
         if len(events_tail):
             self.apply_events(events_tail)
@@ -645,6 +598,36 @@ class GpuReplayPersistencePlugin:
 
     def create_supplier(self, store_name: str) -> GpuReplayKeyValueStore:
         return GpuReplayKeyValueStore(store_name, self.recovered)
+
+
+def _framer(fetches, n_partitions: int, framing_threads: int, depth: int, overlap: bool, device_crc: bool, in_place: bool, start_offsets=None):
+    """The framer of a recovery that keeps ``depth`` pushes in flight: a group of ``n_partitions`` framers, or one (0).
+    device_crc: the batches' CRC-32C is finished on the GPU where their bytes go anyway (SURGE_INGEST_DEVICE_CRC): the framing
+    threads touch a batch's header, not its bytes.  in_place: a fetch response is received into the framer's page-locked slab
+    and framed where it lies (no copy of the sections)."""
+    from .ingest import FramedFetches, PartitionedFramedFetches
+
+    if n_partitions:
+        return PartitionedFramedFetches(fetches, n_partitions, threads=framing_threads, hold=depth, overlap=overlap, device_crc=device_crc, in_place=in_place,
+                                        start_offsets=start_offsets)
+    return FramedFetches(fetches, overlap=overlap, hold=depth, device_crc=device_crc, start_offset=start_offsets)
+
+
+@contextlib.contextmanager
+def _pushes_finished_on_the_way_out(decoder_if_any):
+    """However the block ends, no push is left in flight behind it: pushes that are enqueued read the framer's slabs until
+    they are finished (an error path; nothing is pending after a loop that ran to its end).  ``decoder_if_any()``: the
+    decoder, or ``None`` while none has been made."""
+    try:
+        yield
+    finally:
+        d = decoder_if_any()
+        if d is not None:
+            while d.pending:
+                try:
+                    d.finish()
+                except Exception:
+                    pass
 
 
 class _NotDeviceDecodable(ValueError):

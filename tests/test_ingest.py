@@ -777,6 +777,146 @@ def test_push_pipeline_runs_pushes_on_its_worker_at_most_depth_ahead_and_in_orde
     assert got == 2
 
 
+def test_pushes_in_flight_asks_for_item_i_plus_depth_only_after_push_i_was_finished():
+    """The one-thread form of the same protocol (``store``'s recoveries): the generator yields when the oldest push has to be
+    finished — item i + depth of the source is asked for only after push i was finished, items whose push returns a falsy value
+    take no slot, pushes are finished in source order, and every push still pending at the end is yielded."""
+    from surge_amd.ingest import pushes_in_flight
+
+    depth = 3
+    asked, pushed, finished = [], [], []
+
+    def source():
+        for i in range(20):
+            asked.append((i, len(finished)))
+            yield i
+
+    def push(i):
+        if i % 5 == 4:
+            return False  # (an empty fetch)
+        pushed.append(i)
+        return True
+
+    for _ in pushes_in_flight(source(), push, depth):
+        assert len(pushed) - len(finished) <= depth
+        finished.append(pushed[len(finished)])  # (finish the oldest)
+    kept = [i for i in range(20) if i % 5 != 4]
+    assert finished == pushed == kept and [i for i, _ in asked] == list(range(20))
+    for i, n_done in asked:  # when item i was asked for, all but at most depth - 1 of the pushes before it were finished ...
+        before = sum(1 for j in range(i) if j % 5 != 4)
+        assert before - n_done <= depth - 1, (i, n_done)
+        assert n_done == max(0, before - (depth - 1))  # ... and none sooner than it had to be: depth pushes are kept in flight
+    # the drain: a source shorter than depth is pushed whole, then yielded push by push
+    log = []
+    for _ in pushes_in_flight(iter(range(2)), lambda i: log.append(("push", i)) or True, depth):
+        log.append("finish")
+    assert log == [("push", 0), ("push", 1), "finish", "finish"]
+    assert list(pushes_in_flight(iter(range(4)), lambda i: False, 1)) == []  # nothing pushed: nothing to finish
+
+    def bad_push(i):
+        if i == 3:
+            raise ValueError("push 3 failed")
+        return True
+
+    got = 0
+    with pytest.raises(ValueError, match="push 3 failed"):  # a push's exception comes straight out, the pushes before it finished or pending
+        for _ in pushes_in_flight(iter(range(10)), bad_push, 2):
+            got += 1
+    assert got == 2  # (pushes 0 and 1 were finished to make room for pushes 2 and 3)
+
+
+def _framing_classes():
+    from surge_amd.ingest import FramedFetches, PartitionedFramedFetches
+
+    return [FramedFetches, PartitionedFramedFetches]
+
+
+def _small_fetches(cls, n, fail_at=None):
+    """``n`` fetch responses of two partitions (one for ``FramedFetches``), one five-record batch per partition each: fetch
+    i's batches begin at offset 5 i.  Asked for item ``fail_at`` the generator raises instead."""
+    partitioned = cls.__name__ == "PartitionedFramedFetches"
+    for i in range(n):
+        if i == fail_at:
+            raise ValueError(f"fetch {i}")
+        row = [kw.record_batch(5 * i, [(b"k%d:%d" % (p, j), counter_event(S.EVT_INC, 5 * i + j + 1, 1)) for j in range(5)]) for p in range(2)]
+        yield row if partitioned else row[0]
+
+
+def _framer_of(cls, fetches, **kw_):
+    return cls(fetches, 2, threads=2, device_crc=False, **kw_) if cls.__name__ == "PartitionedFramedFetches" else cls(fetches, device_crc=False, **kw_)
+
+
+def _framing_threads():
+    import threading
+
+    return sorted(t.name for t in threading.enumerate() if t.name in ("surge-framing", "surge-framing-driver", "surge-push"))
+
+
+def _base_offsets(item):
+    return [int(s["base_offset"]) for s in item[0]]
+
+
+@pytest.mark.parametrize("cls", _framing_classes(), ids=lambda c: c.__name__)
+def test_a_framer_hands_its_sources_exception_to_the_consumer_after_the_fetches_before_it(cls):
+    """The one-fetch-ahead protocol's error path, the same for both framers: a ``fetches`` generator that raises when asked for
+    its fourth item — the consumer gets items 0 .. 2 in order, then that exception in its own thread, then ``StopIteration``;
+    ``close()`` returns and no framing thread is left.  ``overlap=False``: the same sequence straight out of ``next()``."""
+    n_parts = 2 if cls.__name__ == "PartitionedFramedFetches" else 1
+    for overlap in (True, False):
+        assert _framing_threads() == []
+        framed = _framer_of(cls, _small_fetches(cls, 8, fail_at=3), overlap=overlap)
+        try:
+            for i in range(3):
+                assert _base_offsets(next(framed)) == [5 * i] * n_parts
+            with pytest.raises(ValueError, match="fetch 3"):
+                next(framed)
+            with pytest.raises(StopIteration):
+                next(framed)
+            with pytest.raises(StopIteration):
+                next(framed)
+        finally:
+            framed.close()
+        assert _framing_threads() == []
+
+
+@pytest.mark.parametrize("cls", _framing_classes(), ids=lambda c: c.__name__)
+def test_closing_a_framer_whose_worker_waits_for_a_slot_returns_and_ends_the_thread(cls):
+    """``hold=2``: the worker frames three fetches (the two the consumer holds and one ahead) and then waits for a slot that
+    only a third ``next()`` would free.  ``close()`` without that ``next()`` returns, and the thread is gone."""
+    import time
+
+    name = "surge-framing-driver" if cls.__name__ == "PartitionedFramedFetches" else "surge-framing"
+    assert _framing_threads() == []
+    framed = _framer_of(cls, _small_fetches(cls, 8), overlap=True, hold=2)
+    try:
+        assert _base_offsets(next(framed))[0] == 0 and _base_offsets(next(framed))[0] == 5
+        assert _framing_threads() == [name]
+        deadline = time.monotonic() + 30
+        while len(framed.framing_seconds) < 3 and time.monotonic() < deadline:  # (microseconds: the third fetch is being framed)
+            time.sleep(0)
+        assert len(framed.framing_seconds) == 3  # the worker is as far ahead as hold lets it: its next step is the wait
+    finally:
+        framed.close()
+    assert _framing_threads() == [] and len(framed.framing_seconds) == 3
+
+
+@pytest.mark.parametrize("cls", _framing_classes(), ids=lambda c: c.__name__)
+def test_the_framing_and_push_threads_carry_the_names_the_benchmark_groups_by(cls):
+    """``bench.py``'s per-thread CPU table groups by ``surge-framing`` / ``surge-framing-driver`` / ``surge-push``: they exist
+    while a ``PushPipeline`` over a framer is iterated, and are gone when both are closed."""
+    from surge_amd.ingest import PushPipeline
+
+    name = "surge-framing-driver" if cls.__name__ == "PartitionedFramedFetches" else "surge-framing"
+    seen, got = set(), []
+    with _framer_of(cls, _small_fetches(cls, 6), overlap=True, hold=2) as framed, PushPipeline(framed, lambda item: _base_offsets(item)[:1], 2) as pipe:
+        for tok in pipe:
+            seen.update(_framing_threads())
+            got += tok
+            pipe.done()
+    assert got == [0, 5, 10, 15, 20, 25] and seen == {name, "surge-push"}
+    assert _framing_threads() == []
+
+
 def test_kafka_clients_pin_of_the_wire_format():
     """Record batches written by kafka-clients itself (tools/WirePin.java) read by the product's host decoder: the same
     records, in order, committed transactions only, the flush record skipped.  Skipped — and the record-batch reader

@@ -357,6 +357,201 @@ def test_recovery_of_a_consumer_with_several_partitions_equals_the_literal_fold(
         store.close()
 
 
+# ---- the error paths of the recovery loops ---------------------------------------------------------------------
+N_FETCHES, BAD_FETCH = 7, 2  # four pushes in flight: fetch 2 is refused while pushes 3 .. 5 are enqueued; seven fetches run the steady state and the drain
+
+
+def _recovery_threads():
+    import threading
+
+    return [t.name for t in threading.enumerate() if t.name.startswith("surge-")]
+
+
+def _fixed16_events_topic(n_partitions, ids, prior=None):
+    """Seven fetch responses of Counter events as 16-byte values, about 40 records per batch (two partitions, or one partition
+    with two batches per fetch): ``(good, bad, expect)`` — ``bad`` is ``good`` with one value of fetch 2 seventeen bytes long,
+    ``expect`` the literal ``handle_event`` fold of the good topic onto ``prior``."""
+    import random
+
+    import kafka_wire as kw
+
+    model = CounterBusinessLogic().command_model()
+    rng = random.Random(41)
+    P = max(n_partitions, 1)
+    expect = dict(prior or {})
+    seq = {k: st.version for k, st in expect.items()}
+    offs = [0] * P
+    good, bad = [], []
+    for f in range(N_FETCHES):
+        rows = ([], [])
+        for p in range(P):
+            chunks = ([], [])
+            for b in range(2 if P == 1 else 1):
+                recs = []
+                for _ in range(rng.randrange(35, 46)):
+                    k = rng.choice(ids[p::P])
+                    seq[k] = seq.get(k, 0) + 1
+                    e = rng.choice([CountIncremented(k, rng.randrange(50), seq[k]), CountDecremented(k, rng.randrange(50), seq[k]), NoOpEvent(k, seq[k])])
+                    expect[k] = model.handle_event(expect.get(k), e)
+                    recs.append((f"{k}:{seq[k]}".encode(), model.encode_events([e]).tobytes()))
+                damaged = list(recs)
+                if f == BAD_FETCH and p == P - 1 and b == 0:
+                    damaged[len(recs) // 2] = (recs[len(recs) // 2][0], b"not sixteen bytes")
+                for out, rs in zip(chunks, (recs, damaged)):
+                    out.append(kw.record_batch(offs[p], rs, compression="lz4" if (f + p) % 2 else "none"))
+                offs[p] += len(recs)
+            for row, c in zip(rows, chunks):
+                row.append(b"".join(c))
+        good.append(rows[0] if n_partitions else rows[0][0])
+        bad.append(rows[1] if n_partitions else rows[1][0])
+    return good, bad, expect
+
+
+def _counter_state_topic(n_partitions, ids):
+    """Seven fetch responses of the state topic, JSON Counter states, about 40 records per batch with overwrites and tombstones:
+    ``(good, bad, records, expect)`` — ``bad`` is ``good`` with the only (so winning) value of one id of fetch 2 cut short,
+    ``records`` the good topic's ``(key, value | None)`` pairs, ``expect`` id -> ``State`` or ``None``."""
+    import random
+
+    import kafka_wire as kw
+    from oracle import oracle
+
+    rng = random.Random(43)
+    P = max(n_partitions, 1)
+    expect, version = {}, {}
+    offs = [0] * P
+    good, bad, records = [], [], []
+    for f in range(N_FETCHES):
+        rows = ([], [])
+        for p in range(P):
+            chunks = ([], [])
+            for b in range(2 if P == 1 else 1):
+                recs = []
+                for _ in range(rng.randrange(35, 46)):
+                    k = rng.choice(ids[p::P])
+                    if expect.get(k) is not None and rng.random() < 0.15:
+                        expect[k] = None
+                        recs.append((k.encode(), None))
+                        continue
+                    version[k] = version.get(k, 0) + 1
+                    expect[k] = State(k, rng.randrange(-1000, 1000), version[k])
+                    recs.append((k.encode(), oracle.counter_state_json(k, expect[k].count, expect[k].version)))
+                damaged = list(recs)
+                if f == BAD_FETCH and p == P - 1 and b == 0:
+                    expect["only-once"] = State("only-once", 5, 1)
+                    recs.insert(len(recs) // 2, (b"only-once", oracle.counter_state_json("only-once", 5, 1)))
+                    damaged.insert(len(damaged) // 2, (b"only-once", oracle.counter_state_json("only-once", 5, 1)[:-1]))
+                records += [(k.decode(), v) for k, v in recs]
+                for out, rs in zip(chunks, (recs, damaged)):
+                    out.append(kw.record_batch(offs[p], rs, compression="lz4" if (f + p) % 2 else "none"))
+                offs[p] += len(recs)
+            for row, c in zip(rows, chunks):
+                row.append(b"".join(c))
+        good.append(rows[0] if n_partitions else rows[0][0])
+        bad.append(rows[1] if n_partitions else rows[1][0])
+    return good, bad, records, expect
+
+
+def _same_as_the_literal_fold(store, bl, expect):
+    assert set(store.keys.keys) == set(expect)
+    for k, st in expect.items():
+        assert store.get_aggregate_bytes(k) == (None if st is None else bl.aggregate_write_formatting().write_state(st).value), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_partitions", [0, 2])
+@pytest.mark.parametrize("overlap,consumer_threads", [(False, 1), (True, 1), (True, 2)])
+def test_a_recovery_whose_middle_fetch_is_refused_raises_returns_and_the_same_store_then_recovers(overlap, consumer_threads, n_partitions):
+    """restore_from_fetches over seven fetches whose third carries one 17-byte value on a topic of 16-byte events: the decoder
+    refuses that push (a status, no fault) while later pushes are in flight — the call raises ``IngestError``, returns with no
+    framing or push thread left, and the same store object then recovers the topic without the bad record to the literal fold."""
+    from surge_amd.ingest import IngestError
+    from surge_amd.store import GpuReplayStateStore
+
+    bl = CounterBusinessLogic()
+    good, bad, expect = _fixed16_events_topic(n_partitions, [f"agg-{i}" for i in range(90)])
+    arm = dict(n_partitions=n_partitions, framing_threads=2, overlap=overlap, consumer_threads=consumer_threads)
+    store = GpuReplayStateStore(bl)
+    try:
+        with pytest.raises(IngestError):
+            store.restore_from_fetches(iter(bad), **arm)
+        assert _recovery_threads() == []
+        counters = store.restore_from_fetches(iter(good), **arm)
+        assert counters["open_transactions"] == 0 and counters["records_delivered"] == counters["records_seen"] > 7 * 2 * 35
+        _same_as_the_literal_fold(store, bl, expect)
+    finally:
+        store.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_partitions", [0, 2])
+def test_a_state_topic_whose_middle_fetch_holds_a_damaged_winner_raises_returns_and_the_same_store_then_resumes(n_partitions):
+    """restore_from_state_topic over seven fetches of JSON Counter states; the only value of one id, in fetch 2, does not decode:
+    ``IngestError`` (CORRUPT) out of that fetch's load while later pushes are in flight, no thread left, and a second call with
+    good bytes on the same store restores every id's last state (tombstones: None)."""
+    from surge_amd.ingest import IngestError
+    from surge_amd.store import GpuReplayStateStore
+
+    bl = CounterBusinessLogic()
+    good, bad, _, expect = _counter_state_topic(n_partitions, [f"agg-{i}" for i in range(90)])
+    store = GpuReplayStateStore(bl)
+    try:
+        with pytest.raises(IngestError) as ei:
+            store.restore_from_state_topic(iter(bad), n_partitions=n_partitions, framing_threads=2)
+        assert ei.value.status == -7  # SURGE_E_CORRUPT
+        assert _recovery_threads() == []
+        counts = store.restore_from_state_topic(iter(good), n_partitions=n_partitions, framing_threads=2)
+        assert counts["refused"] == 0 and counts["tombstones"] > 0 and counts["records_delivered"] > 7 * 2 * 35
+        _same_as_the_literal_fold(store, bl, expect)
+    finally:
+        store.close()
+
+
+@pytest.mark.gpu
+def test_a_refused_fetch_in_the_tail_of_a_resume_raises_returns_and_resets_the_decode_base():
+    """restore_from_state_topic(events_fetches=...): the state topic loads, the state decoder continues as the events decoder, and
+    fetch 2 of the TAIL carries the 17-byte value.  ``IngestError``, no thread left; the engine's decode base is back to zeros
+    (a bare ``decode_states`` leaves the bytes its template does not name zero), ``restore_from_state_records`` on the same store
+    gives them the algebra's defaults as ever, and the call with the good tail resumes to the literal fold."""
+    import torch
+
+    from oracle import oracle
+    from surge_amd import schema as S
+    from surge_amd.encode import JsonTemplate, decode_states, key_table_utf8
+    from surge_amd.ingest import IngestError
+    from surge_amd.store import GpuReplayStateStore
+
+    bl = CounterBusinessLogic()
+    ids = [f"agg-{i}" for i in range(90)]
+    states, _, records, snapshot = _counter_state_topic(2, ids)
+    prior = {k: st for k, st in snapshot.items() if st is not None}
+    tail, bad_tail, expect = _fixed16_events_topic(2, ids + [f"late-{i}" for i in range(10)], prior=prior)
+    expect = {**snapshot, **expect}  # (an id deleted in the snapshot and untouched by the tail stays None)
+    resume = dict(n_partitions=2, framing_threads=2, events_partitions=2)
+    store = GpuReplayStateStore(bl)
+    try:
+        with pytest.raises(IngestError):
+            store.restore_from_state_topic(iter(states), events_fetches=iter(bad_tail), **resume)
+        assert _recovery_threads() == []
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+        value = oracle.counter_state_json("probe", 7, 3)
+        res = decode_states(store.engine, JsonTemplate.counter(), dev(np.frombuffer(value, dtype=np.uint8).copy()), dev(np.array([0, len(value)], dtype=np.int64)),
+                            *(dev(x) for x in key_table_utf8(["probe"])))
+        row = res[0].cpu().numpy().view(S.STATE_DTYPE).reshape(-1)[0]
+        assert res[2][0] == 1 and (int(row["count"]), int(row["version"])) == (7, 3)
+        assert (int(row["min_arg"]), int(row["max_arg"])) == (0, 0)  # no base: what the template does not name is zero
+        store.restore_from_state_records(records)
+        _same_as_the_literal_fold(store, bl, snapshot)
+        rows = store.engine.snapshot()
+        present = (rows["flags"] & S.STATE_PRESENT) != 0
+        assert present.sum() == len(prior) and (rows["min_arg"][present] == S.INT32_MAX).all() and (rows["max_arg"][present] == S.INT32_MIN).all()
+        counts = store.restore_from_state_topic(iter(states), events_fetches=iter(tail), **resume)
+        assert counts["refused"] == 0 and counts["tail_records_delivered"] > 7 * 2 * 35
+        _same_as_the_literal_fold(store, bl, expect)
+    finally:
+        store.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("overlap,consumer_threads", [(False, 1), (True, 1), (True, 2)])
 def test_recovery_that_folds_once_packs_the_decoded_fetches_into_the_log_the_host_pack_gives(overlap, consumer_threads):
