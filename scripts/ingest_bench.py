@@ -3,7 +3,7 @@
 
 One 500-record batch is written once with the test-side wire writer (tests/kafka_wire.py) and replicated with
 patched base offsets (the batch CRC does not cover baseOffset), plain and lz4; the C++ decoder
-(surge_amd/csrc/ingest.cpp) is timed on feed + drain_fixed16 in fetch-sized chunks, one decoder per partition thread.  No GPU involved.
+(surge_amd/csrc/ingest.cpp; its CRC-32C is crc32c.cpp) is timed on feed + drain_fixed16 in fetch-sized chunks, one decoder per partition thread.  No GPU involved.
 
     python scripts/ingest_bench.py [n_batches=20000] [n_keys=100000] [partition_threads=1]
 """

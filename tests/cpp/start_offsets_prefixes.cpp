@@ -1,4 +1,4 @@
-// start_offsets_prefixes.cpp — the host framer's start offsets, floors list and positions (surge_amd/csrc/ingest.cpp:
+// start_offsets_prefixes.cpp — the host framer's start offsets, floors list and positions (surge_amd/csrc/ingest.cpp, ingest_group.cpp:
 // surge_ingest_set_start_offset, _take_floors, _position, _below_start and the group's forms) under -fsanitize=address,undefined.
 // A small topic that straddles every kind of start — batches of 1, 2 and 7 records, a compaction gap, a flush record, a committed
 // and an aborted transaction, uncompressed and lz4 — is fed as every prefix of its bytes (each in a malloc of EXACTLY its length,

@@ -2,7 +2,7 @@
 // rotating slabs read by a consumer thread while the next feeds are framed (what a device push does with them), and the
 // undo of a failed feed.
 //   g++ -std=c++17 -O1 -g -fsanitize=thread -Iinclude tests/cpp/tsan_ingest_group.cpp surge_amd/csrc/ingest.cpp \
-//       surge_amd/csrc/event_decode.cpp surge_amd/csrc/f64_text.cpp surge_amd/csrc/lz4_frame.cpp -lpthread -o tsan_ingest_group
+//       surge_amd/csrc/ingest_group.cpp surge_amd/csrc/crc32c.cpp surge_amd/csrc/event_decode.cpp surge_amd/csrc/f64_text.cpp surge_amd/csrc/lz4_frame.cpp -lpthread -o tsan_ingest_group
 // The topic comes from the independent test-side writer (tests/native/wire_writer.c: transactions per flush, aborted
 // flushes, markers a fetch late).  Checked as well as raced: every fetch's sections == what each partition's own framer
 // (a plain surge_ingest, fed alone) delivers for it.

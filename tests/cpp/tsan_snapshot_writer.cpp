@@ -1,6 +1,7 @@
 // TEST INFRASTRUCTURE: the snapshot writer frames partitions on several host threads; run it under ThreadSanitizer.
 //   g++ -std=c++17 -O1 -g -fsanitize=thread -Iinclude tests/cpp/tsan_snapshot_writer.cpp surge_amd/csrc/snapshot_writer.cpp \
-//       surge_amd/csrc/lz4_frame.cpp surge_amd/csrc/ingest.cpp -lpthread -o tsan_snapshot_writer && ./tsan_snapshot_writer
+//       surge_amd/csrc/lz4_frame.cpp surge_amd/csrc/ingest.cpp surge_amd/csrc/ingest_group.cpp surge_amd/csrc/crc32c.cpp \
+//       surge_amd/csrc/event_decode.cpp surge_amd/csrc/f64_text.cpp -lpthread -o tsan_snapshot_writer && ./tsan_snapshot_writer
 // Also checks the result: every partition's batches decode (through the product's own reader) to the records appended,
 // in index order, for both codecs.
 #include <cstdio>

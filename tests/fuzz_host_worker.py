@@ -1,5 +1,5 @@
-"""TEST INFRASTRUCTURE: mutation fuzzing of the host-side decoders / encoders (ingest.cpp, lz4_frame.cpp,
-snapshot_writer.cpp) built with AddressSanitizer + UBSan.  Run as a subprocess with LD_PRELOAD=libasan.so by
+"""TEST INFRASTRUCTURE: mutation fuzzing of the host-side decoders / encoders (ingest.cpp, ingest_group.cpp, crc32c.cpp,
+lz4_frame.cpp, snapshot_writer.cpp) built with AddressSanitizer + UBSan.  Run as a subprocess with LD_PRELOAD=libasan.so by
 tests/test_host_fuzz.py:  python fuzz_host_worker.py <libsurge_host_asan.so> <seconds> <seed>
 
 Bytes from a Kafka fetch are untrusted input: whatever they are, the decoder must answer with a status code — never read or

@@ -1,12 +1,12 @@
-"""TEST INFRASTRUCTURE: a deterministic trace of the host framer (surge_amd/csrc/ingest.cpp) through its C ABI.
+"""TEST INFRASTRUCTURE: a deterministic trace of the host framer (surge_amd/csrc/ingest.cpp, ingest_group.cpp) through its C ABI.
 
     python tests/ingest_trace.py LIB SEED
 
-LIB is a host-only build of the library (g++ -O2 -shared -fPIC of ingest.cpp, event_decode.cpp, f64_text.cpp, lz4_frame.cpp and
-snapshot_writer.cpp: build_host_library below).  A seeded corpus is driven through single framers and partition groups, and
+LIB is a host-only build of the library (g++ -O2 -shared -fPIC of ingest.cpp, ingest_group.cpp, crc32c.cpp, event_decode.cpp,
+f64_text.cpp, lz4_frame.cpp and snapshot_writer.cpp: build_host_library below).  A seeded corpus is driven through single framers and partition groups, and
 every call prints one line: what was called, the status, what was consumed, the last-error text and a digest of everything the
 call handed back (records and the arena bytes they span, events and offsets, sections with their offsets and codec bits and the
-bytes they span, the counters, the key table, the group's slab bytes).  Two builds of the framer that behave alike print the same
+bytes they span, the counters, the key table, the group's slab bytes, positions, floors and what lies below a start offset).  Two builds of the framer that behave alike print the same
 trace; tests/test_ingest_trace.py holds the trace to be reproducible and to reach every message the framer can return."""
 import ctypes
 import hashlib
@@ -20,8 +20,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 import kafka_wire as kw  # noqa: E402
+import start_offsets_gen as gen  # noqa: E402
 
-HOST_SOURCES = ("ingest.cpp", "event_decode.cpp", "f64_text.cpp", "lz4_frame.cpp", "snapshot_writer.cpp")
+HOST_SOURCES = ("ingest.cpp", "ingest_group.cpp", "crc32c.cpp", "event_decode.cpp", "f64_text.cpp", "lz4_frame.cpp", "snapshot_writer.cpp")
 FRAMES, DEVICE_LZ4, DEVICE_CRC = 0x100, 0x200, 0x400
 vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
 
@@ -38,6 +39,10 @@ class Rec(ctypes.Structure):  # surge_ingest_record
 
 class Section(ctypes.Structure):  # surge_batch_section
     _fields_ = [("byte_off", i64), ("byte_len", i64), ("base_offset", i64), ("n_records", i32), ("codec", i32)]
+
+
+class Floor(ctypes.Structure):  # surge_section_floor
+    _fields_ = [("part", i32), ("reserved", i32), ("section", i64), ("first_offset", i64)]
 
 
 class EvType(ctypes.Structure):  # surge_event_json_type
@@ -72,6 +77,10 @@ def load(path):
         ("surge_ingest_group_receive_buffer", [vp, i64, P(vp)], i32), ("surge_ingest_group_receive_copy", [vp, vp, vp, i32, vp], i32),
         ("surge_ingest_group_slab_bytes", [vp, P(i64), P(i32)], i32), ("surge_ingest_group_queued_sections", [vp], i64),
         ("surge_ingest_group_counters", [vp, P(i64 * 8)], i32), ("surge_ingest_group_set_allocator", [vp, vp, vp], i32),
+        ("surge_ingest_set_start_offset", [vp, i64], i32), ("surge_ingest_take_floors", [vp, i64, vp, P(i64)], i32),
+        ("surge_ingest_position", [vp], i64), ("surge_ingest_below_start", [vp, P(i64 * 2)], i32),
+        ("surge_ingest_group_set_start_offsets", [vp, vp], i32), ("surge_ingest_group_take_floors", [vp, i64, vp, P(i64)], i32),
+        ("surge_ingest_group_positions", [vp, vp], i32), ("surge_ingest_group_below_start", [vp, P(i64 * 2)], i32),
         ("surge_crc32c", [vp, i64], ctypes.c_uint32),
     ]:
         fn = getattr(lib, name)
@@ -259,6 +268,25 @@ class Framer:
             rows.append((s.byte_off, s.byte_len, s.base_offset, s.n_records, s.codec, self.arena(s.byte_off - pre, s.byte_len + pre)))
         self.tr.line(f"{self.tag} drain_sections({max_n})", rc, got.value, self.err(), rows, self.state())
         return rc, got.value
+
+    def set_start(self, first):
+        rc = self.lib.surge_ingest_set_start_offset(self.h, first)
+        self.tr.line(f"{self.tag} set_start_offset({first})", rc, 0, self.err(), self.where())
+
+    def where(self):
+        """(position, batches discarded and records dropped below the start, counters, keys, ready)"""
+        below = (i64 * 2)(-1, -1)
+        rc = self.lib.surge_ingest_below_start(self.h, ctypes.byref(below))
+        return self.lib.surge_ingest_position(self.h), rc, list(below), self.state()
+
+    def report(self):
+        self.tr.line(f"{self.tag} position / below_start", 0, 0, self.err(), self.where())
+
+    def take_floors(self, max_n):
+        floors, got = (Floor * max(max_n, 1))(), i64(-1)
+        rc = self.lib.surge_ingest_take_floors(self.h, max_n, floors if max_n > 0 else None, ctypes.byref(got))
+        rows = [(f.part, f.reserved, f.section, f.first_offset) for f in floors[: max(got.value, 0)]] if rc == 0 else []
+        self.tr.line(f"{self.tag} take_floors({max_n})", rc, got.value, self.err(), rows, self.where())
 
     def any_drain(self, max_n):
         return self.drain_sections(min(max_n, 4096)) if self.flags & ~1 else self.drain(min(max_n, 4096))
@@ -460,6 +488,29 @@ class Group:
         self.tr.line(f"{self.tag} group_feed({what}, threads {threads}, room {cap})", rc, list(consumed), self.err(), n_sec.value, slab.value is None, rows, self.state())
         return rc, list(consumed), n_sec.value
 
+    def thread_err(self):
+        return (self.lib.surge_ingest_group_last_error(None) or b"").decode()
+
+    def where(self):
+        """(status and positions, status and what lies below the starts, the thread's last error, counters / slabs / queued sections)"""
+        pos, below = (i64 * self.n)(*[-1] * self.n), (i64 * 2)(-1, -1)
+        rc = self.lib.surge_ingest_group_positions(self.g, pos)
+        rc2 = self.lib.surge_ingest_group_below_start(self.g, ctypes.byref(below))
+        return rc, list(pos), rc2, list(below), self.thread_err(), self.state()
+
+    def set_starts(self, starts):
+        rc = self.lib.surge_ingest_group_set_start_offsets(self.g, (i64 * self.n)(*starts) if starts is not None else None)
+        self.tr.line(f"{self.tag} group_set_start_offsets({starts})", rc, 0, self.err(), self.where())
+
+    def report(self):
+        self.tr.line(f"{self.tag} group_positions / group_below_start", 0, 0, self.err(), self.where())
+
+    def take_floors(self, max_n):
+        floors, got = (Floor * max(max_n, 1))(), i64(-1)
+        rc = self.lib.surge_ingest_group_take_floors(self.g, max_n, floors if max_n > 0 else None, ctypes.byref(got))
+        rows = [(f.part, f.reserved, f.section, f.first_offset) for f in floors[: max(got.value, 0)]] if rc == 0 else []
+        self.tr.line(f"{self.tag} group_take_floors({max_n})", rc, got.value, self.err(), rows, self.where())
+
     def close(self):
         self.lib.surge_ingest_group_destroy(self.g)
 
@@ -540,10 +591,123 @@ def groups(tr, c):
     g.close()
 
 
+# ---------------------------------------------------------------------------------------------------------------- start offsets
+START = 5
+
+
+def straddling_topic(codec, value_of=lambda n: gen.fixed16(1, n, n * 3 + 1)):
+    """With START = 5: a batch below the start as a whole (0 .. 1); the batch that straddles it (2 .. 6), with a flush record at
+    offset 3, below the start; a committed transaction with a flush record above the start (7 .. 9, marker at 10); 11 .. 12, which
+    straddles a start of 12."""
+    v = value_of
+    t = gen.Topic(codec)
+    t.data([(b"a:0", v(0)), (b"b:1", v(1))])
+    t.data([(b"a:2", v(2)), (b"", b""), (b"c:4", v(4)), (b"c:5", v(5)), (b"d:6", v(6))])
+    t.data([(b"e:7", v(7)), (b"", b""), (b"a:9", v(9))], pid=5).marker(5, kw.COMMIT)
+    t.data([(b"f:11", v(11)), (b"f:12", v(12))])
+    return t
+
+
+def start_offsets(tr):
+    """The start-offset, floors and position calls (include/surge_ingest.h, "start offsets and positions") through single framers
+    — the three host drains and the FRAMES drain — and through groups.  Nothing here is drawn at random."""
+    lib = tr.lib
+    thread_err = lambda: (lib.surge_ingest_last_error(None) or b"").decode()  # noqa: E731
+    tr.line("set_start_offset(handle NULL)", lib.surge_ingest_set_start_offset(None, START), 0, thread_err())
+    tr.line("position(handle NULL)", 0, 0, thread_err(), lib.surge_ingest_position(None))
+    tr.line("below_start(handle NULL)", lib.surge_ingest_below_start(None, None), 0, thread_err())
+    tr.line("take_floors(handle NULL)", lib.surge_ingest_take_floors(None, 0, None, None), 0, thread_err())
+    tmpl = counter_template()
+    json_value = lambda n: b'{"aggregateId":"a","incrementBy":%d,"sequenceNumber":%d,"_type":"countIncremented"}' % (n % 7 - 3, n + 1)  # noqa: E731
+    for codec in ("none", "lz4"):
+        t = straddling_topic(codec)
+        cut = len(t.batches[0]["bytes"]) + len(t.batches[1]["bytes"]) // 2  # inside the straddling batch: what a feed does not consume is fed again
+        # the host drains: records below the start are passed over one by one, the flush record among them
+        for name, drain, topic in (("drain", lambda f, n: f.drain(n), t), ("fixed16", lambda f, n: f.drain_fixed16(n), t),
+                                   ("json", lambda f, n: f.drain_fixed16(n, json_template=tmpl), straddling_topic(codec, json_value))):
+            for iso in (0, 1):
+                f = Framer(tr, iso, f"start-{codec}-{name}-{iso}")
+                f.set_start(START)
+                _, consumed = f.feed(topic.bytes[:cut])
+                f.set_start(START + 1)  # refused: the first feed has been
+                drain(f, 1)
+                f.report()
+                f.feed(topic.bytes[consumed:])
+                f.report()
+                drain(f, 1)  # the first record at the start: in front of it a whole batch and three records are passed over
+                f.report()
+                f.take_floors(0)  # (a host drain floors nothing)
+                drain(f, 2)
+                f.report()
+                drain(f, 100000)
+                f.report()
+                f.close()
+        f = Framer(tr, 1, f"start-{codec}-none")  # a start <= 0 is no start
+        f.set_start(-3)
+        f.feed(t.bytes)
+        f.drain(100000)
+        f.report()
+        f.close()
+        # the FRAMES drain: the batch below the start is discarded, the straddling one handed out floored and named in the floors list
+        for flags in (1 | FRAMES, FRAMES | DEVICE_LZ4, 1 | FRAMES | DEVICE_LZ4 | DEVICE_CRC):
+            for start in (START, 12, 2, 40):
+                f = Framer(tr, flags, f"start-{codec}-{flags:#x}-at{start}")
+                f.set_start(start)
+                f.take_floors(0)
+                _, consumed = f.feed(t.bytes[:cut])
+                f.drain_sections(4)
+                f.take_floors(4)
+                f.report()
+                f.feed(t.bytes[consumed:])
+                f.set_start(start)
+                f.report()
+                f.drain_sections(1)
+                f.take_floors(0)  # too small when the section is floored
+                tr.line(f"{f.tag} take_floors(-1)", lib.surge_ingest_take_floors(f.h, -1, None, ctypes.byref(i64())), 0, f.err())
+                f.take_floors(4)
+                f.report()
+                f.drain_sections(100)
+                f.take_floors(4)
+                f.report()
+                f.close()
+
+    # groups: partition 0 starts at START, partition 1 has no start, partition 2 starts at 12.  The first feed hands out partition 0's
+    # straddling batch (a floor); the second, with partition 2's, is undone for want of room in sections_out and fed again
+    for flags, inplace, codec, threads in ((1, False, "none", 1), (1, False, "lz4", 2), (1 | DEVICE_LZ4, True, "lz4", 2), (1 | DEVICE_LZ4 | DEVICE_CRC, True, "none", 3),
+                                           (DEVICE_LZ4 | DEVICE_CRC, False, "lz4", 1)):
+        t = straddling_topic(codec)
+        g = Group(tr, 3, flags, f"g3-start-{flags:#x}-{codec}-{'inplace' if inplace else 'copy'}")
+        tr.line(f"{g.tag} group_set_start_offsets(NULL)", lib.surge_ingest_group_set_start_offsets(g.g, None), 0, g.err(), g.thread_err())
+        tr.line(f"{g.tag} group_take_floors(n_out NULL)", lib.surge_ingest_group_take_floors(g.g, 0, None, None), 0, g.err(), g.thread_err())
+        tr.line(f"{g.tag} group_positions(out NULL)", lib.surge_ingest_group_positions(g.g, None), 0, g.err(), g.thread_err())
+        tr.line(f"{g.tag} group_below_start(out NULL)", lib.surge_ingest_group_below_start(g.g, None), 0, g.err(), g.thread_err())
+        g.set_starts([START, -1, 12])
+        g.take_floors(0)
+        first = b"".join(b["bytes"] for b in t.batches[:3])  # ... and the open transaction behind the straddling batch
+        g.feed([first, t.bytes, None], threads, inplace)
+        g.take_floors(0)  # too small
+        g.take_floors(8)
+        g.report()
+        g.set_starts([START, -1, 12])  # refused: the first feed has been
+        parts = [t.bytes[len(first):], None, t.bytes]
+        rc, _, need = g.feed(parts, threads, inplace, max_sections=1)  # undone
+        g.take_floors(8)
+        g.report()
+        g.feed(parts, threads, inplace, max_sections=need)
+        g.take_floors(0)
+        g.take_floors(8)
+        g.report()
+        g.feed([None, None, None], threads, inplace)
+        g.take_floors(8)
+        g.report()
+        g.close()
+
+
 def run(lib_path, seed, out=sys.stdout):
     tr = Trace(load(lib_path), out)
     single_framers(tr, Corpus(seed))
     groups(tr, Corpus(seed + 1000003))
+    start_offsets(tr)
     return tr.n
 
 

@@ -1,5 +1,6 @@
 """The host framer's trace (tests/ingest_trace.py) over a host-only build of the library: the same in two fresh processes, and it
-reaches every message surge_amd/csrc/ingest.cpp can hand to a caller."""
+reaches every message the framer's units (surge_amd/csrc: ingest.cpp, ingest_group.cpp, ingest_internal.h, crc32c.cpp) can hand to a
+caller."""
 import os
 import re
 import subprocess
@@ -13,7 +14,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SEED = 1
 
-# Messages no caller can provoke from outside, each with the reason.  Everything else in ingest.cpp that reads like a message
+FRAMER_UNITS = ("ingest.cpp", "ingest_group.cpp", "ingest_internal.h", "crc32c.cpp")
+
+# Messages no caller can provoke from outside, each with the reason.  Everything else in the framer's units that reads like a message
 # (a string literal with a space in it) must appear in the trace: a new message without a case in ingest_trace.py fails.
 UNREACHABLE = {
     "out of host memory": "an allocation has to fail",
@@ -39,9 +42,10 @@ def traces(tmp_path_factory):
 
 
 def source_messages():
-    with open(os.path.join(ROOT, "surge_amd", "csrc", "ingest.cpp")) as f:
-        src = f.read()
-    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
+    src = ""
+    for unit in FRAMER_UNITS:
+        with open(os.path.join(ROOT, "surge_amd", "csrc", unit)) as f:
+            src += re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S) + "\n"
     # (preprocessor lines and static_asserts speak to the compiler, not to a caller)
     lines = [ln for ln in src.split("\n") if not ln.lstrip().startswith(("#", "static_assert"))]
     found = []
@@ -69,8 +73,8 @@ def test_two_fresh_processes_print_the_same_trace(traces):
 
 def test_the_trace_reaches_every_message_the_framer_can_return(traces):
     messages = source_messages()
-    assert len(messages) >= 35, messages  # (the collection itself works: ingest.cpp held 39 when this was written)
+    assert len(messages) >= 35, messages  # (the collection itself works: the framer's units held 42 when this was written)
     for m in UNREACHABLE:
-        assert m in messages, f"{m!r} is listed as unreachable but ingest.cpp no longer holds it"
+        assert m in messages, f"{m!r} is listed as unreachable but none of {FRAMER_UNITS} holds it any longer"
     missing = [m for m in messages if m not in UNREACHABLE and m not in traces[0]]
     assert not missing, missing

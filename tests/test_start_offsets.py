@@ -335,7 +335,7 @@ def test_prefixes_and_mutations_of_a_straddling_topic_under_asan_and_ubsan(tmp_p
         pytest.skip("no g++")
     exe = str(tmp_path / "start_offsets_prefixes")
     srcs = [os.path.join(root, "tests", "cpp", "start_offsets_prefixes.cpp")] + [os.path.join(root, "surge_amd", "csrc", f)
-                                                                                  for f in ("ingest.cpp", "lz4_frame.cpp", "event_decode.cpp", "f64_text.cpp")]
+                                                                                  for f in ("ingest.cpp", "ingest_group.cpp", "crc32c.cpp", "lz4_frame.cpp", "event_decode.cpp", "f64_text.cpp")]
     build = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
                             "-I" + os.path.join(root, "include")] + srcs + ["-pthread", "-o", exe], capture_output=True, text=True)
     if build.returncode != 0 and ("asan" in (build.stderr or "").lower() or "ubsan" in (build.stderr or "").lower()):
