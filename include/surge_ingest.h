@@ -453,6 +453,27 @@ int32_t surge_device_decoder_state_strings(surge_device_decoder* d, int32_t colu
 int32_t surge_device_decoder_keys(surge_device_decoder* d, uint8_t* utf8_out, int64_t utf8_capacity, int64_t* key_off_out, int64_t* n_keys_out,
                                   int64_t* utf8_bytes_out);
 int32_t surge_device_decoder_key_table(surge_device_decoder* d, const uint8_t** d_utf8, const int64_t** d_key_off);
+/* The key table, read: which row is this id.  Query i is the id ids_utf8[id_off[i] .. id_off[i+1]) (n + 1 offsets that do not
+ * decrease); idx_out[i] receives its dense index — the id's position in first-delivered order, the row of the resident state a
+ * hand-over of this decoder wrote — or -1 when the table does not hold it.  One thread per query hashes the id under the hash
+ * function in use (the new one after a re-seed), probes linearly from its home slot, wrapping at the table's end, and compares
+ * length and bytes with the key arena: only byte equality is a hit, an equal 64-bit hash over other bytes goes on probing, an
+ * empty slot is a miss.  The table is only read (no atomics), so nothing a later push sees changes.
+ *   - The id is compared as it stands, in every mode: there is no cut at ':'.  A state decoder's id "a:b" is found as "a:b", also
+ *     after surge_device_decoder_continue_as_events; an events decoder holds the key up to its first ':', so that is what is asked
+ *     for.  An id whose last record was a tombstone resolves (its row is None: that is not a miss).  The empty id is an id.
+ *   - Events decoders, state decoders and continued ones alike.  SURGE_E_STATE while a push is unfinished (its keys have no ids
+ *     yet) and on a decoder a device error poisoned.  n == 0: SURGE_OK, nothing read.  A decoder that has interned nothing
+ *     answers -1 to everything.  SURGE_E_INVALID for a NULL argument with n > 0, a negative n, offsets that decrease (host form).
+ *   - surge_device_decoder_lookup takes HOST buffers: ids and offsets are staged to the device (with the slack below), the device
+ *     form runs on the decoder's stream, the indices are copied back; it returns when they are there.
+ *   - surge_device_decoder_lookup_device takes DEVICE buffers and only enqueues on the decoder's stream: d_idx_out is complete in
+ *     that stream's order (surge_replay_set_stream the consumer onto it, or synchronize it).  d_ids_utf8 must be readable 16 bytes
+ *     behind the end of its last id, as the key arena is: ids are compared four bytes a load.  Offsets that do not describe a
+ *     length in [0, 2^31) make their query a miss.
+ * One caller at a time per decoder (the host form stages into buffers the decoder owns). */
+int32_t surge_device_decoder_lookup(surge_device_decoder* d, const uint8_t* ids_utf8, const int64_t* id_off, int64_t n, int64_t* idx_out);
+int32_t surge_device_decoder_lookup_device(surge_device_decoder* d, const uint8_t* d_ids_utf8, const int64_t* d_id_off, int64_t n, int64_t* d_idx_out);
 /* [0] records seen, [1] delivered, [2] flush records skipped, [3] Double values re-parsed on the host */
 int32_t surge_device_decoder_counters(const surge_device_decoder* d, int64_t out[4]);
 /* [0..3] the counters above, [4] re-seeds of the key table's hash function — two different aggregate ids with the same

@@ -492,6 +492,37 @@ int32_t surge_replay_encode_protobuf_state(surge_replay_handle* h, const surge_j
                                            const uint8_t* d_keys_utf8, const int64_t* d_key_off, uint8_t* d_out,
                                            int64_t out_capacity, int64_t* d_out_off, int64_t* total_bytes_out);
 
+/* ---- serialized state of chosen rows: the read seam (S2, getAggregateBytes) on the device -------------------
+ * The two encoders above over a LIST of rows instead of every aggregate in index order: output q is the text of aggregate
+ * d_rows[q] — d_out[d_out_off[q] .. d_out_off[q+1]), n_rows + 1 offsets, d_out_off[0] = 0 — in the order of the list, which may
+ * name a row any number of times.  The rows come from a key lookup (surge_device_decoder_lookup in surge_ingest.h; the host's
+ * own table) and the key table is the one the rows index: d_key_off has n_agg + 1 entries.
+ *   - row -1 (the lookup's miss): zero bytes, kind SURGE_READ_MISS;
+ *   - an absent / tombstoned aggregate: zero bytes, SURGE_READ_NONE; a poisoned one: zero bytes, SURGE_READ_POISONED (the flag
+ *     wins over presence, as in a point read);
+ *   - an aggregate whose template names a NaN / infinite Double: zero bytes, SURGE_READ_NOT_A_NUMBER, and the call returns
+ *     SURGE_E_UNSUPPORTED after encoding everything else, as the full encoders do;
+ *   - everything else: its text, SURGE_READ_VALUE.
+ * d_kind_out (nullable): n_rows bytes of SURGE_READ_*.  A row outside [-1, n_agg) — SURGE_E_INVALID — and a total beyond
+ * out_capacity — SURGE_E_RANGE, *total_bytes_out says how much room the call needs — are found before anything is written to
+ * d_out, d_out_off or d_kind_out.  n_rows == 0: d_out_off[0] = 0, SURGE_OK.  The filter of surge_replay_set_encode_filter is
+ * NOT consulted: a read serves the state as it is, published or not.  String columns (surge_replay_set_encode_strings) are
+ * read by row.  ABI v1 and v2 handles.  Enqueued on the handle's stream; returns when the output is complete.  One caller
+ * at a time per handle (the passes share the handle's scratch). */
+#define SURGE_READ_MISS         0 /* row -1                                  */
+#define SURGE_READ_VALUE        1
+#define SURGE_READ_NONE         2 /* absent / tombstoned                     */
+#define SURGE_READ_POISONED     3
+#define SURGE_READ_NOT_A_NUMBER 4 /* a NaN / infinite Double: no text exists */
+int32_t surge_replay_encode_json_rows(surge_replay_handle* h, const surge_json_template* tmpl, const uint8_t* d_keys_utf8,
+                                      const int64_t* d_key_off, const int64_t* d_rows, int64_t n_rows, uint8_t* d_out,
+                                      int64_t out_capacity, int64_t* d_out_off, uint8_t* d_kind_out, int64_t* total_bytes_out);
+/* ... every value wrapped in the protobuf State message, as surge_replay_encode_protobuf_state wraps it */
+int32_t surge_replay_encode_protobuf_state_rows(surge_replay_handle* h, const surge_json_template* payload_tmpl,
+                                                const uint8_t* d_keys_utf8, const int64_t* d_key_off, const int64_t* d_rows,
+                                                int64_t n_rows, uint8_t* d_out, int64_t out_capacity, int64_t* d_out_off,
+                                                uint8_t* d_kind_out, int64_t* total_bytes_out);
+
 /* ---- serialized state, read back ------------------------------------------------------------------
  * The inverse of the encoders above: state-topic record VALUES (the compact play-json text a surge_json_template
  * describes, fields in case-class order) -> fixed 64-byte states, for a store that resumes from the compacted state

@@ -237,6 +237,17 @@ class AggregateStateStore {
     return total;
   }
 
+  // The serialized state of the aggregates d_rows names, in that order, composed on the device (surge_replay_encode_json_rows;
+  // arguments as in surge_replay.h).  Returns the bytes the rows need; as with mergeStateStrings a buffer that is too small
+  // is not an error here (the total is > out_capacity, nothing was written).  Throws on any other failure.
+  int64_t encodeJsonRows(const surge_json_template& tmpl, const uint8_t* d_keys_utf8, const int64_t* d_key_off, const int64_t* d_rows, int64_t n_rows,
+                         uint8_t* d_out, int64_t out_capacity, int64_t* d_out_off, uint8_t* d_kind_out = nullptr) {
+    int64_t total = 0;
+    const int32_t rc = surge_replay_encode_json_rows(h_, &tmpl, d_keys_utf8, d_key_off, d_rows, n_rows, d_out, out_capacity, d_out_off, d_kind_out, &total);
+    if (!(rc == SURGE_E_RANGE && total > out_capacity)) check(rc);
+    return total;
+  }
+
   surge_replay_handle* handle() const { return h_; }
 
  private:

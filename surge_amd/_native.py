@@ -69,6 +69,8 @@ EXPORTS = (
     "surge_format_f64_json_many",
     "surge_replay_encode_json",
     "surge_replay_encode_protobuf_state",
+    "surge_replay_encode_json_rows",
+    "surge_replay_encode_protobuf_state_rows",
     "surge_replay_decode_json_states",
     "surge_replay_decode_protobuf_states",
     "surge_replay_merge_state_strings",
@@ -152,6 +154,8 @@ INGEST_EXPORTS = (
     "surge_replay_stage_decoded",
     "surge_device_decoder_keys",
     "surge_device_decoder_key_table",
+    "surge_device_decoder_lookup",
+    "surge_device_decoder_lookup_device",
     "surge_device_decoder_counters",
     "surge_device_decoder_stats",
     "surge_event_json_validate",
@@ -333,6 +337,8 @@ def load() -> ctypes.CDLL:
         "surge_format_f64_json_many": ([vp, i64, vp, i64, vp], i64),
         "surge_replay_encode_json": ([vp, vp, vp, vp, vp, i64, vp, ctypes.POINTER(i64)], i32),
         "surge_replay_encode_protobuf_state": ([vp, vp, vp, vp, vp, i64, vp, ctypes.POINTER(i64)], i32),
+        "surge_replay_encode_json_rows": ([vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, ctypes.POINTER(i64)], i32),
+        "surge_replay_encode_protobuf_state_rows": ([vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, ctypes.POINTER(i64)], i32),
         "surge_replay_decode_json_states": ([vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, ctypes.POINTER(i64 * 4)], i32),
         "surge_replay_set_decode_base": ([vp, vp], i32),
         "surge_replay_decode_protobuf_states": ([vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, ctypes.POINTER(i64 * 4)], i32),
@@ -419,6 +425,8 @@ def load() -> ctypes.CDLL:
         "surge_replay_stage_decoded": ([vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "surge_device_decoder_keys": ([vp, vp, i64, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "surge_device_decoder_key_table": ([vp, ctypes.POINTER(vp), ctypes.POINTER(vp)], i32),
+        "surge_device_decoder_lookup": ([vp, vp, vp, i64, vp], i32),
+        "surge_device_decoder_lookup_device": ([vp, vp, vp, i64, vp], i32),
         "surge_device_decoder_counters": ([vp, ctypes.POINTER(i64 * 4)], i32),
         "surge_device_decoder_stats": ([vp, ctypes.POINTER(i64 * 8)], i32),
         "surge_event_json_validate": ([vp], i32),

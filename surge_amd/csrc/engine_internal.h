@@ -162,6 +162,7 @@ struct surge_replay_handle {
   const uint8_t* encode_filter = nullptr;  // surge_replay_set_encode_filter
   surge::JsonSide json_side{};           // Double-text tables (device copy, made on first use), side string columns
   DevBuf f64_tables, nan_count;
+  DevBuf rows_off;                       // surge_replay_encode_json_rows: lengths, then offsets, of the rows asked for
   alignas(16) uint8_t decode_base[64] = {};       // surge_replay_set_decode_base: what a decoded row's unnamed bytes hold
   DevBuf sd_ptab, sd_counts, sd_last, sd_status;  // surge_replay_decode_json_states: parse table, counters, last record per aggregate, statuses
 

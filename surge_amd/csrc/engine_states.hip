@@ -90,12 +90,8 @@ int32_t surge_replay_gather(surge_replay_handle* h, const int64_t* agg_idx, int6
   return SURGE_OK;
 }
 
-static int32_t encode_states(surge_replay_handle* h, const surge_json_template* tmpl, const uint8_t* d_keys_utf8,
-                             const int64_t* d_key_off, uint8_t* d_out, int64_t out_capacity, int64_t* d_out_off,
-                             int64_t* total_bytes_out, uint32_t envelope) {
-  if (!h) return fail(nullptr, SURGE_E_INVALID, "handle is NULL");
-  if (!h->bound || h->st.n_folds == 0) return fail(h, SURGE_E_STATE, "encode_json before fold");
-  if (!tmpl || !d_key_off || !d_out_off || !total_bytes_out) return fail(h, SURGE_E_INVALID, "NULL argument");
+// what both encoders check before they touch the device, and the tables their kernels read
+static int32_t encode_prepare(surge_replay_handle* h, const surge_json_template* tmpl) {
   if (tmpl->n_parts == 0 || tmpl->n_parts > SURGE_JSON_MAX_PARTS) return fail(h, SURGE_E_INVALID, "template.n_parts out of range");
   bool uses_f64 = false;
   for (uint32_t i = 0; i < tmpl->n_parts; ++i) {
@@ -111,19 +107,35 @@ static int32_t encode_states(surge_replay_handle* h, const surge_json_template* 
     }
     uses_f64 = uses_f64 || pt.kind == SURGE_JP_F64;
   }
-  *total_bytes_out = 0;
-  if (h->n_agg == 0) return SURGE_OK;
-  DeviceGuard g(h->device);
+  return uses_f64 ? 1 : 0;
+}
+
+static int32_t encode_tables(surge_replay_handle* h, bool uses_f64) {
   if (uses_f64 && !h->json_side.f64) {  // the power-of-5 tables of the Double text: one 10.7 KB copy per handle
     HIPCHK(h, h->f64_tables.reserve(sizeof(F64Tables)));
     HIPCHK(h, hipMemcpy(h->f64_tables.ptr, f64_tables_host(), sizeof(F64Tables), hipMemcpyHostToDevice));
     h->json_side.f64 = (const F64Tables*)h->f64_tables.ptr;
   }
-  if (!h->json_side.not_a_number) {
-    HIPCHK(h, h->nan_count.reserve(8));
+  if (!h->json_side.not_a_number) {  // two counters: aggregates without a number text, rows outside the state (the rows encoders)
+    HIPCHK(h, h->nan_count.reserve(16));
     h->json_side.not_a_number = (unsigned long long*)h->nan_count.ptr;
   }
-  HIPCHK(h, hipMemsetAsync(h->nan_count.ptr, 0, 8, h->stream));
+  HIPCHK(h, hipMemsetAsync(h->nan_count.ptr, 0, 16, h->stream));
+  return SURGE_OK;
+}
+
+static int32_t encode_states(surge_replay_handle* h, const surge_json_template* tmpl, const uint8_t* d_keys_utf8,
+                             const int64_t* d_key_off, uint8_t* d_out, int64_t out_capacity, int64_t* d_out_off,
+                             int64_t* total_bytes_out, uint32_t envelope) {
+  if (!h) return fail(nullptr, SURGE_E_INVALID, "handle is NULL");
+  if (!h->bound || h->st.n_folds == 0) return fail(h, SURGE_E_STATE, "encode_json before fold");
+  if (!tmpl || !d_key_off || !d_out_off || !total_bytes_out) return fail(h, SURGE_E_INVALID, "NULL argument");
+  const int32_t uses_f64 = encode_prepare(h, tmpl);
+  if (uses_f64 < 0) return uses_f64;
+  *total_bytes_out = 0;
+  if (h->n_agg == 0) return SURGE_OK;
+  DeviceGuard g(h->device);
+  SURGE_TRY(encode_tables(h, uses_f64 != 0));
   const int64_t nb = (h->n_agg + 1023) / 1024;
   HIPCHK(h, h->scan_totals.reserve((size_t)(nb + 1) * 8));
   HIPCHK(h, launch_json_encode(*tmpl, h->d_state, h->n_agg, d_keys_utf8, d_key_off, d_out_off, (int64_t*)h->scan_totals.ptr,
@@ -149,6 +161,54 @@ static int32_t encode_states(surge_replay_handle* h, const surge_json_template* 
   return SURGE_OK;
 }
 
+// The encoders over a row list: the same two passes, over n_rows output slots.  Pass 1 leaves its lengths in the handle's own
+// scratch, so a call that is refused — a row outside the state, a buffer too small — has written nothing the caller owns.
+static int32_t encode_rows(surge_replay_handle* h, const surge_json_template* tmpl, const uint8_t* d_keys_utf8, const int64_t* d_key_off,
+                           const int64_t* d_rows, int64_t n_rows, uint8_t* d_out, int64_t out_capacity, int64_t* d_out_off, uint8_t* d_kind_out,
+                           int64_t* total_bytes_out, uint32_t envelope) {
+  if (!h) return fail(nullptr, SURGE_E_INVALID, "handle is NULL");
+  if (!h->bound || h->st.n_folds == 0) return fail(h, SURGE_E_STATE, "encode_json_rows before fold");
+  if (!tmpl || !d_out_off || !total_bytes_out) return fail(h, SURGE_E_INVALID, "NULL argument");
+  if (n_rows < 0 || out_capacity < 0) return fail(h, SURGE_E_INVALID, "negative size");
+  if (n_rows > 0 && (!d_rows || !d_key_off)) return fail(h, SURGE_E_INVALID, "NULL argument");
+  const int32_t uses_f64 = encode_prepare(h, tmpl);
+  if (uses_f64 < 0) return uses_f64;
+  *total_bytes_out = 0;
+  DeviceGuard g(h->device);
+  if (n_rows == 0) {
+    HIPCHK(h, hipMemsetAsync(d_out_off, 0, 8, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return SURGE_OK;
+  }
+  SURGE_TRY(encode_tables(h, uses_f64 != 0));
+  const int64_t nb = (n_rows + 1023) / 1024;
+  HIPCHK(h, h->scan_totals.reserve((size_t)(nb + 1) * 8));
+  HIPCHK(h, h->rows_off.reserve_roomy((size_t)(n_rows + 1) * 8));
+  int64_t* off = (int64_t*)h->rows_off.ptr;
+  const JsonRows rw{d_rows, h->n_agg, d_kind_out, (unsigned long long*)h->nan_count.ptr + 1};
+  HIPCHK(h, launch_json_encode(*tmpl, h->d_state, n_rows, d_keys_utf8, d_key_off, off, (int64_t*)h->scan_totals.ptr, d_out, false, envelope, nullptr,
+                               h->json_side, h->stream, &rw));
+  int64_t total = 0;
+  unsigned long long counts[2] = {0, 0};  // rows without a number text, rows outside the state
+  HIPCHK(h, hipMemcpyAsync(&total, (int64_t*)h->scan_totals.ptr + nb, 8, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipMemcpyAsync(counts, h->nan_count.ptr, 16, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (counts[1])
+    return fail(h, SURGE_E_INVALID, std::to_string(counts[1]) + " row(s) outside [-1, n_agg = " + std::to_string(h->n_agg) + "): nothing was written");
+  *total_bytes_out = total;
+  if (total > out_capacity) return fail(h, SURGE_E_RANGE, "output buffer too small for the encoded rows");
+  if (total > 0 && !d_out) return fail(h, SURGE_E_INVALID, "d_out is NULL");
+  HIPCHK(h, hipMemcpyAsync(off + n_rows, &total, 8, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(d_out_off, off, (size_t)(n_rows + 1) * 8, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, launch_json_encode(*tmpl, h->d_state, n_rows, d_keys_utf8, d_key_off, off, (int64_t*)h->scan_totals.ptr, d_out, true, envelope, nullptr,
+                               h->json_side, h->stream, &rw));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (counts[0])
+    return fail(h, SURGE_E_UNSUPPORTED, std::to_string(counts[0]) + " row(s) name an aggregate that holds a NaN / infinite Double: no JSON number exists (the "
+                                        "reference's writeState throws); they were encoded as zero bytes (SURGE_READ_NOT_A_NUMBER), everything else is valid");
+  return SURGE_OK;
+}
+
 int32_t surge_replay_set_encode_strings(surge_replay_handle* h, int32_t column, const uint8_t* d_utf8, const int64_t* d_off) {
   if (!h) return fail(nullptr, SURGE_E_INVALID, "handle is NULL");
   if (column < 0 || column >= SURGE_JSON_STRING_COLUMNS) return fail(h, SURGE_E_INVALID, "string column out of range");
@@ -167,6 +227,18 @@ int32_t surge_replay_encode_protobuf_state(surge_replay_handle* h, const surge_j
                                            const uint8_t* d_keys_utf8, const int64_t* d_key_off, uint8_t* d_out,
                                            int64_t out_capacity, int64_t* d_out_off, int64_t* total_bytes_out) {
   return encode_states(h, payload_tmpl, d_keys_utf8, d_key_off, d_out, out_capacity, d_out_off, total_bytes_out, 1u);
+}
+
+int32_t surge_replay_encode_json_rows(surge_replay_handle* h, const surge_json_template* tmpl, const uint8_t* d_keys_utf8, const int64_t* d_key_off,
+                                      const int64_t* d_rows, int64_t n_rows, uint8_t* d_out, int64_t out_capacity, int64_t* d_out_off, uint8_t* d_kind_out,
+                                      int64_t* total_bytes_out) {
+  return encode_rows(h, tmpl, d_keys_utf8, d_key_off, d_rows, n_rows, d_out, out_capacity, d_out_off, d_kind_out, total_bytes_out, 0u);
+}
+
+int32_t surge_replay_encode_protobuf_state_rows(surge_replay_handle* h, const surge_json_template* payload_tmpl, const uint8_t* d_keys_utf8,
+                                                const int64_t* d_key_off, const int64_t* d_rows, int64_t n_rows, uint8_t* d_out, int64_t out_capacity,
+                                                int64_t* d_out_off, uint8_t* d_kind_out, int64_t* total_bytes_out) {
+  return encode_rows(h, payload_tmpl, d_keys_utf8, d_key_off, d_rows, n_rows, d_out, out_capacity, d_out_off, d_kind_out, total_bytes_out, 1u);
 }
 
 int32_t surge_replay_set_decode_base(surge_replay_handle* h, const void* state64) {

@@ -16,6 +16,7 @@
 // State mode (surge_device_decoder_create_states) reads the compacted STATE topic with the same stages: the id is the whole key,
 // a null value is a delivered tombstone, no value is decoded — stage 2 gathers the delivered records' value bytes into one
 // buffer behind value_off, and surge_device_decoder_load_states hands them to surge_replay_decode_json_states.
+// Between pushes the key table answers reads: surge_device_decoder_lookup[_device], id -> dense index or -1 (lookup_kernel).
 #include <cstdio>
 #include <cstdlib>
 
@@ -457,6 +458,45 @@ int32_t surge_device_decoder_key_table(surge_device_decoder* d, const uint8_t** 
   if (d_utf8) *d_utf8 = (const uint8_t*)d->arena.p;
   if (d_key_off) *d_key_off = (const int64_t*)d->key_off.p;
   return OK;
+}
+
+int32_t surge_device_decoder_lookup_device(surge_device_decoder* d, const uint8_t* d_ids_utf8, const int64_t* d_id_off, int64_t n, int64_t* d_idx_out) {
+  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (n < 0 || (n > 0 && (!d_ids_utf8 || !d_id_off || !d_idx_out))) return dfail(d, E_INVALID, "bad argument");
+  // (a slot the push in flight inserted has no id yet, and its stage 2 may move the table or its hash function)
+  if (d->n_pending != 0) return dfail(d, SURGE_E_STATE, "asynchronous pushes are pending: finish them first (their keys have no ids yet)");
+  if (d->poisoned) return dfail(d, SURGE_E_STATE, "an earlier push failed on the device half way: destroy this decoder and create a new one");
+  if (n == 0) return OK;
+  DeviceScope scope(d->device);
+  DCHK(d, launch_lookup(d_ids_utf8, d_id_off, n, keys_of(d), d->seed, d_idx_out, d->stream));
+  return OK;
+}
+
+int32_t surge_device_decoder_lookup(surge_device_decoder* d, const uint8_t* ids_utf8, const int64_t* id_off, int64_t n, int64_t* idx_out) {
+  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (n < 0 || (n > 0 && (!ids_utf8 || !id_off || !idx_out))) return dfail(d, E_INVALID, "bad argument");
+  if (d->n_pending != 0) return dfail(d, SURGE_E_STATE, "asynchronous pushes are pending: finish them first (their keys have no ids yet)");
+  if (n == 0) return OK;
+  const int64_t first = id_off[0];
+  if (first < 0) return dfail(d, E_INVALID, "id_off[0] is negative");
+  std::vector<int64_t> off;
+  try { off.resize((size_t)n + 1); } catch (const std::bad_alloc&) { return dfail(d, E_NOMEM, "out of host memory"); }
+  for (int64_t i = 0; i <= n; ++i) {  // (the staged bytes begin at the first id)
+    if (i > 0 && (id_off[i] < id_off[i - 1] || id_off[i] - id_off[i - 1] >= (1ll << 31))) return dfail(d, E_INVALID, "id_off must not decrease, and an id is shorter than 2^31 bytes");
+    off[(size_t)i] = id_off[i] - first;
+  }
+  const size_t bytes = (size_t)off[(size_t)n];
+  DeviceScope scope(d->device);
+  hipStream_t st = d->stream;
+  DCHK(d, d->lk_ids.reserve(bytes + 16, false, st));  // (the 16 bytes of slack keys_equal's loads may touch)
+  DCHK(d, d->lk_off.reserve((size_t)(n + 1) * 8, false, st));
+  DCHK(d, d->lk_idx.reserve((size_t)n * 8, false, st));
+  if (bytes) DCHK(d, hipMemcpyAsync(d->lk_ids.p, ids_utf8 + first, bytes, hipMemcpyHostToDevice, st));
+  DCHK(d, hipMemcpyAsync(d->lk_off.p, off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
+  const int32_t rc = surge_device_decoder_lookup_device(d, (const uint8_t*)d->lk_ids.p, (const int64_t*)d->lk_off.p, n, (int64_t*)d->lk_idx.p);
+  if (rc == OK) DCHK(d, hipMemcpyAsync(idx_out, d->lk_idx.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+  DCHK(d, hipStreamSynchronize(st));  // (off is this call's)
+  return rc;
 }
 
 int32_t surge_device_decoder_counters(const surge_device_decoder* d, int64_t out[4]) {

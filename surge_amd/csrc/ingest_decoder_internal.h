@@ -126,6 +126,7 @@ struct surge_device_decoder {
   Buf vlen, vscan, val_src, long_runs, st_status;  // state mode: the value scan and gather's scratch; load_states' per-record statuses
   // hash table + key table
   Buf t_slots, arena, key_off, key_hash;
+  Buf lk_ids, lk_off, lk_idx;  // surge_device_decoder_lookup: the staged queries and their indices
   uint64_t t_cap = 0;
   std::atomic<uint64_t> seed{0};  // (stage 1 reads it once per push; stage 2 of an earlier push may move it on: PushSlot::seed)
   int64_t n_keys = 0, arena_bytes = 0;

@@ -241,6 +241,9 @@ void launch_intern_reseed(RecMeta* meta, int64_t n_rec, const uint8_t* bytes, co
 void launch_intern_commit(const RecMeta* meta, int64_t n_rec, const uint8_t* bytes, const KeyTable& k, const InternScratch& sc, int64_t n_new,
                           const uint4* ev_tmp, int64_t out_base, int64_t* agg_out, uint4* ev_out, int64_t* off_out, hipStream_t st);
 void launch_intern_rollback(const RecMeta* meta, int64_t n_rec, const Table& t, hipStream_t st);  // a failed push takes the keys it probed out again
+// read-only, no push in flight: idx_out[i] = the dense index of the id ids[id_off[i] .. id_off[i + 1]), compared byte for byte, or -1;
+// `ids` must be readable 16 bytes behind its last id, as the arena is (keys_equal's loads)
+hipError_t launch_lookup(const uint8_t* ids, const int64_t* id_off, int64_t n, const KeyTable& k, uint64_t seed, int64_t* idx_out, hipStream_t st);
 
 // ---- state mode (ingest_intern.hip): the kept records' VALUES move out of the push's staged bytes -------------------------------
 constexpr int kGatherRecs = 256;          // kept records per workgroup of the value gather

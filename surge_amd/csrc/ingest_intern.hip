@@ -8,6 +8,7 @@
 //   assign     the new keys' bytes to the device key arena, their ids into their slots
 //   finalize   one thread per delivered record: aggregate index from its slot, event and offset to the result arrays
 //   (state mode) value scan + value gather: the delivered records' value bytes out of the push's bytes into one buffer
+//   lookup     (no push in flight) one thread per queried id: find only — the table is read, never written
 // The control flow around these — the retry after a collision, what is checked before anything is committed, the commit order —
 // is stage 2 of the decoder (ingest_stage2.hip); this unit launches what it is told to.
 #include <rocprim/device/device_radix_sort.hpp>
@@ -160,6 +161,39 @@ __global__ void rekey_records_kernel(RecMeta* __restrict__ meta, int64_t n_rec, 
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_rec || meta[i].status != RS_OK) return;
   meta[i].hash = hash_key(bytes + meta[i].key_off, meta[i].key_len, seed);
+}
+
+// The read side of the table: query i = ids[id_off[i] .. id_off[i + 1]) -> its dense index, or -1.  One query per thread.  The id is
+// hashed under the seed in use and probed linearly from its home slot, wrapping at the table's end: an empty slot ends the probe
+// (a miss), a slot with the id's hash is compared with the arena — length, then bytes — and only byte equality is a hit; an
+// equal hash over other bytes goes on probing (after a re-seed two known keys may share a hash and own two slots).  No atomics,
+// no stores to the table: any number of lookups may run while no push is in flight.  The probe is bounded by the slot count, so
+// it ends on any table; a query whose offsets do not describe a length in [0, 2^31) is a miss.
+__global__ void __launch_bounds__(256) lookup_kernel(const uint8_t* __restrict__ ids, const int64_t* __restrict__ id_off, int64_t n, Table t, const uint8_t* __restrict__ arena,
+                                                    const int64_t* __restrict__ key_off, uint64_t seed, int64_t* __restrict__ idx_out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t o = id_off[i], len = id_off[i + 1] - o;
+  int64_t found = -1;
+  if (o >= 0 && len >= 0 && len < (1ll << 31)) {
+    const uint8_t* p = ids + o;
+    const unsigned long long h = hash_key(p, (int)len, seed);
+    uint64_t s = h & t.mask;
+    for (uint64_t step = 0; step <= t.mask; ++step) {
+      const uint4 e = ((const uint4*)t.s)[s];  // one 16-byte load: {hash, key_id, first_rec}
+      const unsigned long long eh = ((unsigned long long)e.y << 32) | e.x;
+      if (eh == 0ull) break;
+      if (eh == h && e.z != 0xffffffffu) {
+        const int64_t a0 = key_off[e.z], a1 = key_off[e.z + 1];
+        if (a1 - a0 == len && keys_equal(arena + a0, p, (int)len)) {
+          found = (int64_t)e.z;
+          break;
+        }
+      }
+      s = (s + 1) & t.mask;
+    }
+  }
+  idx_out[i] = found;
 }
 
 // ---- state mode: the delivered records' values -> one contiguous buffer --------------------------------------------------------
@@ -333,6 +367,13 @@ void launch_intern_commit(const RecMeta* meta, int64_t n_rec, const uint8_t* byt
 }
 
 void launch_intern_rollback(const RecMeta* meta, int64_t n_rec, const Table& t, hipStream_t st) { LAUNCH_1D(rollback_kernel, n_rec, st, meta, n_rec, t); }
+
+hipError_t launch_lookup(const uint8_t* ids, const int64_t* id_off, int64_t n, const KeyTable& k, uint64_t seed, int64_t* idx_out, hipStream_t st) {
+  if (n <= 0) return hipSuccess;
+  if (k.n_keys == 0 || !k.t.s) return hipMemsetAsync(idx_out, 0xff, (size_t)n * 8, st);  // nothing interned: every query misses (-1)
+  LAUNCH_1D(lookup_kernel, n, st, ids, id_off, n, k.t, (const uint8_t*)k.arena, (const int64_t*)k.key_off, seed, idx_out);
+  return hipGetLastError();
+}
 
 hipError_t launch_value_scan(const RecMeta* meta, int64_t n_rec, const InternScratch& sc, const StateScratch& ss, hipStream_t st) {
   LAUNCH_1D(value_len_kernel, n_rec + 1, st, meta, n_rec, (const uint32_t*)sc.keep, ss.vlen);

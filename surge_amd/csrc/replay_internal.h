@@ -107,9 +107,16 @@ struct JsonSide {
   const int64_t* str_off[SURGE_JSON_STRING_COLUMNS];
   unsigned long long* not_a_number;                  // += aggregates skipped because a Double of theirs is NaN / infinite
 };
+struct JsonRows {  // the encoders over a row list (surge_replay_encode_json_rows): output slot q is aggregate rows[q]
+  const int64_t* rows;      // -1: a miss (zero bytes)
+  int64_t n_agg;            // rows outside [-1, n_agg) are counted in *bad and never dereferenced
+  uint8_t* kind;            // nullable: the write pass leaves each slot's SURGE_READ_* here
+  unsigned long long* bad;
+};
+// rows == nullptr: the n resident aggregates in index order (d_len_off: n + 1 entries)
 hipError_t launch_json_encode(const surge_json_template& tmpl, const uint4* states, int64_t n, const uint8_t* keys,
                               const int64_t* key_off, int64_t* d_len_off, int64_t* d_totals, uint8_t* out, bool write_pass,
-                              uint32_t envelope, const uint8_t* filter, const JsonSide& side, hipStream_t stream);
+                              uint32_t envelope, const uint8_t* filter, const JsonSide& side, hipStream_t stream, const JsonRows* rows = nullptr);
 // ---- state_decode.hip: serialized state values -> 64-byte states (surge_replay_decode_json_states / _protobuf_states) ----
 struct F64ParseTable;
 enum { SD_WRITTEN = 0, SD_TOMBSTONES = 1, SD_REFUSED = 2, SD_AMBIGUOUS = 3, SD_FIRST_REFUSED = 4, SD_BAD_INDEX = 5, SD_N_COUNTS = 6 };

@@ -1,5 +1,6 @@
 // state_kernels.hip — everything on the device that is not the fold itself: the shard map (K4), the state encoders
-// (N3), the snapshot delta (N2), the 40-byte wire form of the exchange, bulk point reads, and the HBM stream probes the
+// (N3: every aggregate in index order, or a list of rows in query order), the snapshot delta (N2), the 40-byte wire form of the
+// exchange, bulk point reads, and the HBM stream probes the
 // bench calibrates against.  Split from fold_kernels.hip so that the fold kernels' sources (what a committed rocprof
 // traffic figure describes) change only when a fold kernel changes.
 #include "f64_text.h"
@@ -227,23 +228,40 @@ __device__ __forceinline__ uint8_t* put_varint(uint8_t* o, uint64_t v) {
 // composed in LDS (placed so that LDS offset == global address mod 16) and then stored as whole 16-byte
 // words by the block — per-thread byte stores to global were the bottleneck of the first version.  A block
 // whose output does not fit the staging buffer (very long keys) writes straight to global.
+// ROWS = true (surge_replay_encode_json_rows): output slot q is the text of aggregate a = rows[q] — state, key, string
+// columns and kind are read by a, lengths / offsets and the output by q, so a block's 256 outputs are contiguous all the
+// same.  Row -1 is a miss; a row outside [-1, n_agg) is counted in rw.bad and never dereferenced (the host refuses the call
+// before pass 2); the encode filter is not consulted: a read serves the state as it is.  Pass 2 leaves each slot's
+// SURGE_READ_* kind in rw.kind.
 constexpr int kJsonBlock = 256;
 constexpr int kJsonStageBytes = 32 * 1024;
 
-template <bool WRITE>
+template <bool WRITE, bool ROWS>
 __global__ void __launch_bounds__(kJsonBlock) json_encode_kernel(const JsonTemplateDev t, const uint4* __restrict__ states, int64_t n,
                                                                  const uint8_t* __restrict__ keys, const int64_t* __restrict__ key_off,
-                                                                 int64_t* __restrict__ len_or_off, uint8_t* __restrict__ out) {
+                                                                 int64_t* __restrict__ len_or_off, uint8_t* __restrict__ out, const JsonRows rw) {
   extern __shared__ __attribute__((aligned(16))) uint8_t json_stage[];
-  const int64_t a0 = (int64_t)blockIdx.x * kJsonBlock;
-  const int64_t a = a0 + threadIdx.x;
-  const bool live = a < n;
-  const uint8_t* st = (const uint8_t*)(states + (live ? a : 0) * 4);
-  const uint32_t fl = *(const uint32_t*)(st + 36);
-  bool emit = live && (fl & FL_PRESENT) && !(fl & FL_POISONED) && (!t.filter || t.filter[a] == SURGE_SNAP_VALUE);
+  const int64_t a0 = (int64_t)blockIdx.x * kJsonBlock;  // the block's first output slot
+  const int64_t q = a0 + threadIdx.x;
+  const bool live = q < n;
+  int64_t a = q;
+  if (ROWS) {
+    a = live ? rw.rows[q] : -1;
+    if (a < -1 || a >= rw.n_agg) {
+      if (!WRITE) atomicAdd(rw.bad, 1ull);
+      a = -1;
+    }
+  }
+  const bool has = ROWS ? a >= 0 : true;
+  const uint8_t* st = (const uint8_t*)(states + ((ROWS ? has : live) ? a : 0) * 4);
+  const uint32_t fl = has ? *(const uint32_t*)(st + 36) : 0u;
+  bool emit = live && (fl & FL_PRESENT) && !(fl & FL_POISONED) && (ROWS || !t.filter || t.filter[a] == SURGE_SNAP_VALUE);
   if (emit && !json_all_finite(t, st)) {
     emit = false;
     if (!WRITE) atomicAdd(t.side.not_a_number, 1ull);
+    if (ROWS && WRITE && rw.kind) rw.kind[q] = SURGE_READ_NOT_A_NUMBER;
+  } else if (ROWS && WRITE && live && rw.kind) {
+    rw.kind[q] = (uint8_t)(!has ? SURGE_READ_MISS : (fl & FL_POISONED) ? SURGE_READ_POISONED : (fl & FL_PRESENT) ? SURGE_READ_VALUE : SURGE_READ_NONE);
   }
   if (!WRITE) {
     if (!live) return;
@@ -255,7 +273,7 @@ __global__ void __launch_bounds__(kJsonBlock) json_encode_kernel(const JsonTempl
         len = (idlen ? 1 + varint_len((uint64_t)idlen) + idlen : 0) + (len ? 1 + varint_len((uint64_t)len) + len : 0);
       }
     }
-    len_or_off[a] = len;
+    len_or_off[q] = len;
     return;
   }
   const int64_t a1 = (a0 + kJsonBlock < n) ? a0 + kJsonBlock : n;
@@ -263,7 +281,7 @@ __global__ void __launch_bounds__(kJsonBlock) json_encode_kernel(const JsonTempl
   const uint32_t shift = (uint32_t)((uintptr_t)(out + base) & 15u);
   const bool staged = (end - base) + shift <= kJsonStageBytes;
   if (emit) {
-    uint8_t* o = staged ? json_stage + shift + (len_or_off[a] - base) : out + len_or_off[a];
+    uint8_t* o = staged ? json_stage + shift + (len_or_off[q] - base) : out + len_or_off[q];
     if (t.envelope == 1) {
       const int64_t idlen = key_off[a + 1] - key_off[a];
       if (idlen) {
@@ -499,9 +517,10 @@ hipError_t launch_scan_lengths_i64(int64_t* v, int64_t n, int64_t* d_totals, hip
 }
 
 // d_len_off: n + 1 entries; d_totals: ceil(n / 1024) + 1 entries of scratch
+// rows == nullptr: the n resident aggregates in index order; otherwise n = the row list's length (JsonRows)
 hipError_t launch_json_encode(const surge_json_template& tmpl, const uint4* states, int64_t n, const uint8_t* keys,
                               const int64_t* key_off, int64_t* d_len_off, int64_t* d_totals, uint8_t* out, bool write_pass,
-                              uint32_t envelope, const uint8_t* filter, const JsonSide& side, hipStream_t stream) {
+                              uint32_t envelope, const uint8_t* filter, const JsonSide& side, hipStream_t stream, const JsonRows* rows) {
   if (n <= 0) return hipSuccess;
   JsonTemplateDev t;
   t.n_parts = tmpl.n_parts;
@@ -514,12 +533,18 @@ hipError_t launch_json_encode(const surge_json_template& tmpl, const uint4* stat
   }
   for (int i = 0; i < 256; ++i) t.literals[i] = tmpl.literals[i];
   const unsigned blocks = (unsigned)((n + 255) / 256);
+  const JsonRows rw = rows ? *rows : JsonRows{};
   if (!write_pass) {
-    hipLaunchKernelGGL(json_encode_kernel<false>, dim3(blocks), dim3(kJsonBlock), 0, stream, t, states, n, keys, key_off, d_len_off, out);
+    if (rows)
+      hipLaunchKernelGGL((json_encode_kernel<false, true>), dim3(blocks), dim3(kJsonBlock), 0, stream, t, states, n, keys, key_off, d_len_off, out, rw);
+    else
+      hipLaunchKernelGGL((json_encode_kernel<false, false>), dim3(blocks), dim3(kJsonBlock), 0, stream, t, states, n, keys, key_off, d_len_off, out, rw);
     return launch_scan_lengths_i64(d_len_off, n, d_totals, stream);
-  } else {
-    hipLaunchKernelGGL(json_encode_kernel<true>, dim3(blocks), dim3(kJsonBlock), kJsonStageBytes + 16, stream, t, states, n, keys, key_off, d_len_off, out);
   }
+  if (rows)
+    hipLaunchKernelGGL((json_encode_kernel<true, true>), dim3(blocks), dim3(kJsonBlock), kJsonStageBytes + 16, stream, t, states, n, keys, key_off, d_len_off, out, rw);
+  else
+    hipLaunchKernelGGL((json_encode_kernel<true, false>), dim3(blocks), dim3(kJsonBlock), kJsonStageBytes + 16, stream, t, states, n, keys, key_off, d_len_off, out, rw);
   return hipGetLastError();
 }
 

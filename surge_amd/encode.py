@@ -1,7 +1,9 @@
 """GPU-side state encoders: fixed 64-byte states -> the plugin's serialized text, in bulk.
 
-Point reads keep using the plugin's own ``writeState`` on the host (``surge_amd/store.py``); this is for
-publishing a whole snapshot (10 M aggregates ≈ 1 GB of JSON) without a per-aggregate host loop.  The
+``encode_states`` publishes a whole snapshot (10 M aggregates ≈ 1 GB of JSON) without a per-aggregate host loop;
+``encode_rows`` writes the same text for a list of rows in query order — the read seam's bytes for a batch of ids
+(``GpuReplayStateStore.get_aggregate_bytes_many``; a store with a host key table still serves single reads through the
+plugin's own ``writeState``).  The
 text shape is declared as a template; ``JsonTemplate.counter()`` is the Counter fixture's play-json form
 ``{"aggregateId":"<id>","count":N,"version":N}``
 (``modules/command-engine/scaladsl/src/test/scala/surge/scaladsl/TestBoundedContext.scala:15-16,127-129``);
@@ -131,6 +133,51 @@ def encode_states(engine: ReplayEngine, template: JsonTemplate, d_keys_utf8, d_k
         msg = lib.surge_replay_last_error(engine._h)
         raise ReplayError(rc, msg.decode() if msg else "")
     raise RuntimeError("encode_states: unreachable")
+
+
+#: ``SURGE_READ_*`` (``include/surge_replay.h``): what a slot of ``encode_rows`` stands for
+READ_MISS, READ_VALUE, READ_NONE, READ_POISONED, READ_NOT_A_NUMBER = 0, 1, 2, 3, 4
+
+
+def encode_rows(engine: ReplayEngine, template: JsonTemplate, d_keys_utf8, d_key_off, d_rows, envelope: str = "none", strings=(), capacity_hint: int = 0):
+    """Encode the aggregates ``d_rows`` names (an ``int64`` CUDA tensor; ``-1``: a miss), in that order
+    (``surge_replay_encode_json_rows`` / ``_protobuf_state_rows``): the read seam's bytes for a batch of ids, composed on the
+    device.  ``d_keys_utf8`` / ``d_key_off``: the key table the rows index (``DeviceDecoder.device_key_table()``); ``envelope`` and
+    ``strings`` as in ``encode_states``.  Returns ``(out, out_off, kind)`` CUDA tensors: slot ``q``'s text is
+    ``out[out_off[q]:out_off[q+1]]`` and ``kind[q]`` one of ``READ_*`` (zero bytes unless ``READ_VALUE``).  The encode filter is
+    not consulted.  A buffer that is too small is retried once with the exact size, as in ``encode_states``; a row outside
+    ``[-1, n_agg)`` raises ``ReplayError`` (INVALID); a row that holds a NaN / infinite Double raises it (UNSUPPORTED) after
+    everything else was encoded."""
+    import torch
+
+    wrapped = check_envelope(envelope)
+    lib = _native.load()
+    fn = lib.surge_replay_encode_protobuf_state_rows if wrapped else lib.surge_replay_encode_json_rows
+    n = int(d_rows.numel())
+    dev = d_rows.device
+    for c in range(STRING_COLUMNS):
+        col = strings[c] if c < len(strings) else None
+        engine._check(lib.surge_replay_set_encode_strings(
+            engine._h, c, ctypes.c_void_p(col[0].data_ptr()) if col is not None and col[0].numel() else None,
+            ctypes.c_void_p(col[1].data_ptr()) if col is not None else None))
+    d_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    kind = torch.empty(n, dtype=torch.uint8, device=dev)
+    cap = int(capacity_hint) if capacity_hint else max(64, 128 * n)  # (a guess: the first pass says what the rows need)
+    t = template.to_c()
+    ptr = lambda x: ctypes.c_void_p(x.data_ptr()) if x is not None and x.numel() else None  # noqa: E731
+    for _ in range(2):
+        d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        total = ctypes.c_int64(0)
+        rc = fn(engine._h, ctypes.byref(t), ptr(d_keys_utf8), ctypes.c_void_p(d_key_off.data_ptr()), ptr(d_rows), n, ctypes.c_void_p(d_out.data_ptr()), cap,
+                ctypes.c_void_p(d_off.data_ptr()), ptr(kind), ctypes.byref(total))
+        if rc == 0:
+            return d_out[: total.value], d_off, kind
+        if rc == -6 and total.value > cap:  # SURGE_E_RANGE: retry with the exact size
+            cap = total.value
+            continue
+        msg = lib.surge_replay_last_error(engine._h)
+        raise ReplayError(rc, msg.decode() if msg else "")
+    raise RuntimeError("encode_rows: unreachable")
 
 
 # ---- the way back: serialized state values -> fixed 64-byte states -----------------------------------------------------

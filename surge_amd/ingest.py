@@ -659,6 +659,7 @@ class DeviceDecoder:
         self._h = ctypes.c_void_p()
         self.device = device
         self.states = bool(states)
+        self._stream = stream  # the hipStream_t stage 2 and the lookups run on (None: the default stream)
         self._inflight = []
         c = template.to_c() if template is not None else None
         if states:
@@ -899,6 +900,56 @@ class DeviceDecoder:
                                                         ctypes.byref(n), ctypes.byref(nb)))
         raw = data.tobytes()
         return [raw[off[i]:off[i + 1]].decode("utf-8") for i in range(n.value)]
+
+    def device_key_table(self):
+        """``(d_utf8, d_key_off)``: CUDA tensors viewing the key table where it lives (``surge_device_decoder_key_table``; what the
+        state encoders and ``encode.encode_rows`` take), valid until the next push that finds a new id, or ``close``.  ``d_utf8`` covers
+        the ids' bytes; the arena behind it is the decoder's."""
+        import torch
+
+        n, nb = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._lib.surge_device_decoder_keys(self._h, None, 0, None, ctypes.byref(n), ctypes.byref(nb)))
+        pk, po = ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self._lib.surge_device_decoder_key_table(self._h, ctypes.byref(pk), ctypes.byref(po)))
+        dev = torch.device("cuda", self.device)
+        d_utf8 = _device_view(pk, (nb.value,), "|u1", dev) if nb.value else torch.zeros(0, dtype=torch.uint8, device=dev)
+        return d_utf8, _device_view(po, (n.value + 1,), "<i8", dev)
+
+    def lookup(self, ids) -> np.ndarray:
+        """Which row is each id (``surge_device_decoder_lookup``): ``ids`` are ``str`` (UTF-8) or ``bytes``; returns ``np.int64[n]``,
+        an id's dense index — its position in first-delivered order — or ``-1`` when the table does not hold it.  Compared byte
+        for byte as it stands (no cut at ``:``).  Every push has to be finished (``IngestError``, STATE, otherwise)."""
+        enc = [k.encode("utf-8") if isinstance(k, str) else bytes(k) for k in ids]
+        n = len(enc)
+        off = np.zeros(n + 1, dtype=np.int64)
+        if n:
+            np.cumsum([len(e) for e in enc], out=off[1:])
+        data = np.frombuffer(b"".join(enc), dtype=np.uint8) if off[-1] else np.zeros(1, np.uint8)
+        out = np.empty(n, dtype=np.int64)
+        self._check(self._lib.surge_device_decoder_lookup(self._h, data.ctypes.data_as(ctypes.c_void_p), off.ctypes.data_as(ctypes.c_void_p), n,
+                                                          out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def lookup_device(self, d_ids, d_off):
+        """The same for queries that are on the device already (``surge_device_decoder_lookup_device``): ``d_ids`` a ``uint8`` CUDA
+        tensor READABLE 16 BYTES BEHIND ITS LAST ID (pad it: ids are compared four bytes a load), ``d_off`` ``n + 1`` ``int64``
+        offsets into it.  Returns an ``int64`` CUDA tensor.  Nothing waits on the host: the work is enqueued on the decoder's stream,
+        behind what torch's current stream has enqueued so far (the queries), and torch's current stream is made to wait for it —
+        the tensor is complete in the order of that stream, like any tensor torch computes."""
+        import torch
+
+        n = int(d_off.numel()) - 1
+        dev = torch.device("cuda", self.device)
+        out = torch.empty(max(n, 0), dtype=torch.int64, device=dev)
+        if n > 0:
+            with torch.cuda.device(dev):
+                mine = torch.cuda.ExternalStream(int(self._stream)) if self._stream else torch.cuda.default_stream(dev)
+                current = torch.cuda.current_stream(dev)
+                mine.wait_stream(current)  # (the queries may have been written on another stream than the decoder's)
+                self._check(self._lib.surge_device_decoder_lookup_device(self._h, ctypes.c_void_p(d_ids.data_ptr()), ctypes.c_void_p(d_off.data_ptr()), n,
+                                                                         ctypes.c_void_p(out.data_ptr())))
+                current.wait_stream(mine)
+        return out
 
     def counters(self) -> dict:
         c = (ctypes.c_int64 * 4)()

@@ -13,11 +13,16 @@ The reference rebuilds this store by replaying the compacted *state* topic into 
 same bytes are produced by folding the *events* topic on the GPU (equal by the reference's own
 invariant: events and snapshot are published in one transaction).  The serialized
 format stays the plugin's: the engine hands a fixed-width state to ``writeState``.
+
+A restore with ``host_keys=False`` keeps the device decoder instead: its key table on the GPU says which row an id is
+(``DeviceDecoder.lookup``) and the state encoders write the bytes of the rows asked for (``encode.encode_rows``), so no id
+is downloaded and no state mirrored until something needs the host table (``GpuReplayStateStore.keys``).
 """
 from __future__ import annotations
 
 import bisect
 import contextlib
+import threading
 from typing import Dict, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -44,7 +49,16 @@ class GpuReplayStateStore:
         self.business_logic = business_logic
         self.model = model
         self.engine = ReplayEngine(model.event_algebra(), device)
-        self.keys = KeyTable()
+        self._keys = KeyTable()
+        #: the device decoder a ``host_keys=False`` restore left alive: its key table on the GPU answers the reads until something
+        #: needs the host table (``keys``)
+        self._decoder = None
+        self._device_lock = threading.RLock()  # the device route serves one reader at a time (decoder and engine scratch)
+        self._uploaded_keys = None  # a host-keys store's key table on the device, for ``get_aggregate_bytes_many``: (n_keys, d_utf8, d_off)
+        #: what ``get_aggregate_bytes`` writes on the device route: the ``encode.JsonTemplate`` of the model's serialized state
+        #: (``None``: ``JsonTemplate.counter()``) and its envelope; ``restore_from_state_topic`` sets both from its arguments
+        self.read_template = None
+        self.read_envelope = "none"
         self.store_name = f"{business_logic.aggregate_name}AggregateStateStore"  # SurgeStateStoreConsumer.scala:110
         self._restored = False
         #: the STR columns of the states a resume from the state topic loaded: per string column ``(d_utf8, d_off)`` CUDA
@@ -52,7 +66,40 @@ class GpuReplayStateStore:
         self.state_strings = None
 
     def close(self):
+        self._drop_decoder()
         self.engine.close()
+
+    # -- the key table: on the device after a ``host_keys=False`` restore, on the host once something needs it there --------
+    @property
+    def device_route(self) -> bool:
+        """``True`` while reads are answered from the device key table (no host dictionary, no host mirror)."""
+        return self._decoder is not None
+
+    @property
+    def keys(self) -> KeyTable:
+        """The host key table.  On a device-route store the first use builds it: the decoder's ids are adopted, the host mirror
+        is published exactly as a ``host_keys=True`` restore does, the decoder is dropped — from then on the store is that store."""
+        if self._decoder is not None:
+            with self._device_lock:
+                d = self._decoder
+                if d is not None:
+                    self._adopt_keys_of(d)
+                    self.engine.snapshot()  # publishes the host mirror that serves point reads
+                    self._decoder = None
+                    d.close()
+        return self._keys
+
+    @keys.setter
+    def keys(self, table: KeyTable) -> None:
+        self._drop_decoder()
+        self._keys = table
+        self._uploaded_keys = None
+
+    def _drop_decoder(self) -> None:
+        with self._device_lock:
+            d, self._decoder = self._decoder, None
+            if d is not None:
+                d.close()
 
     def _bind_all_none(self, n_agg: int) -> None:
         """The resident state becomes ``n_agg`` aggregates, every one None (an empty log, folded)."""
@@ -78,7 +125,8 @@ class GpuReplayStateStore:
         keys = KeyTable()
         for k in (decoder.keys() if decoder is not None else ()):
             keys.intern(k)
-        self.keys = keys
+        self._keys = keys
+        self._uploaded_keys = None
 
     @contextlib.contextmanager
     def _decoding_onto_the_defaults(self):
@@ -172,7 +220,8 @@ class GpuReplayStateStore:
         return counters
 
     def restore_from_fetches(self, fetches, capacity: int = 0, overlap: bool = True, n_partitions: int = 0, framing_threads: int = 8,
-                             consumer_threads: int = 1, bound_log: bool = False, algo: int = ALGO_AUTO, device_crc: bool = True, in_place: bool = True) -> dict:
+                             consumer_threads: int = 1, bound_log: bool = False, algo: int = ALGO_AUTO, device_crc: bool = True, in_place: bool = True,
+                             host_keys: bool = True) -> dict:
         """Recover from the events topic as a consumer receives it: ``fetches`` yields the record-batch bytes of one
         partition, fetch by fetch, in offset order (a list, or a generator that polls) — or, with ``n_partitions``, per
         fetch response the next bytes of each of the consumer's partitions (``PartitionedFramedFetches``: one framer per
@@ -194,12 +243,24 @@ class GpuReplayStateStore:
         ``engine.prepare`` can replay it.  What the reference's restore gets from RocksDB's key order
         (``SurgeStateStoreConsumer.scala:57-76``).
         Needs values the device decoder reads (16-byte fixed events, or JSON with the model's
-        ``event_json_template``); returns the ingest + decoder counters."""
+        ``event_json_template``); returns the ingest + decoder counters.
+        ``host_keys=False``: the recovery ends where the GPU does — the decoder stays alive and its key table answers the reads
+        (``get_aggregate_bytes`` / ``get_aggregate_bytes_many`` / ``get_aggregate``: a lookup and an encode on the device); no id
+        is downloaded, no Python dictionary is built and no host mirror of the states is copied until something asks for the
+        host table (``keys``: ``apply_events``, the key/value store's ``all`` / ``range``), which then builds both as the default
+        does here.  On that route the bytes of a read are NOT the plugin's ``aggregate_write_formatting``'s: they are composed on
+        the GPU through ``read_template`` / ``read_envelope`` — reset here to ``None`` / ``"none"``, that is ``JsonTemplate.counter()``;
+        a model with another serialized form sets ``read_template`` after the restore (or passes ``template`` to
+        ``get_aggregate_bytes_many``)."""
         from .ingest import DeviceDecoder
 
         made = []  # the decoder, made for the first fetch with a record in it
+        kept = False
 
         def new_decoder(template):
+            # (an earlier device-route restore's decoder goes here, not sooner: up to this point — the fetches' first record, whose
+            # values may turn out not to be device-decodable — nothing of the store has changed, and its reads still answer)
+            self._drop_decoder()
             made.append(DeviceDecoder(template, device=self.engine.device))
             return made[0]
 
@@ -207,6 +268,9 @@ class GpuReplayStateStore:
             counters, n_agg = self._fold_fetches(fetches, new_decoder, -1, capacity=capacity, overlap=overlap, n_partitions=n_partitions, framing_threads=framing_threads,
                                                  consumer_threads=consumer_threads, bound_log=bound_log, device_crc=device_crc, in_place=in_place)
             d = made[0] if made else None
+            if d is None:
+                self._drop_decoder()  # (no record in the whole topic: the earlier restore's decoder has not been replaced yet)
+            self.read_template, self.read_envelope = None, "none"  # (an earlier restore_from_state_topic's)
             if bound_log and d is not None:
                 n_agg = max(n_agg, capacity, d.n_keys)
                 self.engine.pack_staged(n_agg)  # decoded fetches -> ONE bound CSR log
@@ -214,13 +278,20 @@ class GpuReplayStateStore:
                 self.engine.synchronize()
             elif n_agg < 0:  # nothing deliverable in the whole topic
                 self._bind_all_none(capacity)
-            self._adopt_keys_of(d)
+            if host_keys or d is None:
+                self._adopt_keys_of(d)
+            else:
+                self._adopt_keys_of(None)  # (the host table is built when something asks for it: ``keys``)
             if d is not None:
                 counters.update(d.counters())
+            kept = not host_keys and d is not None
         finally:
-            if made:
+            if made and not kept:
                 made[0].close()
-        self.engine.snapshot()  # publishes the host mirror that serves point reads
+        if kept:
+            self._decoder = made[0]
+        else:
+            self.engine.snapshot()  # publishes the host mirror that serves point reads
         self._restored = True
         return counters
 
@@ -362,7 +433,7 @@ class GpuReplayStateStore:
 
     def restore_from_state_topic(self, fetches, n_partitions: int = 0, template=None, events_tail: Sequence = (), framing_threads: int = 4,
                                  device_crc: bool = True, in_place: bool = True, envelope: str = "none", events_fetches=None, events_from=None,
-                                 events_partitions: int = 0) -> dict:
+                                 events_partitions: int = 0, host_keys: bool = True) -> dict:
         """``restore_from_state_records`` from what a consumer of the state topic actually receives: ``fetches`` yields the
         topic's bytes — message-format-v2 record batches, LZ4 or uncompressed, transactional, with the producer's flush
         records, tombstones as null values and the offset gaps log compaction leaves — one ``bytes`` per fetch, or with
@@ -381,7 +452,8 @@ class GpuReplayStateStore:
         loop with the framers started at ``events_from``: records below a first offset are dropped where records are parsed,
         on the device.  Aggregates that first appear in the tail have the strings ``restore_from_fetches`` gives them (none).
         Returns the framer's and the decoder's counters plus the summed decode counts; with ``events_fetches`` the tail's own
-        under ``tail_*`` names."""
+        under ``tail_*`` names.  ``host_keys=False``: as in ``restore_from_fetches`` — the decoder (state, or continued as the
+        tail's events decoder) stays and serves the reads; a non-empty ``events_tail`` needs the host table and builds it."""
         from .encode import JsonTemplate, check_envelope
         from .ingest import DeviceDecoder, pushes_in_flight
 
@@ -397,13 +469,17 @@ class GpuReplayStateStore:
                 raise ValueError("one events partition (events_partitions=0) takes one first offset")
             events_from = int(events_from[0])
         template = template or JsonTemplate.counter()
+        self._drop_decoder()  # an earlier device-route restore's — behind every refusal of an argument: a call that is refused changes nothing
+        self.read_template, self.read_envelope = template, envelope
         eng = self.engine
         self._bind_all_none(0)  # no aggregate yet: the loads grow the state for the ids they meet
         depth = 4
         totals = [0, 0, 0, 0]
         self.state_strings = None
         keep = bool(_str_columns(template))  # the STR fields the values carry are kept beside the rows (a template without them pays nothing)
-        with DeviceDecoder(states=True, device=eng.device, keep_strings=keep) as d, self._decoding_onto_the_defaults():
+        with contextlib.ExitStack() as closing, self._decoding_onto_the_defaults():
+            d = closing.enter_context(DeviceDecoder(states=True, device=eng.device, keep_strings=keep))
+
             def push(item):
                 parts = [(sec, arena) for sec, arena in (item if isinstance(item, list) else [item]) if sec.shape[0]]
                 if parts:
@@ -438,11 +514,16 @@ class GpuReplayStateStore:
                 counters.update({"tail_" + k: v for k, v in tail.items()})
             if keep:  # (the decoder's buffers go with it — a decoder that went on as an events decoder still has them: the columns are cloned out)
                 self.state_strings = [None if col is None else (col[0].clone(), col[1].clone()) for col in d.state_strings()]
-            self._adopt_keys_of(d)
+            if host_keys:
+                self._adopt_keys_of(d)
+            else:  # the decoder outlives the block: its key table answers the reads
+                self._adopt_keys_of(None)
+                closing.pop_all()
+                self._decoder = d
         self._restored = True
         if len(events_tail):
             self.apply_events(events_tail)
-        else:
+        elif host_keys:
             eng.snapshot()
         counters.update({"rows_written": totals[0], "tombstones": totals[1], "refused": totals[2], "reparsed_on_host": totals[3]})
         return counters
@@ -496,17 +577,95 @@ class GpuReplayStateStore:
 
     # -- S2 ---------------------------------------------------------------------------------
     def get_aggregate_bytes(self, aggregate_id: str) -> Optional[bytes]:
-        """``None`` = no such aggregate (KTable miss) or tombstone; else ``writeState(state).value``."""
+        """``None`` = no such aggregate (KTable miss) or tombstone; else ``writeState(state).value``.  On the device route
+        (``host_keys=False``) the bytes are ``get_aggregate_bytes_many([aggregate_id])``' — ``read_template`` / ``read_envelope``
+        composed on the GPU; one launch chain and two copies per call, so batches are what that route is for."""
+        if self._decoder is not None:
+            with self._device_lock:
+                if self._decoder is not None:
+                    return self.get_aggregate_bytes_many([aggregate_id], self.read_template, self.read_envelope)[0]
         agg = self.get_aggregate(aggregate_id)
         if agg is None:
             return None
         return write_state_of(self.business_logic.aggregate_write_formatting(), aggregate_id, agg).value
 
+    def get_aggregate_bytes_many(self, aggregate_ids: Sequence[str], template=None, envelope: str = "none") -> List[Optional[bytes]]:
+        """``get_aggregate_bytes`` for a batch of ids, composed on the GPU: the ids' rows — a lookup in the decoder's device key
+        table on the device route, the host table otherwise (its ids uploaded once) — then ``encode.encode_rows`` through
+        ``template`` (the model's serialized state; default ``JsonTemplate.counter()``, as in ``restore_from_state_topic``) and
+        one copy back.  ``None`` for an id the store does not hold and for a tombstone; ``AggregateInitializationException`` when
+        one of the ids is poisoned, as the single read raises it.  ``(JP_STR, column)`` parts take ``state_string_columns()``;
+        a column nothing restored raises ``ValueError``.  ``envelope="protobuf_state"``: what a multilanguage application
+        stores.  The restored columns hold EMPTY strings for aggregates that first appeared after the resume (``apply_events``, an
+        events tail): their strings are the host model's alone, so for such an aggregate a STR part is written ``""`` here while
+        ``get_aggregate_bytes`` — the plugin's formatter over ``restore_static_strings`` — writes the real string.  Every other
+        part, and every aggregate the state topic carried, reads the same on both."""
+        import torch
+
+        from .encode import READ_POISONED, READ_VALUE, JsonTemplate, check_envelope, encode_rows, key_table_utf8
+
+        check_envelope(envelope)
+        template = template or JsonTemplate.counter()
+        ids = list(aggregate_ids)
+        if not ids:
+            return []
+        eng = self.engine
+        dev = torch.device("cuda", eng.device)
+        with self._device_lock:
+            strings = self.state_string_columns()
+            for c in _str_columns(template):
+                if c >= len(strings) or strings[c] is None:
+                    raise ValueError(f"the template names string column {c}, and nothing restored it")
+            d = self._decoder
+            if d is not None:
+                enc = [k.encode("utf-8") for k in ids]
+                off = np.zeros(len(enc) + 1, dtype=np.int64)
+                np.cumsum([len(e) for e in enc], out=off[1:])
+                data = np.zeros(int(off[-1]) + 16, dtype=np.uint8)  # (the slack behind the last id the lookup's loads may touch)
+                data[: int(off[-1])] = np.frombuffer(b"".join(enc), dtype=np.uint8)
+                d_rows = d.lookup_device(torch.from_numpy(data).to(dev), torch.from_numpy(off).to(dev))
+                if eng.stream_ptr:  # (the rows are complete in the order of torch's current stream; an engine on a stream of its own is not in it)
+                    torch.cuda.current_stream(dev).synchronize()
+                d_utf8, d_key_off = d.device_key_table()
+            else:
+                keys = self._keys
+                n_agg = eng.n_agg
+                rows = np.fromiter((-1 if i is None or i >= n_agg else i for i in map(keys.get, ids)), dtype=np.int64, count=len(ids))
+                if self._uploaded_keys is None or self._uploaded_keys[0] != len(keys):
+                    kd, ko = key_table_utf8(keys.keys)
+                    self._uploaded_keys = (len(keys), torch.from_numpy(kd).to(dev), torch.from_numpy(ko).to(dev))
+                _, d_utf8, d_key_off = self._uploaded_keys
+                d_rows = torch.from_numpy(rows).to(dev)
+            out, out_off, kind = encode_rows(eng, template, d_utf8, d_key_off, d_rows, envelope=envelope, strings=strings)
+            raw, off, kind = out.cpu().numpy().tobytes(), out_off.cpu().numpy().tolist(), kind.cpu().numpy()
+        bad = np.flatnonzero(kind == READ_POISONED)
+        if bad.shape[0]:
+            raise AggregateInitializationException(
+                f"replay of aggregate {ids[int(bad[0])]!r} hit an event whose handler throws; state is frozen before it"
+            )
+        value = (kind == READ_VALUE).tolist()
+        return [raw[off[q]:off[q + 1]] if value[q] else None for q in range(len(ids))]
+
+    def _row_of(self, aggregate_id: str):
+        """The id's row, or ``None``: from the device key table while the store is on the device route."""
+        d = self._decoder
+        if d is not None:
+            idx = int(d.lookup([aggregate_id])[0])
+            return None if idx < 0 else idx
+        return self._keys.get(aggregate_id)
+
     def get_aggregate(self, aggregate_id: str):
-        idx = self.keys.get(aggregate_id)
+        if self._decoder is not None:
+            with self._device_lock:
+                if self._decoder is not None:
+                    return self._get_aggregate(aggregate_id, device=True)
+        return self._get_aggregate(aggregate_id, device=False)
+
+    def _get_aggregate(self, aggregate_id: str, device: bool):
+        idx = self._row_of(aggregate_id) if device else self._keys.get(aggregate_id)
         if idx is None or idx >= self.engine.n_agg:
             return None
-        raw = self.engine.get_raw(idx)
+        raw = self.engine.gather([idx])[0] if device else self.engine.get_raw(idx)  # (no mirror on the device route: surge_replay_gather)
         if int(raw["flags"]) & STATE_POISONED:
             raise AggregateInitializationException(
                 f"replay of aggregate {aggregate_id!r} hit an event whose handler throws; state is frozen before it"
