@@ -474,6 +474,30 @@ int32_t surge_device_decoder_key_table(surge_device_decoder* d, const uint8_t** 
  * One caller at a time per decoder (the host form stages into buffers the decoder owns). */
 int32_t surge_device_decoder_lookup(surge_device_decoder* d, const uint8_t* ids_utf8, const int64_t* id_off, int64_t n, int64_t* idx_out);
 int32_t surge_device_decoder_lookup_device(surge_device_decoder* d, const uint8_t* d_ids_utf8, const int64_t* d_id_off, int64_t n, int64_t* d_idx_out);
+/* The key table, read IN KEY ORDER.  The decoder keeps a permutation of the dense indices sorted by the ids' bytes as unsigned
+ * bytes, a proper prefix in front of the longer id ("a" < "a\0" < "a\x01"): the order of Kafka's Bytes comparator — a
+ * KeyValueStore's range / all — and, for valid UTF-8, of the code points.  It is built on the device on first use and whenever
+ * the table has grown since (a push that interns a new id leaves it stale; clear and a re-seed of the hash function do not):
+ * passes over four bytes of every id, most significant first, until every id stands alone — *passes_out of the last build.  It
+ * costs 8 bytes per id; more than 2^29 ids are SURGE_E_UNSUPPORTED.
+ *   - surge_device_decoder_range_device: the rows whose id k satisfies from <= k <= to, both ends inclusive, ascending, to the
+ *     DEVICE array d_rows_out; the bounds are HOST bytes.  from == NULL: unbounded below; to == NULL: unbounded above (NULL, NULL =
+ *     every id); a zero-length bound with a non-NULL pointer is the empty id.  *n_out is always the number of matches; when that is
+ *     more than `capacity`: SURGE_E_RANGE, nothing written.  from > to: SURGE_OK, 0 rows.  An id whose last record was a tombstone
+ *     is in the order (its row reads SURGE_READ_NONE).  Two binary searches on the device, 16 bytes back, one copy.
+ *   - surge_device_decoder_gather_keys_device: the ids of a DEVICE row list, back to back: id q =
+ *     d_utf8_out[d_off_out[q] .. d_off_out[q+1]) (n + 1 offsets).  A row outside [0, n_keys): SURGE_E_INVALID; more bytes than
+ *     utf8_capacity: SURGE_E_RANGE with *total_bytes_out set — both found before anything is written.
+ *   - surge_device_decoder_key_order: where the order lives (n_keys entries, the decoder's: valid until the next push that interns
+ *     an id, or destroy; NULL for an empty table); builds it if stale.
+ * Events decoders, state decoders and continued ones alike; a decoder that has interned nothing answers 0 rows.  SURGE_E_STATE
+ * while a push is unfinished and on a poisoned decoder; SURGE_E_INVALID for a NULL decoder, a negative length or capacity.  The
+ * calls run on the decoder's stream and return when their results are there.  One caller at a time per decoder. */
+int32_t surge_device_decoder_range_device(surge_device_decoder* d, const uint8_t* from_utf8, int64_t from_len, const uint8_t* to_utf8, int64_t to_len,
+                                          int64_t* d_rows_out, int64_t capacity, int64_t* n_out);
+int32_t surge_device_decoder_gather_keys_device(surge_device_decoder* d, const int64_t* d_rows, int64_t n, uint8_t* d_utf8_out, int64_t utf8_capacity,
+                                                int64_t* d_off_out, int64_t* total_bytes_out);
+int32_t surge_device_decoder_key_order(surge_device_decoder* d, const int64_t** d_order, int64_t* n_keys_out, int64_t* passes_out);
 /* [0] records seen, [1] delivered, [2] flush records skipped, [3] Double values re-parsed on the host */
 int32_t surge_device_decoder_counters(const surge_device_decoder* d, int64_t out[4]);
 /* [0..3] the counters above, [4] re-seeds of the key table's hash function — two different aggregate ids with the same

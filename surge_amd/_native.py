@@ -156,6 +156,9 @@ INGEST_EXPORTS = (
     "surge_device_decoder_key_table",
     "surge_device_decoder_lookup",
     "surge_device_decoder_lookup_device",
+    "surge_device_decoder_range_device",
+    "surge_device_decoder_gather_keys_device",
+    "surge_device_decoder_key_order",
     "surge_device_decoder_counters",
     "surge_device_decoder_stats",
     "surge_event_json_validate",
@@ -427,6 +430,9 @@ def load() -> ctypes.CDLL:
         "surge_device_decoder_key_table": ([vp, ctypes.POINTER(vp), ctypes.POINTER(vp)], i32),
         "surge_device_decoder_lookup": ([vp, vp, vp, i64, vp], i32),
         "surge_device_decoder_lookup_device": ([vp, vp, vp, i64, vp], i32),
+        "surge_device_decoder_range_device": ([vp, vp, i64, vp, i64, vp, i64, ctypes.POINTER(i64)], i32),
+        "surge_device_decoder_gather_keys_device": ([vp, vp, i64, vp, i64, vp, ctypes.POINTER(i64)], i32),
+        "surge_device_decoder_key_order": ([vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "surge_device_decoder_counters": ([vp, ctypes.POINTER(i64 * 4)], i32),
         "surge_device_decoder_stats": ([vp, ctypes.POINTER(i64 * 8)], i32),
         "surge_event_json_validate": ([vp], i32),

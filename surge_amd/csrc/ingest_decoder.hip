@@ -16,7 +16,8 @@
 // State mode (surge_device_decoder_create_states) reads the compacted STATE topic with the same stages: the id is the whole key,
 // a null value is a delivered tombstone, no value is decoded — stage 2 gathers the delivered records' value bytes into one
 // buffer behind value_off, and surge_device_decoder_load_states hands them to surge_replay_decode_json_states.
-// Between pushes the key table answers reads: surge_device_decoder_lookup[_device], id -> dense index or -1 (lookup_kernel).
+// Between pushes the key table answers reads: surge_device_decoder_lookup[_device], id -> dense index or -1 (lookup_kernel), and
+// in key order surge_device_decoder_range_device / _gather_keys_device / _key_order (ingest_order.hip; the pass loop is here).
 #include <cstdio>
 #include <cstdlib>
 
@@ -497,6 +498,152 @@ int32_t surge_device_decoder_lookup(surge_device_decoder* d, const uint8_t* ids_
   if (rc == OK) DCHK(d, hipMemcpyAsync(idx_out, d->lk_idx.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
   DCHK(d, hipStreamSynchronize(st));  // (off is this call's)
   return rc;
+}
+
+// ---- reads in key order (ingest_order.hip) -------------------------------------------------------------------------------------
+namespace {
+
+int32_t readable(surge_device_decoder* d) {
+  if (d->n_pending != 0) return dfail(d, SURGE_E_STATE, "asynchronous pushes are pending: finish them first (their keys have no ids yet)");
+  if (d->poisoned) return dfail(d, SURGE_E_STATE, "an earlier push failed on the device half way: destroy this decoder and create a new one");
+  return OK;
+}
+
+// d->ord = the dense indices in key order, built when the table has grown since the last build.  Most significant chunk first:
+// a pass sorts every key by (its group, its next four bytes, how many it has left), then the groups are re-numbered; the loop
+// ends when every group is one key.  (Unique keys: a group of several holds only keys that go on, so that is after at most
+// ceil(max_len / 4) + 1 passes; a pass in which no key had a byte left ends it whatever the table holds.)  Eight bytes come
+// back per pass.  The scratch — 28 bytes per key and rocPRIM's — goes when the build is over; ord stays, 8 bytes per key.
+int32_t ensure_order(surge_device_decoder* d) {
+  const int64_t n = d->n_keys;
+  if (d->ord_keys == n) return OK;
+  if (n > kOrderMaxKeys) return dfail(d, E_UNSUPPORTED, "more than 2^29 aggregate ids: the key order sorts 29 bits of group");
+  hipStream_t st = d->stream;
+  d->ord_keys = -1;
+  int64_t passes = 0;
+  if (n > 0) {
+    DCHK(d, d->ord.reserve((size_t)n * 8, false, st));
+    Buf key_a, key_b, idx_a, idx_b, grp, flag, live, temp;
+    OrderScratch sc{};
+    DCHK(d, order_temp_bytes(n, &sc.temp_bytes, st));
+    DCHK(d, key_a.reserve((size_t)n * 8, false, st));
+    DCHK(d, key_b.reserve((size_t)n * 8, false, st));
+    for (Buf* b : {&idx_a, &idx_b, &grp, &flag}) DCHK(d, b->reserve((size_t)n * 4, false, st));
+    DCHK(d, live.reserve(4, false, st));
+    DCHK(d, temp.reserve(sc.temp_bytes ? sc.temp_bytes : 1, false, st));
+    sc.key_in = (unsigned long long*)key_a.p;
+    sc.key_out = (unsigned long long*)key_b.p;
+    sc.idx_in = (uint32_t*)idx_a.p;
+    sc.idx_out = (uint32_t*)idx_b.p;
+    sc.grp = (uint32_t*)grp.p;
+    sc.flag = (uint32_t*)flag.p;
+    sc.live = (uint32_t*)live.p;
+    sc.temp = temp.p;
+    DCHK(d, launch_order_init(sc, n, st));
+    int64_t groups = 1;
+    while (groups < n) {
+      int group_bits = 0;
+      while ((1ll << group_bits) < groups) ++group_bits;
+      DCHK(d, launch_order_pass(keys_of(d), passes, group_bits, sc, st));
+      ++passes;
+      uint32_t last_group = 0, had_bytes = 0;
+      DCHK(d, hipMemcpyAsync(&last_group, sc.grp + (n - 1), 4, hipMemcpyDeviceToHost, st));
+      DCHK(d, hipMemcpyAsync(&had_bytes, sc.live, 4, hipMemcpyDeviceToHost, st));
+      DCHK(d, hipStreamSynchronize(st));
+      groups = (int64_t)last_group + 1;
+      if (!had_bytes) break;
+    }
+    DCHK(d, launch_order_finish(sc, n, (int64_t*)d->ord.p, st));
+    DCHK(d, hipStreamSynchronize(st));  // (the scratch is freed on the way out)
+    if (groups < n) return dfail(d, SURGE_E_CORRUPT, "the key table holds the same id twice");
+  }
+  d->ord_keys = n;
+  d->ord_passes = passes;
+  return OK;
+}
+
+}  // namespace
+
+int32_t surge_device_decoder_key_order(surge_device_decoder* d, const int64_t** d_order, int64_t* n_keys_out, int64_t* passes_out) {
+  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  int32_t rc = readable(d);
+  if (rc != OK) return rc;
+  DeviceScope scope(d->device);
+  if ((rc = ensure_order(d)) != OK) return rc;
+  if (d_order) *d_order = d->n_keys ? (const int64_t*)d->ord.p : nullptr;
+  if (n_keys_out) *n_keys_out = d->n_keys;
+  if (passes_out) *passes_out = d->ord_passes;
+  return OK;
+}
+
+int32_t surge_device_decoder_range_device(surge_device_decoder* d, const uint8_t* from_utf8, int64_t from_len, const uint8_t* to_utf8, int64_t to_len,
+                                          int64_t* d_rows_out, int64_t capacity, int64_t* n_out) {
+  // (what the numbers alone decide comes first: it is refused the same with and without a decoder)
+  if (from_len < 0 || to_len < 0 || capacity < 0) return dfail(d, E_INVALID, "a negative length or capacity");
+  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (!n_out) return dfail(d, E_INVALID, "bad argument");
+  if (from_len >= (1ll << 31) || to_len >= (1ll << 31)) return dfail(d, E_INVALID, "a bound is shorter than 2^31 bytes");
+  int32_t rc = readable(d);
+  if (rc != OK) return rc;
+  *n_out = 0;
+  if (d->n_keys == 0) return OK;
+  DeviceScope scope(d->device);
+  if ((rc = ensure_order(d)) != OK) return rc;
+  hipStream_t st = d->stream;
+  // the two bounds, each with the 16 bytes behind it that the compare's loads may touch; a NULL bound has the length -1
+  const int64_t fl = from_utf8 ? from_len : -1, tl = to_utf8 ? to_len : -1;
+  const int64_t to_at = ((fl > 0 ? fl : 0) + 15) / 16 * 16 + 16;
+  DCHK(d, d->rd_bounds.reserve((size_t)(to_at + (tl > 0 ? tl : 0) + 16), false, st));
+  DCHK(d, d->rd_lo_hi.reserve(16, false, st));
+  if (fl > 0) DCHK(d, hipMemcpyAsync(d->rd_bounds.p, from_utf8, (size_t)fl, hipMemcpyHostToDevice, st));
+  if (tl > 0) DCHK(d, hipMemcpyAsync((uint8_t*)d->rd_bounds.p + to_at, to_utf8, (size_t)tl, hipMemcpyHostToDevice, st));
+  DCHK(d, launch_order_bounds(keys_of(d), (const int64_t*)d->ord.p, (const uint8_t*)d->rd_bounds.p, fl, to_at, tl, (int64_t*)d->rd_lo_hi.p, st));
+  int64_t lo_hi[2] = {0, 0};
+  DCHK(d, hipMemcpyAsync(lo_hi, d->rd_lo_hi.p, 16, hipMemcpyDeviceToHost, st));
+  DCHK(d, hipStreamSynchronize(st));
+  if (lo_hi[0] < 0 || lo_hi[1] > d->n_keys) return dfail(d, E_DEVICE, "the bound search left the key order");
+  const int64_t n = lo_hi[1] > lo_hi[0] ? lo_hi[1] - lo_hi[0] : 0;  // (from > to: nothing)
+  *n_out = n;
+  if (n > capacity) return dfail(d, SURGE_E_RANGE, "d_rows_out is too small (see *n_out)");
+  if (n == 0) return OK;
+  if (!d_rows_out) return dfail(d, E_INVALID, "d_rows_out is NULL");
+  DCHK(d, hipMemcpyAsync(d_rows_out, (const int64_t*)d->ord.p + lo_hi[0], (size_t)n * 8, hipMemcpyDeviceToDevice, st));
+  DCHK(d, hipStreamSynchronize(st));
+  return OK;
+}
+
+int32_t surge_device_decoder_gather_keys_device(surge_device_decoder* d, const int64_t* d_rows, int64_t n, uint8_t* d_utf8_out, int64_t utf8_capacity,
+                                                int64_t* d_off_out, int64_t* total_bytes_out) {
+  if (n < 0 || utf8_capacity < 0) return dfail(d, E_INVALID, "a negative length or capacity");
+  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (!d_off_out || (n > 0 && !d_rows)) return dfail(d, E_INVALID, "bad argument");
+  const int32_t rc = readable(d);
+  if (rc != OK) return rc;
+  DeviceScope scope(d->device);
+  hipStream_t st = d->stream;
+  KeyGatherScratch sc{};
+  DCHK(d, key_gather_temp_bytes(n, &sc.temp_bytes, st));
+  DCHK(d, d->gk_len.reserve((size_t)(n + 1) * 8, false, st));
+  DCHK(d, d->gk_at.reserve((size_t)(n + 1) * 8, false, st));
+  DCHK(d, d->gk_bad.reserve(4, false, st));
+  DCHK(d, d->gk_temp.reserve(sc.temp_bytes ? sc.temp_bytes : 1, false, st));
+  sc.len = (unsigned long long*)d->gk_len.p;
+  sc.at = (unsigned long long*)d->gk_at.p;
+  sc.bad = (uint32_t*)d->gk_bad.p;
+  sc.temp = d->gk_temp.p;
+  DCHK(d, launch_key_lengths(keys_of(d), d_rows, n, sc, st));
+  unsigned long long total = 0;
+  uint32_t bad = 0;
+  DCHK(d, hipMemcpyAsync(&total, sc.at + n, 8, hipMemcpyDeviceToHost, st));
+  DCHK(d, hipMemcpyAsync(&bad, sc.bad, 4, hipMemcpyDeviceToHost, st));
+  DCHK(d, hipStreamSynchronize(st));
+  if (bad) return dfail(d, E_INVALID, "a row is outside [0, n_keys)");
+  if (total_bytes_out) *total_bytes_out = (int64_t)total;
+  if ((int64_t)total > utf8_capacity) return dfail(d, SURGE_E_RANGE, "d_utf8_out is too small (see *total_bytes_out)");
+  if (total > 0 && !d_utf8_out) return dfail(d, E_INVALID, "d_utf8_out is NULL");
+  DCHK(d, launch_key_gather(keys_of(d), d_rows, n, sc, d_utf8_out, d_off_out, st));
+  DCHK(d, hipStreamSynchronize(st));
+  return OK;
 }
 
 int32_t surge_device_decoder_counters(const surge_device_decoder* d, int64_t out[4]) {

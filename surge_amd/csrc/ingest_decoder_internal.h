@@ -127,6 +127,11 @@ struct surge_device_decoder {
   // hash table + key table
   Buf t_slots, arena, key_off, key_hash;
   Buf lk_ids, lk_off, lk_idx;  // surge_device_decoder_lookup: the staged queries and their indices
+  // the key order (ingest_order.hip): valid while ord_keys == n_keys — a push that interns an id leaves it stale, the next read
+  // rebuilds it whole; clear and a re-seed do not touch the keys' bytes, so they do not touch it
+  Buf ord, rd_bounds, rd_lo_hi;  // n_keys dense indices in key order; a range's staged bounds and its two positions
+  Buf gk_len, gk_at, gk_bad, gk_temp;  // surge_device_decoder_gather_keys_device: lengths, their scan, the bad-row word
+  int64_t ord_keys = -1, ord_passes = 0;
   uint64_t t_cap = 0;
   std::atomic<uint64_t> seed{0};  // (stage 1 reads it once per push; stage 2 of an earlier push may move it on: PushSlot::seed)
   int64_t n_keys = 0, arena_bytes = 0;

@@ -1,7 +1,7 @@
 // ingest_device.h — what the translation units of the device decoder share.  Internal, like replay_internal.h: not part of
 // the C ABI.  Each stage is a unit of its own that knows the plain structs below and nothing of the decoder around it
 // (the host object: ingest_decoder.hip and its units ingest_stage1.hip, ingest_stage2.hip, ingest_handover.hip, which share
-// ingest_decoder_internal.h): ingest_crc.hip, ingest_lz4.hip, ingest_records.hip, ingest_intern.hip.  Their launch_* functions
+// ingest_decoder_internal.h): ingest_crc.hip, ingest_lz4.hip, ingest_records.hip, ingest_intern.hip, ingest_order.hip.  Their launch_* functions
 // enqueue on the stream they are given and return what the runtime said; none of them waits for the device.
 #pragma once
 
@@ -244,6 +244,37 @@ void launch_intern_rollback(const RecMeta* meta, int64_t n_rec, const Table& t, 
 // read-only, no push in flight: idx_out[i] = the dense index of the id ids[id_off[i] .. id_off[i + 1]), compared byte for byte, or -1;
 // `ids` must be readable 16 bytes behind its last id, as the arena is (keys_equal's loads)
 hipError_t launch_lookup(const uint8_t* ids, const int64_t* id_off, int64_t n, const KeyTable& k, uint64_t seed, int64_t* idx_out, hipStream_t st);
+
+// ---- ingest_order.hip: the key table in key order (unsigned bytes, a proper prefix first), and what reads through it ---------
+constexpr int64_t kOrderMaxKeys = 1ll << 29;  // a pass sorts (group << 35 | chunk << 3 | bytes left) as one 64-bit key: 29 bits of group
+struct OrderScratch {  // per build, n_keys entries each; freed behind it
+  unsigned long long *key_in, *key_out;
+  uint32_t *idx_in, *idx_out;  // (launch_order_pass swaps them: idx_in is always what the last pass sorted)
+  uint32_t *grp, *flag;
+  uint32_t* live;  // one word: did a key have a byte in the last pass
+  void* temp;
+  size_t temp_bytes;
+};
+hipError_t order_temp_bytes(int64_t n_keys, size_t* bytes, hipStream_t st);  // of OrderScratch::temp
+hipError_t launch_order_init(const OrderScratch& sc, int64_t n_keys, hipStream_t st);  // idx_in = 0, 1, 2, ...; one group
+// pass p: stable sort by (group, bytes [4p, 4p + 4) big-endian, bytes left clipped to 0..4) over 35 + group_bits bits, groups re-numbered:
+// afterwards grp[n_keys - 1] + 1 = groups, *live = a key had a byte
+hipError_t launch_order_pass(const KeyTable& k, int64_t pass, int group_bits, OrderScratch& sc, hipStream_t st);
+hipError_t launch_order_finish(const OrderScratch& sc, int64_t n_keys, int64_t* ord, hipStream_t st);
+// lo_hi[0] = lower_bound(from), lo_hi[1] = upper_bound(to) over ord; the bounds' bytes are bounds[0 .. from_len) and
+// bounds[to_at .. to_at + to_len), each readable 16 bytes behind its end; a negative length: no bound (0 / n_keys)
+hipError_t launch_order_bounds(const KeyTable& k, const int64_t* ord, const uint8_t* bounds, int64_t from_len, int64_t to_at, int64_t to_len, int64_t* lo_hi, hipStream_t st);
+struct KeyGatherScratch {  // (n + 1) entries each
+  unsigned long long *len, *at;
+  uint32_t* bad;  // one word: a row outside [0, n_keys)
+  void* temp;
+  size_t temp_bytes;
+};
+hipError_t key_gather_temp_bytes(int64_t n, size_t* bytes, hipStream_t st);
+// at[q] = bytes of the ids in front of rows[q] (at[n]: of all of them), *bad; nothing of the caller's is written
+hipError_t launch_key_lengths(const KeyTable& k, const int64_t* rows, int64_t n, const KeyGatherScratch& sc, hipStream_t st);
+// behind the checks: off_out[0 .. n] = at, the ids' bytes to out
+hipError_t launch_key_gather(const KeyTable& k, const int64_t* rows, int64_t n, const KeyGatherScratch& sc, uint8_t* out, int64_t* off_out, hipStream_t st);
 
 // ---- state mode (ingest_intern.hip): the kept records' VALUES move out of the push's staged bytes -------------------------------
 constexpr int kGatherRecs = 256;          // kept records per workgroup of the value gather

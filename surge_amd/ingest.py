@@ -661,6 +661,7 @@ class DeviceDecoder:
         self.states = bool(states)
         self._stream = stream  # the hipStream_t stage 2 and the lookups run on (None: the default stream)
         self._inflight = []
+        self.order_passes = 0  # passes of the key order's last build, as the last ``key_order()`` reported them
         c = template.to_c() if template is not None else None
         if states:
             rc = self._lib.surge_device_decoder_create_states(device, stream, ctypes.byref(self._h))
@@ -950,6 +951,79 @@ class DeviceDecoder:
                                                                          ctypes.c_void_p(out.data_ptr())))
                 current.wait_stream(mine)
         return out
+
+    # -- the key table in key order (unsigned bytes, a proper prefix first: Kafka's ``Bytes`` order, ``sorted`` on ``bytes``) --------
+    def _behind_torch(self):
+        """The decoder's stream waits for what torch's current stream has enqueued (a row list torch computed).  The calls below
+        return when their results are there, so nothing has to wait the other way round."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            mine = torch.cuda.ExternalStream(int(self._stream)) if self._stream else torch.cuda.default_stream(dev)
+            mine.wait_stream(torch.cuda.current_stream(dev))
+
+    def key_order(self):
+        """The dense indices in key order (``surge_device_decoder_key_order``): an ``int64`` CUDA tensor viewing the decoder's
+        array — valid until the next push that interns an id, or ``close`` — built now if the table has grown since the last
+        build.  ``order_passes`` says what that build took."""
+        import torch
+
+        po, n, passes = ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._lib.surge_device_decoder_key_order(self._h, ctypes.byref(po), ctypes.byref(n), ctypes.byref(passes)))
+        self.order_passes = int(passes.value)
+        dev = torch.device("cuda", self.device)
+        return _device_view(po, (n.value,), "<i8", dev) if n.value else torch.zeros(0, dtype=torch.int64, device=dev)
+
+    def range_rows(self, from_key=None, to_key=None):
+        """The rows whose id lies in ``[from_key, to_key]`` — both ends inclusive, as a Kafka Streams ``range`` — ascending by id
+        (``surge_device_decoder_range_device``): an ``int64`` CUDA tensor of the caller's.  A bound is ``str`` (its UTF-8), ``bytes``
+        or ``None`` (unbounded: ``range_rows()`` is every row in key order); ``b""`` is the empty id, not ``None``.  ``from_key >
+        to_key``: no row.  Two calls: the count, then the rows."""
+        import torch
+
+        def bound(k):
+            if k is None:
+                return None, 0
+            raw = k.encode("utf-8") if isinstance(k, str) else bytes(k)
+            return ctypes.create_string_buffer(raw, len(raw) + 1), len(raw)  # (never NULL, also for the empty id)
+
+        (pf, nf), (pt, nt) = bound(from_key), bound(to_key)
+        dev = torch.device("cuda", self.device)
+        n = ctypes.c_int64()
+        rc = self._lib.surge_device_decoder_range_device(self._h, pf, nf, pt, nt, None, 0, ctypes.byref(n))
+        if rc != -6:  # (SURGE_E_RANGE: there are rows, and no room was given)
+            self._check(rc)
+            return torch.zeros(0, dtype=torch.int64, device=dev)
+        out = torch.empty(n.value, dtype=torch.int64, device=dev)
+        self._behind_torch()
+        self._check(self._lib.surge_device_decoder_range_device(self._h, pf, nf, pt, nt, ctypes.c_void_p(out.data_ptr()), n.value, ctypes.byref(n)))
+        return out[: n.value]
+
+    def gather_keys(self, d_rows) -> List[bytes]:
+        """The ids of ``d_rows`` (an ``int64`` CUDA tensor of rows inside the table), in that order
+        (``surge_device_decoder_gather_keys_device``; one copy back).  A row outside ``[0, n_keys)`` raises ``IngestError`` (INVALID)."""
+        import torch
+
+        n = int(d_rows.numel())
+        if n == 0:
+            return []
+        dev = torch.device("cuda", self.device)
+        d_rows = d_rows.contiguous()
+        d_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        total = ctypes.c_int64(-1)
+        cap = 0
+        self._behind_torch()
+        for _ in range(2):  # (the first call says how many bytes the ids are)
+            d_out = torch.empty(max(cap, 1), dtype=torch.uint8, device=dev)
+            rc = self._lib.surge_device_decoder_gather_keys_device(self._h, ctypes.c_void_p(d_rows.data_ptr()), n, ctypes.c_void_p(d_out.data_ptr()), cap,
+                                                                   ctypes.c_void_p(d_off.data_ptr()), ctypes.byref(total))
+            if rc != -6 or total.value <= cap:
+                break
+            cap = total.value
+        self._check(rc)
+        raw, off = d_out[: total.value].cpu().numpy().tobytes(), d_off.cpu().numpy().tolist()
+        return [raw[off[q]:off[q + 1]] for q in range(n)]
 
     def counters(self) -> dict:
         c = (ctypes.c_int64 * 4)()

@@ -16,7 +16,9 @@ format stays the plugin's: the engine hands a fixed-width state to ``writeState`
 
 A restore with ``host_keys=False`` keeps the device decoder instead: its key table on the GPU says which row an id is
 (``DeviceDecoder.lookup``) and the state encoders write the bytes of the rows asked for (``encode.encode_rows``), so no id
-is downloaded and no state mirrored until something needs the host table (``GpuReplayStateStore.keys``).
+is downloaded and no state mirrored until something needs the host table (``GpuReplayStateStore.keys``).  Reads in key order —
+``range_bytes`` / ``all_bytes`` / ``substates_for_aggregate`` / ``num_entries``, and ``GpuReplayKeyValueStore(device_scans=True)``
+over them — stay on that route too: the decoder keeps its ids sorted (``DeviceDecoder.range_rows``).
 """
 from __future__ import annotations
 
@@ -55,6 +57,7 @@ class GpuReplayStateStore:
         self._decoder = None
         self._device_lock = threading.RLock()  # the device route serves one reader at a time (decoder and engine scratch)
         self._uploaded_keys = None  # a host-keys store's key table on the device, for ``get_aggregate_bytes_many``: (n_keys, d_utf8, d_off)
+        self._sorted_keys = None  # ... and its ids in key order, for ``range_bytes``: (n_keys, ids)
         #: what ``get_aggregate_bytes`` writes on the device route: the ``encode.JsonTemplate`` of the model's serialized state
         #: (``None``: ``JsonTemplate.counter()``) and its envelope; ``restore_from_state_topic`` sets both from its arguments
         self.read_template = None
@@ -94,6 +97,7 @@ class GpuReplayStateStore:
         self._drop_decoder()
         self._keys = table
         self._uploaded_keys = None
+        self._sorted_keys = None
 
     def _drop_decoder(self) -> None:
         with self._device_lock:
@@ -127,6 +131,7 @@ class GpuReplayStateStore:
             keys.intern(k)
         self._keys = keys
         self._uploaded_keys = None
+        self._sorted_keys = None
 
     @contextlib.contextmanager
     def _decoding_onto_the_defaults(self):
@@ -646,6 +651,101 @@ class GpuReplayStateStore:
         value = (kind == READ_VALUE).tolist()
         return [raw[off[q]:off[q + 1]] if value[q] else None for q in range(len(ids))]
 
+    # -- reads in key order: KafkaStreamsKeyValueStore.range / all, SurgeAggregateStore.getSubstatesForAggregate ----------------
+    def _sorted_host_keys(self) -> List[str]:
+        """The host table's ids in key order (code points: the order of their UTF-8 bytes), sorted once per table size."""
+        keys = self._keys
+        if self._sorted_keys is None or self._sorted_keys[0] != len(keys):
+            self._sorted_keys = (len(keys), sorted(keys.keys))
+        return self._sorted_keys[1]
+
+    def range_bytes(self, from_key: Optional[str] = None, to_key: Optional[str] = None, template=None, envelope: Optional[str] = None,
+                    page_rows: int = 1 << 20) -> Iterator[Tuple[str, bytes]]:
+        """``(id, writeState(state).value)`` of every aggregate whose id lies in ``[from_key, to_key]`` — both ends inclusive,
+        ``None``: unbounded — ascending by the ids' UTF-8 bytes: ``KafkaStreamsKeyValueStore.range``
+        (``.../streams/KafkaStreamsKeyValueStore.scala:41-51``) over the recovered state.  On the device route the rows come from
+        the decoder's key order (``DeviceDecoder.range_rows``: two binary searches and a slice), their bytes from
+        ``encode.encode_rows`` and their ids from ``DeviceDecoder.gather_keys``, ``page_rows`` rows at a time: the store stays on
+        the device route, no host table is built, no mirror published, and never more than a page of text is held.  With a host
+        table the rows are a ``bisect`` over its sorted ids and the bytes the same encoders'.  Aggregates that are ``None`` or
+        ended are passed over; a poisoned aggregate in the range raises ``AggregateInitializationException`` naming it when its
+        page is reached, as the point read does.  ``template`` / ``envelope`` default to ``read_template`` / ``read_envelope``."""
+        import torch
+
+        from .encode import READ_POISONED, READ_VALUE, JsonTemplate, check_envelope, encode_rows, key_table_utf8
+
+        envelope = self.read_envelope if envelope is None else envelope
+        check_envelope(envelope)
+        template = template or self.read_template or JsonTemplate.counter()
+        page_rows = max(1, int(page_rows))
+        eng = self.engine
+        dev = torch.device("cuda", eng.device)
+        with self._device_lock:
+            strings = self.state_string_columns()
+            for c in _str_columns(template):
+                if c >= len(strings) or strings[c] is None:
+                    raise ValueError(f"the template names string column {c}, and nothing restored it")
+            d = self._decoder
+            if d is not None:
+                d_rows = d.range_rows(from_key, to_key)
+                host_ids = None
+            else:
+                order = self._sorted_host_keys()
+                lo = 0 if from_key is None else bisect.bisect_left(order, from_key)
+                hi = len(order) if to_key is None else bisect.bisect_right(order, to_key)
+                index, n_agg = self._keys.index, eng.n_agg
+                host_ids = [k for k in order[lo:hi] if index[k] < n_agg]
+                d_rows = torch.from_numpy(np.fromiter((index[k] for k in host_ids), dtype=np.int64, count=len(host_ids))).to(dev)
+        for first in range(0, int(d_rows.numel()), page_rows):
+            with self._device_lock:
+                if self._decoder is not d:
+                    raise RuntimeError("the store's key table moved while a range was being read: start the range again")
+                page = d_rows[first:first + page_rows]
+                if d is not None:
+                    d_utf8, d_key_off = d.device_key_table()
+                else:
+                    if self._uploaded_keys is None or self._uploaded_keys[0] != len(self._keys):
+                        kd, ko = key_table_utf8(self._keys.keys)
+                        self._uploaded_keys = (len(self._keys), torch.from_numpy(kd).to(dev), torch.from_numpy(ko).to(dev))
+                    _, d_utf8, d_key_off = self._uploaded_keys
+                out, out_off, d_kind = encode_rows(eng, template, d_utf8, d_key_off, page, envelope=envelope, strings=strings)
+                kind = d_kind.cpu().numpy()
+                bad = np.flatnonzero(kind == READ_POISONED)
+                if bad.shape[0]:
+                    q = int(bad[0])
+                    name = host_ids[first + q] if d is None else d.gather_keys(page[q:q + 1])[0].decode("utf-8")
+                    raise AggregateInitializationException(f"replay of aggregate {name!r} hit an event whose handler throws; state is frozen before it")
+                kept = np.flatnonzero(kind == READ_VALUE)
+                if d is None:
+                    ids = [host_ids[first + int(q)] for q in kept]
+                else:
+                    ids = [k.decode("utf-8") for k in d.gather_keys(page[torch.from_numpy(kept).to(dev)])] if kept.shape[0] else []
+                raw, off = out.cpu().numpy().tobytes(), out_off.cpu().numpy().tolist()
+            for k, q in zip(ids, kept.tolist()):
+                yield k, raw[off[q]:off[q + 1]]
+
+    def all_bytes(self, template=None, envelope: Optional[str] = None, page_rows: int = 1 << 20) -> Iterator[Tuple[str, bytes]]:
+        """``KafkaStreamsKeyValueStore.all`` (``KafkaStreamsKeyValueStore.scala:28-39``): ``range_bytes`` without bounds."""
+        return self.range_bytes(None, None, template, envelope, page_rows)
+
+    def substates_for_aggregate(self, aggregate_id: str) -> List[Tuple[str, bytes]]:
+        """``SurgeAggregateStore.getSubstatesForAggregate`` (``.../streams/SurgeAggregateStore.scala:13-21``): the range
+        ``[aggregate_id, aggregate_id + ":~"]``, of which the keys are kept whose text in front of the first ``:`` is the id —
+        the reference's filter, applied here over the few results."""
+        return [(k, v) for k, v in self.range_bytes(aggregate_id, aggregate_id + ":~") if k.split(":", 1)[0] == aggregate_id]
+
+    def num_entries(self) -> int:
+        """How many aggregates ``all_bytes`` would list if none of them were poisoned: rows that are present and not poisoned,
+        counted on the device from the resident states' flag words — no text is composed, no state copied."""
+        with self._device_lock:
+            eng = self.engine
+            n = eng.n_agg
+            if not n:
+                return 0
+            eng.synchronize()
+            flags = eng.device_state()[:n, STATE_DTYPE.fields["flags"][1]]  # (both flags are in the word's low byte)
+            return int(((flags & (STATE_PRESENT | STATE_POISONED)) == STATE_PRESENT).sum().item())
+
     def _row_of(self, aggregate_id: str):
         """The id's row, or ``None``: from the device key table while the store is on the device route."""
         d = self._decoder
@@ -698,9 +798,12 @@ class GpuReplayKeyValueStore:
 
     _TOMBSTONE = object()
 
-    def __init__(self, name: str, recovered: Optional[GpuReplayStateStore] = None):
+    def __init__(self, name: str, recovered: Optional[GpuReplayStateStore] = None, device_scans: bool = False):
         self.name = name
         self.recovered = recovered
+        #: ``True``: while ``recovered`` is on the device route, ``all`` / ``range`` / ``all_values`` / ``approximate_num_entries``
+        #: read it through ``range_bytes`` / ``num_entries`` and leave it there; ``False``: they build its host table, as ever
+        self.device_scans = bool(device_scans)
         self._overlay: Dict[str, object] = {}
 
     def put(self, key: str, value: Optional[bytes]) -> None:
@@ -723,7 +826,34 @@ class GpuReplayKeyValueStore:
             ks.update(self.recovered.keys.keys)
         return sorted(ks)
 
+    def _scans_on_the_device(self) -> bool:
+        return self.device_scans and self.recovered is not None and self.recovered.device_route
+
+    def _merged(self, from_key: Optional[str], to_key: Optional[str]) -> Iterator[Tuple[str, bytes]]:
+        """The overlay's keys inside the bounds, sorted, merged with ``recovered.range_bytes`` on the keys' UTF-8 bytes: the
+        overlay wins, a tombstone drops the key."""
+        lo = None if from_key is None else from_key.encode("utf-8")
+        hi = None if to_key is None else to_key.encode("utf-8")
+        over = sorted((kb, k, v) for kb, k, v in ((k.encode("utf-8"), k, v) for k, v in self._overlay.items())
+                      if (lo is None or lo <= kb) and (hi is None or kb <= hi))
+        at = 0
+        for k, v in self.recovered.range_bytes(from_key, to_key):
+            kb = k.encode("utf-8")
+            while at < len(over) and over[at][0] < kb:
+                if over[at][2] is not self._TOMBSTONE:
+                    yield over[at][1], over[at][2]
+                at += 1
+            if at < len(over) and over[at][0] == kb:
+                continue  # (the overlay's entry for this key comes in the next round, or behind the loop)
+            yield k, v
+        for _, k, v in over[at:]:
+            if v is not self._TOMBSTONE:
+                yield k, v
+
     def all(self) -> Iterator[Tuple[str, bytes]]:
+        if self._scans_on_the_device():
+            yield from self._merged(None, None)
+            return
         for k in self._all_keys():
             v = self.get(k)
             if v is not None:
@@ -733,6 +863,9 @@ class GpuReplayKeyValueStore:
         return [v for _, v in self.all()]
 
     def range(self, from_key: str, to_key: str) -> Iterator[Tuple[str, bytes]]:
+        if self._scans_on_the_device():
+            yield from self._merged(from_key, to_key)
+            return
         ks = self._all_keys()
         for k in ks[bisect.bisect_left(ks, from_key): bisect.bisect_right(ks, to_key)]:
             v = self.get(k)
@@ -740,6 +873,21 @@ class GpuReplayKeyValueStore:
                 yield k, v
 
     def approximate_num_entries(self) -> int:
+        if self._scans_on_the_device():
+            # what the device counts (``num_entries``: no text composed), corrected by the overlay's keys: one more for a value
+            # over nothing, one fewer for a tombstone over a value
+            rec = self.recovered
+            keys = list(self._overlay)
+            try:
+                there = [v is not None for v in rec.get_aggregate_bytes_many(keys, rec.read_template, rec.read_envelope)]
+            except AggregateInitializationException:  # (a poisoned aggregate under the overlay: it is not counted, ask one by one)
+                there = []
+                for k in keys:
+                    try:
+                        there.append(rec.get_aggregate_bytes(k) is not None)
+                    except AggregateInitializationException:
+                        there.append(False)
+            return rec.num_entries() + sum((self._overlay[k] is not self._TOMBSTONE) - t for k, t in zip(keys, there))
         return sum(1 for _ in self.all())
 
 
