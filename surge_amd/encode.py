@@ -84,12 +84,18 @@ def play_json_double(x: float) -> str:
     return buf.raw[:n].decode("ascii")
 
 
-def key_table_utf8(keys: Sequence[str]) -> Tuple[np.ndarray, np.ndarray]:
-    enc = [k.encode("utf-8") for k in keys]
+def key_table_utf8(keys: Sequence[Union[str, bytes]], slack: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """Ids packed for the device: ``(their UTF-8 bytes, n + 1 int64 offsets)``.  ``bytes`` ids are taken as they stand;
+    ``slack``: that many readable zero bytes behind the last id (``DeviceDecoder.lookup_device`` asks for 16)."""
+    try:
+        enc = [k.encode("utf-8") for k in keys]
+    except AttributeError:  # (some are bytes already)
+        enc = [k.encode("utf-8") if isinstance(k, str) else bytes(k) for k in keys]
     off = np.zeros(len(enc) + 1, dtype=np.int64)
     if enc:
         np.cumsum([len(e) for e in enc], out=off[1:])
-    data = np.frombuffer(b"".join(enc), dtype=np.uint8).copy() if enc else np.zeros(0, np.uint8)
+    data = np.zeros(int(off[-1]) + slack, dtype=np.uint8)
+    data[: int(off[-1])] = np.frombuffer(b"".join(enc), dtype=np.uint8)
     return data, off
 
 

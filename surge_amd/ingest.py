@@ -15,6 +15,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 
 from . import _native
+from .encode import key_table_utf8
 from .log import KeyTable
 from .schema import EVENT_DTYPE
 
@@ -920,12 +921,8 @@ class DeviceDecoder:
         """Which row is each id (``surge_device_decoder_lookup``): ``ids`` are ``str`` (UTF-8) or ``bytes``; returns ``np.int64[n]``,
         an id's dense index — its position in first-delivered order — or ``-1`` when the table does not hold it.  Compared byte
         for byte as it stands (no cut at ``:``).  Every push has to be finished (``IngestError``, STATE, otherwise)."""
-        enc = [k.encode("utf-8") if isinstance(k, str) else bytes(k) for k in ids]
-        n = len(enc)
-        off = np.zeros(n + 1, dtype=np.int64)
-        if n:
-            np.cumsum([len(e) for e in enc], out=off[1:])
-        data = np.frombuffer(b"".join(enc), dtype=np.uint8) if off[-1] else np.zeros(1, np.uint8)
+        data, off = key_table_utf8(ids, slack=1)  # (one byte, so that no id at all still has an address)
+        n = off.shape[0] - 1
         out = np.empty(n, dtype=np.int64)
         self._check(self._lib.surge_device_decoder_lookup(self._h, data.ctypes.data_as(ctypes.c_void_p), off.ctypes.data_as(ctypes.c_void_p), n,
                                                           out.ctypes.data_as(ctypes.c_void_p)))

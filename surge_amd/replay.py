@@ -309,6 +309,24 @@ class ReplayEngine:
         self._check(self._lib.surge_replay_snapshot(self._h, _np_ptr(out), None))
         return out
 
+    def snapshot_delta(self, d_kind, commit: bool):
+        """What changed since the last committed snapshot (``surge_replay_snapshot_delta``): ``d_kind``, a ``uint8`` CUDA tensor
+        ``n_agg`` long, takes each aggregate's ``SURGE_SNAP_*`` (skip / value / tombstone); ``commit`` makes the current states
+        the baseline of the aggregates reported.  Returns ``(n_values, n_tombstones)``."""
+        nv, nt = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._lib.surge_replay_snapshot_delta(self._h, ctypes.c_void_p(d_kind.data_ptr()), ctypes.byref(nv), ctypes.byref(nt), int(bool(commit))))
+        return nv.value, nt.value
+
+    @contextlib.contextmanager
+    def decoding_onto(self, defaults):
+        """Inside the block the bytes a decoded state's template does not name are ``defaults``', a 64-byte ctypes state (an
+        algebra's ``to_c().default_state``: ``surge_replay_set_decode_base``); zeros again on the way out."""
+        self._check(self._lib.surge_replay_set_decode_base(self._h, ctypes.byref(defaults)))
+        try:
+            yield
+        finally:
+            self._check(self._lib.surge_replay_set_decode_base(self._h, None))
+
     def get(self, agg_idx: int) -> Optional[np.ndarray]:
         """Fixed-width state of one aggregate, or ``None`` when it is absent (KTable miss)."""
         out = np.zeros(1, dtype=self.state_dtype)

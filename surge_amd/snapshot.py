@@ -297,12 +297,11 @@ class BulkSnapshotPublisher:
         lib = _native.load()
         t0 = time.perf_counter()
         d_kind = torch.zeros(n, dtype=torch.uint8, device=self.device)
-        nv, nt = ctypes.c_int64(), ctypes.c_int64()
-        eng._check(lib.surge_replay_snapshot_delta(eng._h, ctypes.c_void_p(d_kind.data_ptr()), ctypes.byref(nv), ctypes.byref(nt), 0))
+        nv, nt = eng.snapshot_delta(d_kind, commit=False)
         self._pending_kind = None
         eng._check(lib.surge_replay_set_encode_filter(eng._h, ctypes.c_void_p(d_kind.data_ptr())))
         try:
-            d_out, d_off = encode_states(eng, self.template, self.d_keys, self.d_key_off, capacity_hint=max(64, 96 * nv.value + int(self.d_keys.numel())) if not self.strings else 0,
+            d_out, d_off = encode_states(eng, self.template, self.d_keys, self.d_key_off, capacity_hint=max(64, 96 * nv + int(self.d_keys.numel())) if not self.strings else 0,
                                           strings=self.strings, envelope=self.envelope)
         finally:
             eng._check(lib.surge_replay_set_encode_filter(eng._h, None))
@@ -315,8 +314,8 @@ class BulkSnapshotPublisher:
             if commit:
                 self.commit_published()
             t3 = time.perf_counter()
-            self.timings = {"gpu_delta_and_encode_ms": (t1 - t0) * 1e3, "device_framing_copy_crc_ms": (t3 - t1) * 1e3, "values": nv.value,
-                            "tombstones": nt.value, "text_bytes": int(d_off[n].item()), "batches": self.framer.batches}
+            self.timings = {"gpu_delta_and_encode_ms": (t1 - t0) * 1e3, "device_framing_copy_crc_ms": (t3 - t1) * 1e3, "values": nv,
+                            "tombstones": nt, "text_bytes": int(d_off[n].item()), "batches": self.framer.batches}
             if self.framer.compression != "none":
                 self.timings["record_batch_bytes"] = sum(len(v) for v in out.values())
                 self.timings["uncompressed_bytes"] = self.framer.uncompressed_bytes
@@ -340,7 +339,7 @@ class BulkSnapshotPublisher:
             self.commit_published()
         t3 = time.perf_counter()
         self.timings = {"gpu_delta_and_encode_ms": (t1 - t0) * 1e3, "d2h_ms": (t2 - t1) * 1e3, "record_batches_ms": (t3 - t2) * 1e3,
-                        "values": nv.value, "tombstones": nt.value, "text_bytes": int(text.nbytes)}
+                        "values": nv, "tombstones": nt, "text_bytes": int(text.nbytes)}
         return out
 
     def publish_async(self, timestamp_ms: Optional[int] = None) -> "PendingPublish":
@@ -372,11 +371,10 @@ class BulkSnapshotPublisher:
         lib = _native.load()
         t0 = time.perf_counter()
         d_kind = torch.zeros(n, dtype=torch.uint8, device=self.device)
-        nv, nt = ctypes.c_int64(), ctypes.c_int64()
-        eng._check(lib.surge_replay_snapshot_delta(eng._h, ctypes.c_void_p(d_kind.data_ptr()), ctypes.byref(nv), ctypes.byref(nt), 1))
+        nv, nt = eng.snapshot_delta(d_kind, commit=True)
         eng._check(lib.surge_replay_set_encode_filter(eng._h, ctypes.c_void_p(d_kind.data_ptr())))
         try:
-            d_out, d_off = encode_states(eng, self.template, self.d_keys, self.d_key_off, capacity_hint=max(64, 96 * nv.value + int(self.d_keys.numel())) if not self.strings else 0,
+            d_out, d_off = encode_states(eng, self.template, self.d_keys, self.d_key_off, capacity_hint=max(64, 96 * nv + int(self.d_keys.numel())) if not self.strings else 0,
                                           strings=self.strings, envelope=self.envelope)
         except Exception:
             eng._check(lib.surge_replay_set_encode_filter(eng._h, None))
@@ -387,7 +385,7 @@ class BulkSnapshotPublisher:
         kind = d_kind[sel].cpu().numpy()
         off = torch.cat((d_off[sel], d_off[n:n + 1])).cpu().numpy()
         text, sel_h = d_out.cpu().numpy(), sel.cpu().numpy()
-        pending = PendingPublish(self, d_kind, {"gpu_and_copy_ms": (time.perf_counter() - t0) * 1e3, "values": nv.value, "tombstones": nt.value,
+        pending = PendingPublish(self, d_kind, {"gpu_and_copy_ms": (time.perf_counter() - t0) * 1e3, "values": nv, "tombstones": nt,
                                                 "text_bytes": int(text.nbytes)})
 
         def frame():

@@ -331,3 +331,30 @@ def test_the_sdk_sample_in_its_protobuf_envelope():
             pub.close()
         writer.close()
         dev.close()
+
+
+def test_the_batched_read_defaults_to_the_counter_form_and_the_other_reads_to_the_restored_template():
+    """The defaults differ on purpose: ``get_aggregate_bytes_many`` without a template writes ``JsonTemplate.counter()`` whatever
+    the restore was given, ``get_aggregate_bytes`` and ``range_bytes`` write ``read_template`` — the restore's."""
+    from surge_amd.encode import JP_I32
+
+    short = JsonTemplate((b'{"id":', "KEY", b',"n":', (JP_I32, 0), b',"v":', (JP_I32, 4), b"}"))
+    ids = ["k%d" % i for i in range(8)]
+    state = {k: (3 * i - 7, i + 1) for i, k in enumerate(ids)}
+    in_short = {k: b'{"id":"%s","n":%d,"v":%d}' % (k.encode(), n, v) for k, (n, v) in state.items()}
+    in_counter = {k: b'{"aggregateId":"%s","count":%d,"version":%d}' % (k.encode(), n, v) for k, (n, v) in state.items()}
+    wire = kw.record_batch(0, [(k.encode(), in_short[k]) for k in ids])
+    store = GpuReplayStateStore(CounterBusinessLogic())
+    try:
+        counts = store.restore_from_state_topic([wire], template=short, host_keys=False)
+        assert counts["rows_written"] == 8 and counts["refused"] == 0 and store.device_route
+        assert store.read_template is short and store.read_envelope == "none"
+        assert store.get_aggregate_bytes_many(ids) == [in_counter[k] for k in ids]
+        assert store.get_aggregate_bytes_many(ids, template=short) == [in_short[k] for k in ids]
+        assert [store.get_aggregate_bytes(k) for k in ids] == [in_short[k] for k in ids]
+        assert list(store.range_bytes()) == [(k, in_short[k]) for k in sorted(ids)] and store.device_route
+        assert len(store.keys) == 8 and not store.device_route  # with the host table the two defaults are the same two
+        assert store.get_aggregate_bytes_many(ids) == [in_counter[k] for k in ids]
+        assert list(store.range_bytes()) == [(k, in_short[k]) for k in sorted(ids)]
+    finally:
+        store.close()
