@@ -412,6 +412,14 @@ class BankAccountCommandModel(ReplayableCommandModel[BankAccount, object, object
         return EventJsonTemplate("_type", [("docs.command.BankAccountCreated", BA_CREATED, "", "balance", ARG_F64),
                                            ("docs.command.BankAccountUpdated", BA_UPDATED, "", "newBalance", ARG_F64)])
 
+    def event_string_fields(self):
+        """The strings ``BankAccountCreated`` carries and the state keeps (BankAccountSurgeModel.scala:14-17): ``accountOwner`` ->
+        string column 0, ``securityCode`` -> column 1, the columns of ``JsonTemplate.bank_account()``.  Optional hook: nothing
+        calls it unless a recovery is asked to keep the events' strings (``restore_from_fetches(keep_strings=True)``)."""
+        from surge_amd.ingest import EventStrings
+
+        return EventStrings([("docs.command.BankAccountCreated", "accountOwner", 0), ("docs.command.BankAccountCreated", "securityCode", 1)])
+
     def aggregate_id_of(self, event) -> str:
         return str(event.accountNumber)
 

@@ -448,6 +448,78 @@ int32_t surge_device_decoder_load_protobuf_states(surge_device_decoder* d, struc
  * named. */
 int32_t surge_device_decoder_keep_strings(surge_device_decoder* d, int32_t on);
 int32_t surge_device_decoder_state_strings(surge_device_decoder* d, int32_t column, const uint8_t** d_utf8, const int64_t** d_off, int64_t* n_agg);
+
+/* ---- the STRING fields of events -------------------------------------------------------------------------------------------
+ * A 16-byte event carries a type, a sequence number and one numeric argument; an event class may also carry strings the state
+ * keeps (BankAccountCreated: accountOwner, securityCode — BankAccountSurgeModel.scala:14-17).  surge_event_strings names them:
+ * up to SURGE_EVS_MAX entries {type name, field name, column}.  type_name is the discriminator value of the class, as in
+ * surge_event_json_type.name ("" for a template without a discriminator); column is the side string column
+ * (0 .. SURGE_JSON_STRING_COLUMNS - 1 of surge_replay.h) the string lands in.  surge_event_json_template is untouched.
+ * THE RULE (one text for host and device, surge_amd/csrc/event_strings_parse.h):
+ *   - the record's class is the one surge_event_json_decode chooses;
+ *   - for every column that class names, the string is the FIRST string-valued field of that name among the first 24 top-level
+ *     fields with unescaped names (the rule surge_event_json_decode applies to its numeric fields): a numeric field of the same
+ *     name in front does not count, a field with an escaped name does not count, the field at position 25 does not count;
+ *   - its contents (the bytes between the quotes) must pass surge_unescape_json_string's rules (surge_replay.h); the bytes kept
+ *     are that routine's output;
+ *   - a class that names a column, in a record without such a field or with a string that is refused, REFUSES THE RECORD.
+ * Which event wins: per aggregate and column the last event in topic order whose class names the column; an aggregate without
+ * such an event keeps what it had, an aggregate new to the table has empty strings. */
+#define SURGE_EVS_MAX 16
+#define SURGE_EVENT_STRING_OK      0   /* == SURGE_STATE_DECODE_OK: the span is the column's string                             */
+#define SURGE_EVENT_STRING_MISSING 12  /* refusal: the class names the column and the record has no string-valued field of that name */
+#define SURGE_EVENT_STRING_RECORD  13  /* refusal: the value is not an event the template decodes (not the object, unknown class, bad envelope) */
+#define SURGE_EVENT_STRING_ABSENT  254 /* not a refusal: the record's class does not name this column                          */
+/* (the other refusals are surge_unescape_json_string's: SURGE_STATE_DECODE_STRING, _ESCAPE, _SURROGATE) */
+typedef struct surge_event_string_field {
+  char     type_name[SURGE_EVJ_NAME]; /* NUL-terminated */
+  char     field[SURGE_EVJ_NAME];     /* NUL-terminated, not empty */
+  uint32_t column;
+  uint32_t reserved;
+} surge_event_string_field;
+typedef struct surge_event_strings {
+  uint32_t n;
+  uint32_t reserved;
+  surge_event_string_field entry[SURGE_EVS_MAX];
+} surge_event_strings;
+/* 0, or -1 with the reason in surge_event_json_last_error(): a template that fails surge_event_json_validate, n outside
+ * [1, SURGE_EVS_MAX], a name that is not NUL-terminated, a type name the template does not have, a column out of range, the
+ * same (type, column) named twice, an empty field name. */
+int32_t surge_event_strings_validate(const surge_event_json_template* tmpl, const surge_event_strings* strings);
+/* The rule for ONE record value on the host (thread-safe, no device).  spans_out: 2 x SURGE_JSON_STRING_COLUMNS int64 {offset
+ * into value, length} of the still-escaped bytes between the quotes — with an enveloped template offsets into the VALUE, of the
+ * payload's text; status_out: one byte per column, SURGE_EVENT_STRING_OK, _ABSENT or the refusal.  Returns 0 when no column is
+ * refused, SURGE_E_CORRUPT when one is (a value that is no event of the template refuses every column with _RECORD), -1 for a
+ * bad argument or strings that do not validate. */
+int32_t surge_event_json_string_spans(const surge_event_json_template* tmpl, const surge_event_strings* strings, const uint8_t* value, int64_t len,
+                                      int64_t* spans_out, uint8_t* status_out);
+/* Arms an events decoder (created with a template; SURGE_E_STATE on a state decoder and on a 16-byte-event decoder) BEFORE ITS
+ * FIRST PUSH — a decoder that went through surge_device_decoder_continue_as_events: before its first EVENTS push — anywhere
+ * else SURGE_E_STATE; strings that do not validate against the decoder's template: SURGE_E_INVALID.  From then on every push,
+ * behind its interning, selects the delivered records whose class names a column, validates their strings by the rule (a
+ * refusal fails the push with SURGE_E_CORRUPT naming the record's offset, nothing delivered, no key kept, the columns as they
+ * were) and keeps those records' values on the device; the columns are merged (surge_replay_merge_state_strings' kernels, the
+ * last naming event wins) when surge_device_decoder_state_strings asks for them or when more than SURGE_INGEST_EVENT_STRINGS_PENDING
+ * (environment, default 1048576) records are pending.  A continued decoder that kept the state topic's strings
+ * (surge_device_decoder_keep_strings) goes on merging into the SAME columns.  surge_device_decoder_clear drops what is pending
+ * and not yet merged.  A decoder that was never armed launches exactly what it launched before.
+ * On an armed decoder what surge_device_decoder_state_strings answered is valid only until the next push_finish[_async], clear
+ * or destroy: a push that crosses the pending bound merges at its end — with its host waits, also when the push was finished
+ * without its closing wait — and a merge writes the column's other buffer, which may have moved. */
+int32_t surge_device_decoder_keep_event_strings(surge_device_decoder* d, const surge_event_strings* strings);
+/* What an armed decoder holds until the next merge (SURGE_E_STATE on any other): out[0] records pending, out[1] their value
+ * bytes, out[2] the capacity of the values buffer, out[3] merges that have run; d_values / d_value_off (out[0] + 1 offsets) /
+ * d_rows (nullable): where the pending values, their CSR offsets and their aggregate rows lie on the device — complete in the order
+ * of the decoder's stream, valid until the next push_finish, merge or clear.  For tests and for sizing the bound. */
+int32_t surge_device_decoder_event_strings_pending(surge_device_decoder* d, int64_t out[4], const uint8_t** d_values, const int64_t** d_value_off, const int64_t** d_rows);
+/* Where the NEXT merge of an armed decoder writes column `column` (SURGE_E_STATE on any other decoder): the call makes the
+ * reservation that merge would make for what is pending now — the column's other buffer, room for the column's bytes so far plus
+ * the pending values' and for key count + 1 offsets — and reports out[0] the capacity of the bytes buffer, out[1] of the offsets
+ * buffer (bytes), out[2] the key count; *d_utf8 / *d_off: the buffers.  A merge that follows with nothing pushed in between
+ * writes exactly these buffers — surge_device_decoder_state_strings then answers the same addresses — and nothing in them
+ * behind the column's total bytes and behind its key count + 1 offsets.  A column the next merge would not write (not named, or
+ * already up to date with nothing pending): out[0] = out[1] = 0, NULL.  For tests. */
+int32_t surge_device_decoder_event_strings_next_column(surge_device_decoder* d, int32_t column, int64_t out[3], uint8_t** d_utf8, int64_t** d_off);
 /* The key table (aggregate ids in first-delivered order): to the host (NULL / NULL = size query), or where it lives on
  * the device (n_keys + 1 offsets; what the GPU state encoders and K4 take). */
 int32_t surge_device_decoder_keys(surge_device_decoder* d, uint8_t* utf8_out, int64_t utf8_capacity, int64_t* key_off_out, int64_t* n_keys_out,

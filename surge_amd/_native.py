@@ -149,6 +149,9 @@ INGEST_EXPORTS = (
     "surge_device_decoder_load_protobuf_states",
     "surge_device_decoder_keep_strings",
     "surge_device_decoder_state_strings",
+    "surge_device_decoder_keep_event_strings",
+    "surge_device_decoder_event_strings_pending",
+    "surge_device_decoder_event_strings_next_column",
     "surge_replay_append_decoded",
     "surge_replay_append_decoded_async",
     "surge_replay_stage_decoded",
@@ -165,6 +168,7 @@ INGEST_EXPORTS = (
     "surge_event_json_decode",
     "surge_event_json_decode_keyed",
     "surge_event_json_last_error",
+    "surge_event_json_string_spans",
     "surge_parse_f64_json",
     "surge_ingest_key_count",
     "surge_ingest_key",
@@ -207,6 +211,9 @@ SNAPSHOT_EXPORTS = (
 
 #: the host half of the state decoder (declared in ``include/surge_replay.h``; needs no handle and no device)
 STATE_EXPORTS = ("surge_decode_json_state", "surge_decode_protobuf_state", "surge_unescape_json_string")
+
+#: which event class carries which string (declared in ``include/surge_ingest.h`` beside the two exports above that use it)
+EVENT_STRINGS_EXPORTS = ("surge_event_strings_validate",)
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -423,6 +430,11 @@ def load() -> ctypes.CDLL:
         "surge_device_decoder_load_protobuf_states": ([vp, vp, vp, ctypes.POINTER(i64 * 4)], i32),
         "surge_device_decoder_keep_strings": ([vp, i32], i32),
         "surge_device_decoder_state_strings": ([vp, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64)], i32),
+        "surge_device_decoder_keep_event_strings": ([vp, vp], i32),
+        "surge_device_decoder_event_strings_next_column": ([vp, i32, ctypes.POINTER(i64 * 3), ctypes.POINTER(vp), ctypes.POINTER(vp)], i32),
+        "surge_device_decoder_event_strings_pending": ([vp, ctypes.POINTER(i64 * 4), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)], i32),
+        "surge_event_strings_validate": ([vp, vp], i32),
+        "surge_event_json_string_spans": ([vp, vp, vp, i64, vp, vp], i32),
         "surge_replay_append_decoded": ([vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "surge_replay_append_decoded_async": ([vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
         "surge_replay_stage_decoded": ([vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
@@ -476,7 +488,7 @@ def load() -> ctypes.CDLL:
         "surge_device_framer_next_offsets": ([vp, vp], i32),
         "surge_device_framer_uncompressed_bytes": ([vp], i64),
     })
-    for name in EXPORTS + INGEST_EXPORTS + SNAPSHOT_EXPORTS + STATE_EXPORTS:
+    for name in EXPORTS + INGEST_EXPORTS + SNAPSHOT_EXPORTS + STATE_EXPORTS + EVENT_STRINGS_EXPORTS:
         try:
             fn = getattr(L, name)
         except AttributeError as e:

@@ -23,6 +23,7 @@
 
 #include "../../include/surge_ingest.h"
 #include "state_parse.h"  // sp_envelope: the one text of the protobuf envelope's grammar (host, state kernel, event kernels)
+#include "event_strings_parse.h"
 
 namespace {
 
@@ -266,6 +267,30 @@ int32_t surge_event_json_decode_keyed(const surge_event_json_template* t, const 
   std::memcpy(o + 4, &seq, 4);
   std::memcpy(o + 8, &raw, 8);
   return 0;
+}
+
+// ---- the string fields of events: which class carries which string, and the rule for one value (event_strings_parse.h) ----
+int32_t surge_event_strings_validate(const surge_event_json_template* tmpl, const surge_event_strings* strings) {
+  if (surge_event_json_validate(tmpl) != 0) return -1;
+  const char* why = surge::evs_compile(tmpl, strings, nullptr);
+  if (!why) return 0;
+  t_err = std::string("event strings: ") + why;
+  return -1;
+}
+
+int32_t surge_event_json_string_spans(const surge_event_json_template* tmpl, const surge_event_strings* strings, const uint8_t* value, int64_t len,
+                                      int64_t* spans_out, uint8_t* status_out) {
+  if (!spans_out || !status_out || len < 0 || (!value && len > 0)) { t_err = "bad argument"; return -1; }
+  if (surge_event_strings_validate(tmpl, strings) != 0) return -1;
+  surge::EvsRule rule;
+  (void)surge::evs_compile(tmpl, strings, &rule);
+  static const uint8_t none = 0;
+  const int rc = surge::evs_string_spans(rule, value ? value : &none, len, spans_out, status_out);
+  if (rc == SURGE_EVENT_STRING_OK) return 0;
+  t_err = rc == SURGE_EVENT_STRING_RECORD    ? "the value is not an event the template decodes"
+          : rc == SURGE_EVENT_STRING_MISSING ? "the event's class names a string field the value does not have"
+                                             : "a string field the event's class names is not a valid JSON string";
+  return SURGE_E_CORRUPT;
 }
 
 }  // extern "C"

@@ -394,6 +394,7 @@ int32_t surge_device_decoder_continue_as_events(surge_device_decoder* d, const s
   d->json = tmpl != nullptr;
   d->states = false;
   d->continued = true;
+  d->events_from_push = d->push_seq;
   return OK;
 }
 
@@ -437,6 +438,8 @@ int32_t surge_device_decoder_clear(surge_device_decoder* d) {
   if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
   d->n_records = 0;
   d->val_bytes = 0;
+  d->ev_pend_n = 0;  // (kept event strings: what is pending and not merged goes with the records)
+  d->ev_pend_bytes = 0;
   return OK;
 }
 

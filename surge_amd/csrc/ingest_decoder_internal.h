@@ -151,6 +151,19 @@ struct surge_device_decoder {
   Buf st_spans;
   bool keep_strings = false;
   int64_t state_loads = 0;
+  // events mode, surge_device_decoder_keep_event_strings (ingest_strings.hip): the rule on the device, the event types that
+  // select a record and the columns the rule names; a push's select / list / spans scratch; the selected records of the pushes
+  // since the last merge (values, n + 1 offsets, rows, spans, a status array per column), merged into str_cols when the
+  // columns are asked for or more than ev_pend_bound records are pending; the merge's scratch
+  bool ev_strings = false;
+  surge::ingest::EvsTypes ev_types{};
+  bool ev_named[SURGE_JSON_STRING_COLUMNS] = {};
+  Buf d_evs_rule;
+  Buf es_seg, es_count, es_base, es_cell, es_sel, es_lens, es_totals;
+  Buf ev_pend_val, ev_pend_off, ev_pend_rows, ev_pend_spans, ev_pend_status[SURGE_JSON_STRING_COLUMNS];
+  int64_t ev_pend_n = 0, ev_pend_bytes = 0, ev_pend_bound = 1 << 20, ev_merges = 0;
+  Buf es_win, es_bad, es_merge_totals;
+  uint64_t events_from_push = 0;  // push_seq when the decoder became an events decoder: arming comes before the push behind it
   // hand-over of the result arrays to a consumer on another stream (surge_replay_append_decoded_async): `consumed` is
   // recorded on the consumer's stream behind its last read, the next stage 2 waits for it before it writes the arrays
   hipEvent_t ready = nullptr, consumed = nullptr;
@@ -245,6 +258,13 @@ int32_t stage1_records(surge_device_decoder* d, PushSlot& s, const uint8_t* keys
                        const int64_t* offsets, int64_t n);
 // ---- ingest_stage2.hip: interning, compaction, append on the decoder's stream; wait = false leaves the closing wait out -----
 int32_t stage2(surge_device_decoder* d, PushSlot& s, bool wait);
+// ---- ingest_handover.hip: what is pending of the kept event strings merged into str_cols, every column brought to n_keys ------
+inline surge::ingest::StringsPending strings_pending_of(surge_device_decoder* d) {
+  surge::ingest::StringsPending p{(uint8_t*)d->ev_pend_val.p, (int64_t*)d->ev_pend_off.p, (int64_t*)d->ev_pend_rows.p, (int64_t*)d->ev_pend_spans.p, {}, d->ev_pend_n, d->ev_pend_bytes};
+  for (int c = 0; c < SURGE_JSON_STRING_COLUMNS; ++c) p.status[c] = (uint8_t*)d->ev_pend_status[c].p;
+  return p;
+}
+int32_t merge_event_strings(surge_device_decoder* d);
 
 }  // namespace host
 }  // namespace ingest

@@ -32,7 +32,8 @@ enum : uint32_t {
   RS_ENVELOPE = 11,     // enveloped events (JsonCtx::envelope): the value is not `[aggregateId] [payload]` and nothing else (sp_envelope_spans, state_parse.h)
   RS_KEY_MISMATCH = 12, // ... its aggregateId is not the aggregate id of the record's key
   RS_BELOW = 13,        // below its section's floor (a consumer's start offset): passed over like RS_SKIP — not an error, never reported
-  RS_COUNT,             // (how many there are: the host's text per status is checked against it, ingest_stage2.hip)
+  RS_STRING = 14,       // kept event strings (ingest_strings.hip): the record's class names a string field the value lacks, or that string is refused
+  RS_COUNT,            // (how many there are: the host's text per status is checked against it, ingest_stage2.hip)
 };
 
 struct RecMeta {
@@ -289,6 +290,57 @@ hipError_t launch_value_scan(const RecMeta* meta, int64_t n_rec, const InternScr
 // behind launch_intern_commit: value_off[out_base + k] (and the closing entry) = val_base + ..., the values' bytes to values[val_base ..)
 hipError_t launch_value_gather(const RecMeta* meta, int64_t n_rec, const uint8_t* bytes, const InternScratch& sc, const StateScratch& ss, int64_t kept, int64_t out_base,
                                int64_t val_base, int64_t* value_off, uint8_t* values, hipStream_t st);
+
+// ---- ingest_strings.hip: the string fields of events (surge_device_decoder_keep_event_strings), behind a push's interning ------
+struct EvsTypes {  // the surge_event16.type values of the classes that name a string column
+  uint32_t n;
+  uint32_t type[SURGE_EVJ_MAX_TYPES];
+};
+struct StringsCell {  // where a push's finish reads what the select found
+  uint32_t n_sel, pad;
+};
+struct StringsSelect {  // per push: seg holds kStringsBlock entries per block of records, block_count / block_base one each
+  uint32_t *seg, *block_count, *block_base;
+  StringsCell* cell;
+};
+constexpr int kStringsBlock = 256;
+// What a decoder keeps until the columns are merged: the selected records of every push since, in push order.  Record q's
+// value is values[off[q] .. off[q + 1]), its aggregate rows[q], its spans spans[q * 2 * SURGE_JSON_STRING_COLUMNS ..), its
+// status for column c status[c][q].
+struct StringsPending {
+  uint8_t* values;
+  int64_t *off, *rows, *spans;
+  uint8_t* status[4];
+  int64_t n, bytes;
+};
+// select: one lane per record; the kept records (keep[i], behind launch_intern_probe) whose event type is one of `types`, compacted
+// per block of kStringsBlock records in record order; cell->n_sel += their count (the caller zeroes the cell)
+hipError_t launch_strings_select(const uint32_t* keep, const uint4* ev_tmp, int64_t n_rec, const EvsTypes& types, const StringsSelect& s, hipStream_t st);
+// behind the wait that brought n_sel back (> 0): sel[0 .. n_sel) = the selected records in record order, lens[k] = record sel[k]'s value length
+hipError_t launch_strings_list(const RecMeta* meta, int64_t n_rec, const StringsSelect& s, uint32_t* sel, int64_t* lens, hipStream_t st);
+// spans: one lane per selected record walks its value where stage 1 left it (event_strings_parse.h; `rule`: a device EvsRule) and
+// writes spans and statuses at pending entry p.n + k; a refusal is reported as RS_STRING
+hipError_t launch_strings_spans(const void* rule, const RecMeta* meta, const uint8_t* bytes, const uint32_t* sel, int64_t n_sel, const StringsPending& p, ErrorCell* err,
+                                hipStream_t st);
+// gather, behind launch_intern_commit and the scan of lens: the selected records' values to p.values[p.bytes ..), their offsets
+// (and the closing one, p.bytes + total) and rows (agg[keep_pos[record]]: the push's part of the result) to entries p.n ..
+hipError_t launch_strings_gather(const RecMeta* meta, const uint8_t* bytes, const uint32_t* sel, const int64_t* lens, int64_t n_sel, int64_t total, const uint32_t* keep_pos,
+                                 const int64_t* agg, const StringsPending& p, hipStream_t st);
+// lens[0 .. n) scanned in place (exclusive; state_kernels.hip's scan); totals: ceil(n / 1024) + 1 entries, the sum lands in the last
+hipError_t launch_strings_scan(int64_t* lens, int64_t n, int64_t* totals, hipStream_t st);
+// One column of the merge over what is pending (state_strings.hip's kernels; the highest pending record with status OK wins, an
+// aggregate without one keeps prev's string, a new one is empty): out_off gets n_agg + 1 offsets, out the bytes, *total_out their
+// sum.  win1: n_agg u64 of scratch, bad: one u64, totals: ceil(n_agg / 1024) + 1 i64.  Waits for the stream (the total sizes
+// nothing here — out holds prev's bytes + the pending values' — but the closing offset is the host's to write).
+struct StringsColumn {
+  const uint8_t* prev;
+  const int64_t* prev_off;
+  int64_t n_prev;
+  uint8_t* out;
+  int64_t* out_off;
+};
+hipError_t strings_merge_column(const StringsPending& p, int column, int64_t n_agg, const StringsColumn& col, unsigned long long* win1, unsigned long long* bad, int64_t* totals,
+                                int64_t* total_out, hipStream_t st);
 
 }  // namespace ingest
 }  // namespace surge

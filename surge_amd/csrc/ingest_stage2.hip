@@ -15,7 +15,8 @@ const char* const kWhyBad[] = {"", "", "has a null key or value (not an event)",
                                "collides with another key on its 64-bit hash",
                                "has an empty, non-null value under a key (a state record carries a value or the null of a tombstone)",
                                "is not the protobuf Event envelope the event template names ([aggregateId] [payload] and nothing else)",
-                               "names another aggregateId in its envelope than the aggregate id of its key", ""};
+                               "names another aggregateId in its envelope than the aggregate id of its key", "",
+                               "lacks a string field its event class names (kept event strings), or that string is not a valid JSON string"};
 static_assert(sizeof(kWhyBad) / sizeof(kWhyBad[0]) == RS_COUNT, "one text per record status");
 const char* why_bad(uint32_t status) { return status < RS_COUNT ? kWhyBad[status] : "is bad"; }
 
@@ -71,6 +72,9 @@ struct Stage2 {
   unsigned long long first_total = 0, val_total = 0;
   uint32_t kept = 0;
   int64_t n_new = 0, new_bytes = 0;
+  // kept event strings (ingest_strings.hip): what the select found, the selected values' bytes
+  StringsCell strings_cell{};
+  int64_t n_sel = 0, sel_bytes = 0;
 
   Stage2(surge_device_decoder* d_, PushSlot& s_)
       : d(d_), s(s_), n_rec(s_.n_rec), st(d_->stream), R((size_t)s_.n_rec), dby((const uint8_t*)s_.d_bytes.p), derr((ErrorCell*)s_.d_err.p), dmeta((RecMeta*)s_.meta.p) {}
@@ -87,6 +91,13 @@ struct Stage2 {
     if (d->states) {
       DCHK(d, d->vlen.reserve((R + 1) * 8, false, st));
       DCHK(d, d->vscan.reserve((R + 1) * 8, false, st));
+    }
+    if (d->ev_strings) {
+      const size_t n_blocks = (R + kStringsBlock - 1) / kStringsBlock;
+      DCHK(d, d->es_seg.reserve(n_blocks * kStringsBlock * 4, false, st));
+      DCHK(d, d->es_count.reserve(n_blocks * 4, false, st));
+      DCHK(d, d->es_base.reserve(n_blocks * 4, false, st));
+      DCHK(d, d->es_cell.reserve(sizeof(StringsCell), false, st));
     }
     const int32_t rc = ensure_table(d, n_rec);
     if (rc != OK) return rc;
@@ -105,6 +116,11 @@ struct Stage2 {
       if (d->states) {  // the delivered records' value lengths, scanned: where each value goes, and how many bytes the push adds
         PCHK(d, launch_value_scan(dmeta, n_rec, scratch, values, st));
         PCHK(d, hipMemcpyAsync(&val_total, values.vscan + R, 8, hipMemcpyDeviceToHost, st));
+      }
+      if (d->ev_strings) {  // the kept records whose class carries a string, and how many they are
+        PCHK(d, hipMemsetAsync(d->es_cell.p, 0, sizeof(StringsCell), st));
+        PCHK(d, launch_strings_select(scratch.keep, (const uint4*)s.ev_tmp.p, n_rec, d->ev_types, strings_select(), st));
+        PCHK(d, hipMemcpyAsync(&strings_cell, d->es_cell.p, sizeof(strings_cell), hipMemcpyDeviceToHost, st));
       }
       PCHK(d, hipMemcpyAsync(&ec, derr, sizeof(ec), hipMemcpyDeviceToHost, st));
       PCHK(d, hipMemcpyAsync(&first_total, (unsigned long long*)d->first_scan.p + R, 8, hipMemcpyDeviceToHost, st));
@@ -126,6 +142,33 @@ struct Stage2 {
     d->counters[0] += n_rec;
     n_new = (int64_t)(first_total >> 40);
     new_bytes = (int64_t)(first_total & ((1ull << 40) - 1));
+    n_sel = d->ev_strings ? (int64_t)strings_cell.n_sel : 0;
+    return OK;
+  }
+
+  StringsSelect strings_select() const { return StringsSelect{(uint32_t*)d->es_seg.p, (uint32_t*)d->es_count.p, (uint32_t*)d->es_base.p, (StringsCell*)d->es_cell.p}; }
+
+  // kept event strings, a push that selected records: their list, their strings validated by the rule where stage 1 left the
+  // values — spans and statuses go straight behind what is pending — and the bytes their values take; the wait brings a refusal
+  // back while nothing of the push is committed (a push that selected nothing has none of this)
+  int32_t validate_strings() {
+    const size_t keep_n = (size_t)(d->ev_pend_n + n_sel);
+    hipError_t e = d->es_sel.reserve((size_t)n_sel * 4, false, st);
+    if (e == hipSuccess) e = d->es_lens.reserve((size_t)n_sel * 8, false, st);
+    if (e == hipSuccess) e = d->es_totals.reserve((((size_t)n_sel + 1023) / 1024 + 1) * 8, false, st);
+    if (e == hipSuccess) e = d->ev_pend_off.reserve((keep_n + 1) * 8, true, st);
+    if (e == hipSuccess) e = d->ev_pend_rows.reserve(keep_n * 8, true, st);
+    if (e == hipSuccess) e = d->ev_pend_spans.reserve(keep_n * (2 * SURGE_JSON_STRING_COLUMNS) * 8, true, st);
+    for (int c = 0; c < SURGE_JSON_STRING_COLUMNS && e == hipSuccess; ++c) e = d->ev_pend_status[c].reserve(keep_n, true, st);
+    if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? E_NOMEM : E_DEVICE, std::string("growing the kept event strings: ") + hipGetErrorString(e));
+    int64_t* const lens = (int64_t*)d->es_lens.p;
+    int64_t* const totals = (int64_t*)d->es_totals.p;
+    PCHK(d, launch_strings_list(dmeta, n_rec, strings_select(), (uint32_t*)d->es_sel.p, lens, st));
+    PCHK(d, launch_strings_spans(d->d_evs_rule.p, dmeta, dby, (const uint32_t*)d->es_sel.p, n_sel, strings_pending_of(d), derr, st));
+    PCHK(d, launch_strings_scan(lens, n_sel, totals, st));
+    PCHK(d, hipMemcpyAsync(&sel_bytes, totals + (n_sel + 1023) / 1024, 8, hipMemcpyDeviceToHost, st));
+    PCHK(d, hipMemcpyAsync(&ec, derr, sizeof(ec), hipMemcpyDeviceToHost, st));
+    PCHK(d, wait_stream(d, st));
     return OK;
   }
 
@@ -174,6 +217,7 @@ struct Stage2 {
       if (e == hipSuccess) e = d->long_runs.reserve((n_runs + 1) * 4, false, st);
     }
     if (e == hipSuccess) e = d->r_off.reserve((size_t)(d->n_records + kept) * 8 + 16, true, st);
+    if (e == hipSuccess && n_sel > 0) e = d->ev_pend_val.reserve((size_t)(d->ev_pend_bytes + sel_bytes) + 64, true, st);
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? E_NOMEM : E_DEVICE, std::string("growing the key table / result arrays: ") + hipGetErrorString(e));
     return OK;
   }
@@ -192,6 +236,12 @@ struct Stage2 {
       values.long_runs = (uint32_t*)d->long_runs.p;
       PCHK(d, launch_value_gather(dmeta, n_rec, dby, scratch, values, kept, d->n_records, d->val_bytes, (int64_t*)d->r_val_off.p, (uint8_t*)d->r_val.p, st));
       d->val_bytes += (int64_t)val_total;
+    }
+    if (n_sel > 0) {  // the selected records' values leave the slot's bytes too, their rows beside them
+      PCHK(d, launch_strings_gather(dmeta, dby, (const uint32_t*)d->es_sel.p, (const int64_t*)d->es_lens.p, n_sel, sel_bytes, (const uint32_t*)d->keep_pos.p,
+                                    (const int64_t*)d->r_agg.p + d->n_records, strings_pending_of(d), st));
+      d->ev_pend_n += n_sel;
+      d->ev_pend_bytes += sel_bytes;
     }
     d->n_keys += n_new;
     d->arena_bytes += new_bytes;
@@ -252,8 +302,15 @@ int32_t surge::ingest::host::stage2(surge_device_decoder* d, PushSlot& s, bool w
   int32_t rc = push.reserve_scratch();
   if (rc == OK) rc = push.probe();
   if (rc == OK && push.found_bad()) return push.name_failure();
+  if (rc == OK && push.n_sel > 0) {
+    rc = push.validate_strings();
+    if (rc == OK && push.found_bad()) return push.name_failure();
+  }
   if (rc == OK) rc = push.grow();
   if (rc == OK) rc = push.commit_and_gather();
   if (rc == OK) rc = push.patch_host_doubles();
-  return rc == OK ? push.close(wait) : rc;
+  if (rc == OK) rc = push.close(wait);
+  // more pending than the bound: the columns are merged now (the merge waits for the stream)
+  if (rc == OK && d->ev_strings && d->ev_pend_n > d->ev_pend_bound) rc = merge_event_strings(d);
+  return rc;
 }

@@ -57,6 +57,50 @@ class CEventJsonTemplate(ctypes.Structure):
                 ("types", _CEventJsonType * EVJ_MAX_TYPES)]
 
 
+EVS_MAX = 16  # SURGE_EVS_MAX
+EVENT_STRING_OK, EVENT_STRING_MISSING, EVENT_STRING_RECORD, EVENT_STRING_ABSENT = 0, 12, 13, 254  # SURGE_EVENT_STRING_*
+
+
+class _CEventStringField(ctypes.Structure):
+    _fields_ = [("type_name", ctypes.c_char * EVJ_NAME), ("field", ctypes.c_char * EVJ_NAME), ("column", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class CEventStrings(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("entry", _CEventStringField * EVS_MAX)]
+
+
+class EventStrings:
+    """``surge_event_strings``: which event class carries which string.  ``entries``: ``(type name, field name, column)`` —
+    the discriminator value of the class as in ``EventJsonTemplate.types`` (``""`` for a template without a discriminator), the
+    JSON field that holds the string, and the side string column (``0 .. encode.STRING_COLUMNS - 1``) it lands in.  Per aggregate
+    and column the last event in topic order whose class names the column wins (``include/surge_ingest.h``, "the STRING fields of
+    events")."""
+
+    def __init__(self, entries):
+        self.entries = [(str(t), str(f), int(c)) for t, f, c in entries]
+
+    def to_c(self) -> CEventStrings:
+        if len(self.entries) > EVS_MAX:
+            raise ValueError(f"at most {EVS_MAX} event string fields")
+        s = CEventStrings()
+        s.n = len(self.entries)
+        for i, (type_name, field, column) in enumerate(self.entries):
+            if not 0 <= column < 1 << 32:
+                raise ValueError(f"string column {column} out of range")
+            tn, fn = type_name.encode(), field.encode()
+            if len(tn) >= EVJ_NAME or len(fn) >= EVJ_NAME:
+                raise ValueError(f"a name of more than {EVJ_NAME - 1} bytes")
+            s.entry[i].type_name, s.entry[i].field, s.entry[i].column = tn, fn, column
+        return s
+
+    def validate(self, template: "EventJsonTemplate") -> None:
+        """``surge_event_strings_validate`` against ``template``; ``ValueError`` with the library's reason."""
+        lib = _native.load()
+        t, c = template.to_c(), self.to_c()
+        if lib.surge_event_strings_validate(ctypes.byref(t), ctypes.byref(c)) != 0:
+            raise ValueError((lib.surge_event_json_last_error() or b"").decode())
+
+
 class EventJsonTemplate:
     """``surge_event_json_template``: how a model's JSON event text maps onto the 16-byte fixed event.
 
@@ -103,6 +147,22 @@ class EventJsonTemplate:
         if rc != 0:
             raise IngestError(rc, (lib.surge_event_json_last_error() or b"").decode("utf-8", "replace"))  # (the message may quote the value's own bytes)
         return out[0]
+
+    def string_spans(self, strings: "EventStrings", value: bytes):
+        """``surge_event_json_string_spans``: the rule the device applies to one record value, on the host.  Returns ``(rc,
+        spans, status)``: ``rc`` 0 or ``-7`` (CORRUPT: a column is refused), ``spans`` one ``(offset into value, length)`` per
+        string column — the still-escaped bytes between the quotes — and ``status`` one ``EVENT_STRING_*`` / ``DECODE_*`` per
+        column.  ``ValueError`` for strings that do not validate against this template."""
+        lib = _native.load()
+        t, c = self.to_c(), strings.to_c()
+        strings.validate(self)
+        buf = (ctypes.c_uint8 * max(len(value), 1)).from_buffer_copy(value or b"\0")
+        spans = np.zeros(8, dtype=np.int64)
+        status = np.zeros(4, dtype=np.uint8)
+        rc = lib.surge_event_json_string_spans(ctypes.byref(t), ctypes.byref(c), buf, len(value), spans.ctypes.data_as(ctypes.c_void_p), status.ctypes.data_as(ctypes.c_void_p))
+        if rc not in (0, -7):
+            raise IngestError(rc, (lib.surge_event_json_last_error() or b"").decode())
+        return int(rc), [(int(spans[2 * k]), int(spans[2 * k + 1])) for k in range(4)], [int(x) for x in status]
 
 
 class IngestError(RuntimeError):
@@ -651,11 +711,14 @@ class DeviceDecoder:
     are kept as bytes (``state_result()``) and handed to the engine with ``load_states_into``; ``result`` / ``fold_into`` /
     ``stage_into`` are an events decoder's and fail on it (STATE)."""
 
-    def __init__(self, template: Optional[EventJsonTemplate] = None, device: int = 0, stream=None, states: bool = False, keep_strings: bool = False):
+    def __init__(self, template: Optional[EventJsonTemplate] = None, device: int = 0, stream=None, states: bool = False, keep_strings: bool = False,
+                 event_strings: Optional[EventStrings] = None):
         if states and template is not None:
             raise ValueError("DeviceDecoder: states=True is the alternative to an event template")
         if keep_strings and not states:
             raise ValueError("DeviceDecoder: keep_strings belongs to a state decoder (states=True)")
+        if event_strings is not None and template is None:
+            raise ValueError("DeviceDecoder: event_strings name fields of the event template's classes (a state decoder takes them behind continue_as_events)")
         self._lib = _native.load()
         self._h = ctypes.c_void_p()
         self.device = device
@@ -676,6 +739,56 @@ class DeviceDecoder:
                 msg = (self._lib.surge_device_decoder_last_error(self._h) or b"").decode()
                 self.close()
                 raise IngestError(rc, msg)
+        self.event_strings = None
+        if event_strings is not None:
+            try:
+                self.keep_event_strings(event_strings)
+            except Exception:  # (the library's refusal, or entries that do not fit the C struct: the handle goes either way)
+                self.close()
+                raise
+
+    def keep_event_strings(self, strings: EventStrings) -> None:
+        """``surge_device_decoder_keep_event_strings``: from here on every push keeps, on the device, the strings ``strings``
+        names — before the decoder's first push (a continued state decoder: before its first push of events; STATE anywhere
+        else).  A record whose class names a string it does not carry, or carries a string that is no valid JSON string, fails
+        its push (CORRUPT, naming the record's offset).  The columns are read with ``state_strings()``; a continued decoder that
+        kept the state topic's strings goes on merging into the same columns."""
+        c = strings.to_c()
+        self._check(self._lib.surge_device_decoder_keep_event_strings(self._h, ctypes.byref(c)))
+        self.event_strings = strings
+
+    def event_strings_pending(self) -> dict:
+        """What an armed decoder holds until the next merge (``surge_device_decoder_event_strings_pending``): ``records``,
+        ``bytes``, ``capacity`` (of the values buffer), ``merges`` so far, and ``values`` / ``value_off`` / ``rows`` — CUDA tensors
+        viewing the pending values (the whole buffer, ``capacity`` bytes), their ``records + 1`` offsets and their rows, or
+        ``None`` while nothing was ever kept."""
+        import torch
+
+        out = (ctypes.c_int64 * 4)()
+        pv, po, pr = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self._lib.surge_device_decoder_event_strings_pending(self._h, ctypes.byref(out), ctypes.byref(pv), ctypes.byref(po), ctypes.byref(pr)))
+        dev = torch.device("cuda", self.device)
+        torch.cuda.synchronize(dev)
+        n, cap = int(out[0]), int(out[2])
+        return {"records": n, "bytes": int(out[1]), "capacity": cap, "merges": int(out[3]),
+                "values": _device_view(pv, (cap,), "|u1", dev) if pv.value and cap else None,
+                "value_off": _device_view(po, (n + 1,), "<i8", dev) if po.value and n else None,
+                "rows": _device_view(pr, (n,), "<i8", dev) if pr.value and n else None}
+
+    def event_strings_next_column(self, column: int):
+        """Where the next merge writes ``column`` (``surge_device_decoder_event_strings_next_column``: the call reserves what
+        that merge would): ``(utf8, off)`` — CUDA ``uint8`` tensors over the WHOLE capacity of the two buffers — or ``None``
+        for a column the next merge would not write.  A ``state_strings()`` right behind it merges into exactly these."""
+        import torch
+
+        out = (ctypes.c_int64 * 3)()
+        pu, po = ctypes.c_void_p(), ctypes.c_void_p()
+        self._check(self._lib.surge_device_decoder_event_strings_next_column(self._h, column, ctypes.byref(out), ctypes.byref(pu), ctypes.byref(po)))
+        if not pu.value or not po.value:
+            return None
+        dev = torch.device("cuda", self.device)
+        torch.cuda.synchronize(dev)
+        return _device_view(pu, (int(out[0]),), "|u1", dev), _device_view(po, (int(out[1]),), "|u1", dev)
 
     def close(self):
         if self._h:
@@ -853,10 +966,11 @@ class DeviceDecoder:
         return tuple(int(c) for c in counts)
 
     def state_strings(self):
-        """The STR columns a ``keep_strings=True`` state decoder has kept (``surge_device_decoder_state_strings``): one entry
-        per string column, ``(d_utf8, d_off)`` CUDA tensors viewing the decoder's buffers (valid until the next
-        ``load_states_into`` / ``clear`` / ``close``: clone what has to live longer) — aggregate ``a``'s string is
-        ``d_utf8[d_off[a]:d_off[a+1]]`` — or ``None`` for a column no load has named."""
+        """The STR columns a ``keep_strings=True`` state decoder has kept, or an events decoder armed with ``event_strings``
+        (``surge_device_decoder_state_strings``; on the latter the call merges what the pushes since the last one kept): one
+        entry per string column, ``(d_utf8, d_off)`` CUDA tensors viewing the decoder's buffers (valid until the next
+        ``load_states_into`` / ``finish`` / ``clear`` / ``close``: clone what has to live longer) — aggregate ``a``'s string is
+        ``d_utf8[d_off[a]:d_off[a+1]]`` — or ``None`` for a column nothing has named."""
         import torch
 
         from .encode import STRING_COLUMNS

@@ -86,10 +86,13 @@ class StoreReads:
         one copy back.  ``None`` for an id the store does not hold and for a tombstone; ``AggregateInitializationException`` when
         one of the ids is poisoned, as the single read raises it.  ``(JP_STR, column)`` parts take ``state_string_columns()``;
         a column nothing restored raises ``ValueError``.  ``envelope="protobuf_state"``: what a multilanguage application
-        stores.  The restored columns hold EMPTY strings for aggregates that first appeared after the resume (``apply_events``, an
-        events tail): their strings are the host model's alone, so for such an aggregate a STR part is written ``""`` here while
-        ``get_aggregate_bytes`` — the plugin's formatter over ``restore_static_strings`` — writes the real string.  Every other
-        part, and every aggregate the state topic carried, reads the same on both."""
+        stores.  The columns come from a resume from the state topic or from ``restore_from_fetches(keep_strings=True)``; an events
+        tail read as bytes with ``restore_from_state_topic(events_fetches=..., keep_event_strings=True)`` goes into the same
+        columns, so its aggregates read the same on both paths.  What is left: aggregates that first appear through
+        ``apply_events`` (decoded events, a host-side ``events_tail``), or through an events tail read without
+        ``keep_event_strings``, have EMPTY strings in the columns — theirs are the host model's alone, so for such an aggregate a STR part is
+        written ``""`` here while ``get_aggregate_bytes`` — the plugin's formatter over ``restore_static_strings`` — writes the real
+        string.  Every other part, and every aggregate the topics carried, reads the same on both."""
         import torch
 
         check_envelope(envelope)

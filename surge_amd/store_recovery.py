@@ -100,7 +100,7 @@ class TopicRecoveries:
 
     def restore_from_fetches(self, fetches, capacity: int = 0, overlap: bool = True, n_partitions: int = 0, framing_threads: int = 8,
                              consumer_threads: int = 1, bound_log: bool = False, algo: int = ALGO_AUTO, device_crc: bool = True, in_place: bool = True,
-                             host_keys: bool = True) -> dict:
+                             host_keys: bool = True, keep_strings: bool = False) -> dict:
         """Recover from the events topic as a consumer receives it: ``fetches`` yields the record-batch bytes of one
         partition, fetch by fetch, in offset order (a list, or a generator that polls) — or, with ``n_partitions``, per
         fetch response the next bytes of each of the consumer's partitions (``PartitionedFramedFetches``: one framer per
@@ -130,13 +130,24 @@ class TopicRecoveries:
         does here.  On that route the bytes of a read are NOT the plugin's ``aggregate_write_formatting``'s: they are composed on
         the GPU through ``read_template`` / ``read_envelope`` — reset here to ``None`` / ``"none"``, that is ``JsonTemplate.counter()``;
         a model with another serialized form sets ``read_template`` after the restore (or passes ``template`` to
-        ``get_aggregate_bytes_many``)."""
+        ``get_aggregate_bytes_many``).
+        ``keep_strings=True``: the string fields the events carry stay on the device.  The model's optional hook
+        ``event_string_fields()`` (an ``ingest.EventStrings``: which event class carries which string, into which column) arms the
+        decoder (``DeviceDecoder(event_strings=...)``); a model without the hook raises ``ValueError`` before anything of the
+        store changes.  Per aggregate and column the last event in topic order whose class names the column wins; an event
+        that lacks a string its class names fails the recovery like any value that does not decode.  At the end
+        ``state_strings`` holds the columns (cloned: the decoder may be closed), as after ``restore_from_state_topic`` — so
+        ``restore_static_strings``, ``get_aggregate_bytes_many`` / ``range_bytes`` / ``all_bytes`` with a template that has STR
+        parts, ``state_string_columns()`` and ``encode_states(strings=...)`` work on top.  The default does what it always did."""
+        strings = _event_strings_of(self.model) if keep_strings else None
         with contextlib.ExitStack() as closing:
             def new_decoder(template):
+                if strings is not None and template is None:
+                    raise ValueError("keep_strings: the topic's values are 16-byte fixed events, which carry no strings")
                 # (an earlier device-route restore's decoder goes here, not sooner: up to this point — the fetches' first record, whose
                 # values may turn out not to be device-decodable — nothing of the store has changed, and its reads still answer)
                 self._drop_decoder()
-                return closing.enter_context(DeviceDecoder(template, device=self.engine.device))
+                return closing.enter_context(DeviceDecoder(template, device=self.engine.device, event_strings=strings))
 
             counters, n_agg, d = self._fold_fetches(fetches, new_decoder, -1, capacity=capacity, overlap=overlap, n_partitions=n_partitions, framing_threads=framing_threads,
                                                     consumer_threads=consumer_threads, bound_log=bound_log, device_crc=device_crc, in_place=in_place)
@@ -152,6 +163,8 @@ class TopicRecoveries:
                 self._bind_all_none(capacity)
             if d is not None:
                 counters.update(d.counters())
+            if strings is not None:  # (the decoder's buffers go with it: the columns are cloned out, as the state-topic resume does)
+                self.state_strings = None if d is None else [None if col is None else (col[0].clone(), col[1].clone()) for col in d.state_strings()]
             self._recovery_ends(d, closing, host_keys)
         self._restored = True
         return counters
@@ -286,7 +299,7 @@ class TopicRecoveries:
 
     def restore_from_state_topic(self, fetches, n_partitions: int = 0, template=None, events_tail: Sequence = (), framing_threads: int = 4,
                                  device_crc: bool = True, in_place: bool = True, envelope: str = "none", events_fetches=None, events_from=None,
-                                 events_partitions: int = 0, host_keys: bool = True) -> dict:
+                                 events_partitions: int = 0, host_keys: bool = True, keep_event_strings: bool = False) -> dict:
         """``restore_from_state_records`` from what a consumer of the state topic actually receives: ``fetches`` yields the
         topic's bytes — message-format-v2 record batches, LZ4 or uncompressed, transactional, with the producer's flush
         records, tombstones as null values and the offset gaps log compaction leaves — one ``bytes`` per fetch, or with
@@ -303,7 +316,12 @@ class TopicRecoveries:
         16-byte fixed events when the values are those): the ids it interned are the resident state's rows, so the tail's
         events find their aggregates, and new ids are numbered behind them.  The tail runs through ``restore_from_fetches``'
         loop with the framers started at ``events_from``: records below a first offset are dropped where records are parsed,
-        on the device.  Aggregates that first appear in the tail have the strings ``restore_from_fetches`` gives them (none).
+        on the device.  Aggregates that first appear in the tail have the strings ``restore_from_fetches`` gives them (none) —
+        unless ``keep_event_strings=True`` (with ``events_fetches`` and a ``template`` that has STR parts; ``ValueError``
+        otherwise, and for a model without the hook ``event_string_fields()``, before anything of the store changes): the
+        continued decoder is armed with the model's ``event_string_fields()`` as ``restore_from_fetches(keep_strings=True)``
+        arms its own, and the tail's events replace and extend the restored columns — aggregates that first appear in the tail,
+        and tombstoned ids it creates again, have the tail's strings on both read paths.
         Returns the framer's and the decoder's counters plus the summed decode counts; with ``events_fetches`` the tail's own
         under ``tail_*`` names.  ``host_keys=False``: as in ``restore_from_fetches`` — the decoder (state, or continued as the
         tail's events decoder) stays and serves the reads; a non-empty ``events_tail`` needs the host table and builds it."""
@@ -319,6 +337,11 @@ class TopicRecoveries:
                 raise ValueError("one events partition (events_partitions=0) takes one first offset")
             events_from = int(events_from[0])
         template = template or JsonTemplate.counter()
+        tail_strings = None
+        if keep_event_strings:
+            if events_fetches is None or not _str_columns(template):
+                raise ValueError("keep_event_strings: the tail's strings go into the columns a template with STR parts restores, from events_fetches")
+            tail_strings = _event_strings_of(self.model)
         self._drop_decoder()  # an earlier device-route restore's — behind every refusal of an argument: a call that is refused changes nothing
         self.read_template, self.read_envelope = template, envelope
         eng = self.engine
@@ -350,6 +373,10 @@ class TopicRecoveries:
                 if events_fetches is not None:  # fold(prev snapshot, new events): the same decoder reads the events behind the snapshot
                     def as_events_decoder(event_template):
                         d.continue_as_events(event_template)
+                        if tail_strings is not None:  # the tail's strings go into the same columns
+                            if event_template is None:
+                                raise ValueError("keep_event_strings: the tail's values are 16-byte fixed events, which carry no strings")
+                            d.keep_event_strings(tail_strings)
                         return d
 
                     state_counts, below_before = d.counters(), d.below_floor()
@@ -421,6 +448,14 @@ def _pushes_finished_on_the_way_out(decoder_if_any):
                     d.finish()
                 except Exception:
                     pass
+
+
+def _event_strings_of(model):
+    """The model's ``event_string_fields()`` (an optional hook: read with ``getattr``), or ``ValueError`` for a model without it."""
+    hook = getattr(model, "event_string_fields", None)
+    if hook is None:
+        raise ValueError(f"keep_strings: {type(model).__name__} has no event_string_fields() hook (which event class carries which string)")
+    return hook()
 
 
 class _NotDeviceDecodable(ValueError):
