@@ -17,6 +17,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.abspath(os.path.join(_HERE, "..", "include"))
 LIB_PATH = os.path.join(_HERE, "libsurge_replay.so")
+
+
 def _read_sources() -> tuple:
     """The translation units, from ``csrc/SOURCES`` — the one list the Makefile reads too (tests/test_abi.py)."""
     with open(os.path.join(CSRC, "SOURCES")) as f:
@@ -28,192 +30,204 @@ SOURCES = _read_sources()
 HEADERS = tuple(sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))) + tuple(
     os.path.join(INCLUDE, f) for f in ("surge_replay.h", "surge_ingest.h", "surge_snapshot.h"))
 
-#: every symbol ``include/surge_replay.h`` declares (checked by tests/test_abi.py)
-EXPORTS = (
-    "surge_replay_default_schema",
-    "surge_replay_create",
-    "surge_replay_create_v2",
-    "surge_replay_kernel_info",
-    "surge_replay_compile_schema_v2",
-    "surge_replay_compile_schema",
-    "surge_replay_destroy",
-    "surge_replay_last_error",
-    "surge_replay_set_stream",
-    "surge_replay_get_stream",
-    "surge_replay_synchronize",
-    "surge_replay_load_csr",
-    "surge_replay_bind_device_csr",
-    "surge_replay_fold",
-    "surge_replay_prepare",
-    "surge_replay_layout_info",
-    "surge_replay_index_order",
-    "surge_replay_stage_reserve",
-    "surge_replay_stage_events_device",
-    "surge_replay_staged",
-    "surge_replay_pack_staged",
-    "surge_replay_bound_log",
-    "surge_replay_append_fold",
-    "surge_replay_append_events",
-    "surge_replay_append_events_device",
-    "surge_replay_append_fold_device",
-    "surge_replay_get",
-    "surge_replay_gather",
-    "surge_replay_snapshot",
-    "surge_replay_device_state",
-    "surge_replay_snapshot_delta",
-    "surge_replay_snapshot_commit",
-    "surge_replay_snapshot_invalidate",
-    "surge_replay_set_encode_filter",
-    "surge_replay_set_encode_strings",
-    "surge_format_f64_json",
-    "surge_format_f64_json_many",
-    "surge_replay_encode_json",
-    "surge_replay_encode_protobuf_state",
-    "surge_replay_encode_json_rows",
-    "surge_replay_encode_protobuf_state_rows",
-    "surge_replay_decode_json_states",
-    "surge_replay_decode_protobuf_states",
-    "surge_replay_merge_state_strings",
-    "surge_replay_set_decode_base",
-    "surge_replay_pack_states",
-    "surge_replay_unpack_states",
-    "surge_replay_partition_hash",
-    "surge_replay_partition_hash_device",
-    "surge_replay_partition_hash_up_to_colon",
-    "surge_replay_partition_hash_up_to_colon_device",
-    "surge_replay_set_state_out",
-    "surge_replay_grow",
-    "surge_replay_comm_unique_id",
-    "surge_replay_comm_init",
-    "surge_replay_comm_destroy",
-    "surge_replay_comm_info",
-    "surge_replay_comm_counts",
-    "surge_replay_allgather_snapshot",
-    "surge_replay_allgather",
-    "surge_replay_comm_wait",
-    "surge_replay_gathered",
-    "surge_replay_gathered_read",
-    "surge_replay_stats",
-    "surge_replay_stats_reset",
-    "surge_replay_fold_times",
-    "surge_replay_stream_probe",
-)
+_vp, _i64, _i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
 
-#: every symbol ``include/surge_ingest.h`` declares
-INGEST_EXPORTS = (
-    "surge_ingest_create",
-    "surge_ingest_destroy",
-    "surge_ingest_last_error",
-    "surge_ingest_feed",
-    "surge_ingest_set_threads",
-    "surge_ingest_ready",
-    "surge_ingest_drain",
-    "surge_ingest_arena",
-    "surge_ingest_drain_fixed16",
-    "surge_ingest_drain_json",
-    "surge_ingest_drain_sections",
-    "surge_ingest_group_create",
-    "surge_ingest_group_destroy",
-    "surge_ingest_group_last_error",
-    "surge_ingest_group_feed",
-    "surge_ingest_group_receive_buffer",
-    "surge_ingest_group_receive_copy",
-    "surge_ingest_group_cpu_seconds",
-    "surge_ingest_group_slab_bytes",
-    "surge_ingest_group_queued_sections",
-    "surge_ingest_group_counters",
-    "surge_ingest_group_set_allocator",
-    "surge_ingest_group_use_pinned_slabs",
-    "surge_ingest_set_allocator",
-    "surge_ingest_use_pinned_arena",
-    "surge_device_decoder_create",
-    "surge_device_decoder_create_states",
-    "surge_device_decoder_destroy",
-    "surge_device_decoder_last_error",
-    "surge_device_decoder_push",
-    "surge_device_decoder_push_records",
-    "surge_device_decoder_push_async",
-    "surge_device_decoder_push_parts_async",
-    "surge_device_decoder_push_parts_floored_async",
-    "surge_device_decoder_push_floored",
-    "surge_device_decoder_below_floor",
-    "surge_device_decoder_continue_as_events",
-    "surge_device_decoder_push_finish",
-    "surge_device_decoder_push_finish_async",
-    "surge_device_decoder_pending",
-    "surge_device_decoder_reserve",
-    "surge_device_decoder_result",
-    "surge_device_decoder_state_result",
-    "surge_device_decoder_clear",
-    "surge_device_decoder_load_states",
-    "surge_device_decoder_load_protobuf_states",
-    "surge_device_decoder_keep_strings",
-    "surge_device_decoder_state_strings",
-    "surge_device_decoder_keep_event_strings",
-    "surge_device_decoder_event_strings_pending",
-    "surge_device_decoder_event_strings_next_column",
-    "surge_replay_append_decoded",
-    "surge_replay_append_decoded_async",
-    "surge_replay_stage_decoded",
-    "surge_device_decoder_keys",
-    "surge_device_decoder_key_table",
-    "surge_device_decoder_lookup",
-    "surge_device_decoder_lookup_device",
-    "surge_device_decoder_range_device",
-    "surge_device_decoder_gather_keys_device",
-    "surge_device_decoder_key_order",
-    "surge_device_decoder_counters",
-    "surge_device_decoder_stats",
-    "surge_event_json_validate",
-    "surge_event_json_decode",
-    "surge_event_json_decode_keyed",
-    "surge_event_json_last_error",
-    "surge_event_json_string_spans",
-    "surge_parse_f64_json",
-    "surge_ingest_key_count",
-    "surge_ingest_key",
-    "surge_ingest_counters",
-    "surge_ingest_set_start_offset",
-    "surge_ingest_take_floors",
-    "surge_ingest_position",
-    "surge_ingest_below_start",
-    "surge_ingest_group_set_start_offsets",
-    "surge_ingest_group_take_floors",
-    "surge_ingest_group_positions",
-    "surge_ingest_group_below_start",
-    "surge_crc32c",
-    "surge_crc32c_portable",
-    "surge_lz4_frame_decompress",
-    "surge_lz4_frame_bound",
-    "surge_lz4_frame_compress",
-    "surge_xxh32",
-)
+# One table per header: every symbol it declares, name -> (argtypes, restype).  The export tuples below are these tables' keys
+# (tests/test_abi.py holds them against the headers) and ``load()`` sets the signatures from them: a new export is named once.
+#: ``include/surge_replay.h``
+REPLAY_H = {
+    "surge_replay_default_schema": ([ctypes.POINTER(CSchema)], _i32),
+    "surge_replay_create": ([ctypes.POINTER(CSchema), _i32, ctypes.POINTER(_vp)], _i32),
+    "surge_replay_create_v2": ([_vp, _i32, ctypes.POINTER(_vp)], _i32),
+    "surge_replay_kernel_info": ([_vp, ctypes.POINTER(CKernelInfo)], _i32),
+    "surge_replay_compile_schema_v2": ([_vp, ctypes.c_char_p, _vp, _i64, ctypes.POINTER(_i64)], _i32),
+    "surge_replay_compile_schema": ([_vp, ctypes.c_char_p, _vp, _i64, ctypes.POINTER(_i64)], _i32),
+    "surge_replay_destroy": ([_vp], _i32),
+    "surge_replay_last_error": ([_vp], ctypes.c_char_p),
+    "surge_replay_set_stream": ([_vp, _vp], _i32),
+    "surge_replay_get_stream": ([_vp, ctypes.POINTER(_vp)], _i32),
+    "surge_replay_synchronize": ([_vp], _i32),
+    "surge_replay_load_csr": ([_vp, _vp, _i64, _vp, _i64, _vp], _i32),
+    "surge_replay_bind_device_csr": ([_vp, _vp, _i64, _vp, _i64, _vp, _vp], _i32),
+    "surge_replay_fold": ([_vp, _i32], _i32),
+    "surge_replay_prepare": ([_vp, _i32], _i32),
+    "surge_replay_layout_info": ([_vp, ctypes.POINTER(CLayoutInfo)], _i32),
+    "surge_replay_index_order": ([_vp, _i32, _vp, _i64, ctypes.POINTER(_i64)], _i32),
+    "surge_replay_stage_reserve": ([_vp, _i64], _i32),
+    "surge_replay_stage_events_device": ([_vp, _vp, _vp, _i64], _i32),
+    "surge_replay_staged": ([_vp, ctypes.POINTER(_i64)], _i32),
+    "surge_replay_pack_staged": ([_vp, _i64], _i32),
+    "surge_replay_bound_log": ([_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _i32),
+    "surge_replay_append_fold": ([_vp, _vp, _vp, _i64, _vp, _i64], _i32),
+    "surge_replay_append_fold_device": ([_vp, _vp, _vp, _i64, _vp, _i64], _i32),
+    "surge_replay_append_events": ([_vp, _vp, _vp, _i64], _i32),
+    "surge_replay_append_events_device": ([_vp, _vp, _vp, _i64], _i32),
+    "surge_replay_get": ([_vp, _i64, _vp, ctypes.POINTER(ctypes.c_uint8)], _i32),
+    "surge_replay_gather": ([_vp, _vp, _i64, _vp], _i32),
+    "surge_replay_snapshot": ([_vp, _vp, _vp], _i32),
+    "surge_replay_device_state": ([_vp, ctypes.POINTER(_vp), ctypes.POINTER(_i64)], _i32),
+    "surge_replay_snapshot_delta": ([_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), _i32], _i32),
+    "surge_replay_set_encode_filter": ([_vp, _vp], _i32),
+    "surge_replay_snapshot_commit": ([_vp, _vp], _i32),
+    "surge_replay_snapshot_invalidate": ([_vp, _vp], _i32),
+    "surge_replay_set_encode_strings": ([_vp, _i32, _vp, _vp], _i32),
+    "surge_format_f64_json": ([ctypes.c_uint64, _vp, _i32], _i32),
+    "surge_format_f64_json_many": ([_vp, _i64, _vp, _i64, _vp], _i64),
+    "surge_replay_encode_json": ([_vp, _vp, _vp, _vp, _vp, _i64, _vp, ctypes.POINTER(_i64)], _i32),
+    "surge_replay_encode_protobuf_state": ([_vp, _vp, _vp, _vp, _vp, _i64, _vp, ctypes.POINTER(_i64)], _i32),
+    "surge_replay_encode_json_rows": ([_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, ctypes.POINTER(_i64)], _i32),
+    "surge_replay_encode_protobuf_state_rows": ([_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, ctypes.POINTER(_i64)], _i32),
+    "surge_replay_decode_json_states": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, ctypes.POINTER(_i64 * 4)], _i32),
+    "surge_replay_set_decode_base": ([_vp, _vp], _i32),
+    "surge_replay_decode_protobuf_states": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, ctypes.POINTER(_i64 * 4)], _i32),
+    "surge_decode_json_state": ([_vp, _vp, _i64, _vp, _i64, _vp, _vp], _i32),
+    "surge_decode_protobuf_state": ([_vp, _vp, _i64, _vp, _i64, _vp, _vp], _i32),
+    "surge_unescape_json_string": ([_vp, _i64, _vp, _i64], _i64),
+    "surge_replay_merge_state_strings": ([_vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, ctypes.POINTER(_i64)], _i32),
+    "surge_replay_pack_states": ([_vp, _vp, _i64, _vp, _vp], _i32),
+    "surge_replay_unpack_states": ([_vp, _vp, _i64, _vp, _vp], _i32),
+    "surge_replay_partition_hash": ([_vp, _vp, _i64, _i32, _vp], _i32),
+    "surge_replay_partition_hash_device": ([_vp, _vp, _vp, _i64, _i32, _vp], _i32),
+    "surge_replay_partition_hash_up_to_colon": ([_vp, _vp, _i64, _i32, _vp], _i32),
+    "surge_replay_partition_hash_up_to_colon_device": ([_vp, _vp, _vp, _i64, _i32, _vp], _i32),
+    "surge_replay_set_state_out": ([_vp, _vp], _i32),
+    "surge_replay_grow": ([_vp, _i64], _i32),
+    "surge_replay_comm_unique_id": ([_vp], _i32),
+    "surge_replay_comm_init": ([_vp, _i32, _i32, _vp], _i32),
+    "surge_replay_comm_destroy": ([_vp], _i32),
+    "surge_replay_comm_info": ([_vp, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(ctypes.c_char_p)], _i32),
+    "surge_replay_comm_counts": ([_vp, _i64, _vp, ctypes.POINTER(_i64)], _i32),
+    "surge_replay_allgather_snapshot": ([_vp, _vp, _i64, _vp, _i64, _i32, _i32], _i32),
+    "surge_replay_allgather": ([_vp, _i32, _vp, _vp, _i64, _i32], _i32),
+    "surge_replay_comm_wait": ([_vp, _i32, _i32], _i32),
+    "surge_replay_gathered": ([_vp, _i32, ctypes.POINTER(_vp), ctypes.POINTER(_i64)], _i32),
+    "surge_replay_gathered_read": ([_vp, _i32, _i32, _i64, _i64, _vp], _i32),
+    "surge_replay_stats": ([_vp, ctypes.POINTER(CStats)], _i32),
+    "surge_replay_stats_reset": ([_vp], _i32),
+    "surge_replay_fold_times": ([_vp, _vp, _i64, ctypes.POINTER(_i64)], _i32),
+    "surge_replay_stream_probe": ([_vp, _vp, _i64, ctypes.POINTER(ctypes.c_double)], _i32),
+}
 
-#: every symbol ``include/surge_snapshot.h`` declares
-SNAPSHOT_EXPORTS = (
-    "surge_snapshot_writer_create",
-    "surge_snapshot_writer_destroy",
-    "surge_snapshot_writer_set_compression",
-    "surge_snapshot_writer_last_error",
-    "surge_snapshot_writer_append",
-    "surge_snapshot_writer_append_indexed",
-    "surge_snapshot_writer_flush",
-    "surge_snapshot_writer_partition",
-    "surge_snapshot_writer_reset",
-    "surge_device_framer_create",
-    "surge_device_framer_destroy",
-    "surge_device_framer_last_error",
-    "surge_device_framer_set_compression",
-    "surge_device_framer_frame",
-    "surge_device_framer_next_offsets",
-    "surge_device_framer_uncompressed_bytes",
-)
+#: ``include/surge_ingest.h``
+INGEST_H = {
+    "surge_ingest_create": ([_i32, ctypes.POINTER(_vp)], _i32),
+    "surge_ingest_destroy": ([_vp], _i32),
+    "surge_ingest_last_error": ([_vp], ctypes.c_char_p),
+    "surge_ingest_feed": ([_vp, _vp, _i64, ctypes.POINTER(_i64)], _i32),
+    "surge_ingest_set_threads": ([_vp, _i32], _i32),
+    "surge_ingest_ready": ([_vp], _i64),
+    "surge_ingest_drain": ([_vp, _i64, _vp, ctypes.POINTER(_i64)], _i32),
+    "surge_ingest_arena": ([_vp], _vp),
+    "surge_ingest_drain_fixed16": ([_vp, _i64, _vp, _vp, _vp, ctypes.POINTER(_i64)], _i32),
+    "surge_ingest_drain_json": ([_vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(_i64)], _i32),
+    "surge_ingest_drain_sections": ([_vp, _i64, _vp, ctypes.POINTER(_i64)], _i32),
+    "surge_ingest_group_create": ([_i32, _i32, ctypes.POINTER(_vp)], _i32),
+    "surge_ingest_group_destroy": ([_vp], _i32),
+    "surge_ingest_group_last_error": ([_vp], ctypes.c_char_p),
+    "surge_ingest_group_feed": ([_vp, _vp, _vp, _i32, _vp, _i64, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_vp)], _i32),
+    "surge_ingest_group_receive_buffer": ([_vp, _i64, ctypes.POINTER(_vp)], _i32),
+    "surge_ingest_group_receive_copy": ([_vp, _vp, _vp, _i32, _vp], _i32),
+    "surge_ingest_group_cpu_seconds": ([_vp, ctypes.POINTER(ctypes.c_double * 2)], _i32),
+    "surge_ingest_group_slab_bytes": ([_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i32)], _i32),
+    "surge_ingest_group_queued_sections": ([_vp], _i64),
+    "surge_ingest_group_counters": ([_vp, ctypes.POINTER(_i64 * 8)], _i32),
+    "surge_ingest_group_set_allocator": ([_vp, _vp, _vp], _i32),
+    "surge_ingest_group_use_pinned_slabs": ([_vp], _i32),
+    "surge_ingest_set_allocator": ([_vp, _vp, _vp], _i32),
+    "surge_ingest_use_pinned_arena": ([_vp], _i32),
+    "surge_device_decoder_create": ([_i32, _vp, _vp, ctypes.POINTER(_vp)], _i32),
+    "surge_device_decoder_create_states": ([_i32, _vp, ctypes.POINTER(_vp)], _i32),
+    "surge_device_decoder_destroy": ([_vp], _i32),
+    "surge_device_decoder_last_error": ([_vp], ctypes.c_char_p),
+    "surge_device_decoder_push": ([_vp, _vp, _vp, _i64], _i32),
+    "surge_device_decoder_push_records": ([_vp, _vp, _vp, _vp, _vp, _vp, _i64], _i32),
+    "surge_device_decoder_push_async": ([_vp, _vp, _vp, _i64], _i32),
+    "surge_device_decoder_push_parts_async": ([_vp, _i32, _vp, _vp, _vp], _i32),
+    "surge_device_decoder_push_parts_floored_async": ([_vp, _i32, _vp, _vp, _vp, _i64, _vp], _i32),
+    "surge_device_decoder_push_floored": ([_vp, _vp, _vp, _i64, _i64, _vp], _i32),
+    "surge_device_decoder_below_floor": ([_vp, ctypes.POINTER(_i64)], _i32),
+    "surge_device_decoder_continue_as_events": ([_vp, _vp], _i32),
+    "surge_device_decoder_push_finish": ([_vp], _i32),
+    "surge_device_decoder_push_finish_async": ([_vp], _i32),
+    "surge_device_decoder_pending": ([_vp], _i32),
+    "surge_device_decoder_reserve": ([_vp, _i64, _i64], _i32),
+    "surge_device_decoder_result": ([_vp, ctypes.POINTER(_i64), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i64)], _i32),
+    "surge_device_decoder_state_result": ([_vp, ctypes.POINTER(_i64), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
+                                           ctypes.POINTER(_i64)], _i32),
+    "surge_device_decoder_clear": ([_vp], _i32),
+    "surge_device_decoder_load_states": ([_vp, _vp, _vp, ctypes.POINTER(_i64 * 4)], _i32),
+    "surge_device_decoder_load_protobuf_states": ([_vp, _vp, _vp, ctypes.POINTER(_i64 * 4)], _i32),
+    "surge_device_decoder_keep_strings": ([_vp, _i32], _i32),
+    "surge_device_decoder_state_strings": ([_vp, _i32, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i64)], _i32),
+    "surge_device_decoder_keep_event_strings": ([_vp, _vp], _i32),
+    "surge_device_decoder_event_strings_next_column": ([_vp, _i32, ctypes.POINTER(_i64 * 3), ctypes.POINTER(_vp), ctypes.POINTER(_vp)], _i32),
+    "surge_device_decoder_event_strings_pending": ([_vp, ctypes.POINTER(_i64 * 4), ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp)], _i32),
+    "surge_event_strings_validate": ([_vp, _vp], _i32),
+    "surge_event_json_string_spans": ([_vp, _vp, _vp, _i64, _vp, _vp], _i32),
+    "surge_replay_append_decoded": ([_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _i32),
+    "surge_replay_append_decoded_async": ([_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _i32),
+    "surge_replay_stage_decoded": ([_vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _i32),
+    "surge_device_decoder_keys": ([_vp, _vp, _i64, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _i32),
+    "surge_device_decoder_key_table": ([_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp)], _i32),
+    "surge_device_decoder_lookup": ([_vp, _vp, _vp, _i64, _vp], _i32),
+    "surge_device_decoder_lookup_device": ([_vp, _vp, _vp, _i64, _vp], _i32),
+    "surge_device_decoder_range_device": ([_vp, _vp, _i64, _vp, _i64, _vp, _i64, ctypes.POINTER(_i64)], _i32),
+    "surge_device_decoder_gather_keys_device": ([_vp, _vp, _i64, _vp, _i64, _vp, ctypes.POINTER(_i64)], _i32),
+    "surge_device_decoder_key_order": ([_vp, ctypes.POINTER(_vp), ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _i32),
+    "surge_device_decoder_counters": ([_vp, ctypes.POINTER(_i64 * 4)], _i32),
+    "surge_device_decoder_stats": ([_vp, ctypes.POINTER(_i64 * 8)], _i32),
+    "surge_event_json_validate": ([_vp], _i32),
+    "surge_event_json_decode": ([_vp, _vp, _i64, _vp], _i32),
+    "surge_event_json_decode_keyed": ([_vp, _vp, _i64, _vp, _i64, _vp], _i32),
+    "surge_event_json_last_error": ([], ctypes.c_char_p),
+    "surge_parse_f64_json": ([_vp, _i64, ctypes.POINTER(ctypes.c_uint64)], _i32),
+    "surge_ingest_key_count": ([_vp], _i64),
+    "surge_ingest_key": ([_vp, _i64, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_i64)], _i32),
+    "surge_ingest_counters": ([_vp, ctypes.POINTER(_i64 * 8)], _i32),
+    "surge_ingest_set_start_offset": ([_vp, _i64], _i32),
+    "surge_ingest_take_floors": ([_vp, _i64, _vp, ctypes.POINTER(_i64)], _i32),
+    "surge_ingest_position": ([_vp], _i64),
+    "surge_ingest_below_start": ([_vp, ctypes.POINTER(_i64 * 2)], _i32),
+    "surge_ingest_group_set_start_offsets": ([_vp, _vp], _i32),
+    "surge_ingest_group_take_floors": ([_vp, _i64, _vp, ctypes.POINTER(_i64)], _i32),
+    "surge_ingest_group_positions": ([_vp, _vp], _i32),
+    "surge_ingest_group_below_start": ([_vp, ctypes.POINTER(_i64 * 2)], _i32),
+    "surge_crc32c": ([_vp, _i64], ctypes.c_uint32),
+    "surge_crc32c_portable": ([_vp, _i64], ctypes.c_uint32),
+    "surge_lz4_frame_decompress": ([_vp, _i64, _vp, _i64], _i64),
+    "surge_lz4_frame_bound": ([_i64], _i64),
+    "surge_lz4_frame_compress": ([_vp, _i64, _vp, _i64], _i64),
+    "surge_xxh32": ([_vp, _i64, ctypes.c_uint32], ctypes.c_uint32),
+}
+
+#: ``include/surge_snapshot.h``
+SNAPSHOT_H = {
+    "surge_snapshot_writer_create": ([_i32, _i32, _i64, ctypes.POINTER(_vp)], _i32),
+    "surge_snapshot_writer_destroy": ([_vp], _i32),
+    "surge_snapshot_writer_last_error": ([_vp], ctypes.c_char_p),
+    "surge_snapshot_writer_append": ([_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64], _i32),
+    "surge_snapshot_writer_append_indexed": ([_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64], _i32),
+    "surge_snapshot_writer_flush": ([_vp], _i32),
+    "surge_snapshot_writer_partition": ([_vp, _i32, ctypes.POINTER(_vp), ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _i32),
+    "surge_snapshot_writer_reset": ([_vp], _i32),
+    "surge_snapshot_writer_set_compression": ([_vp, _i32], _i32),
+    "surge_device_framer_create": ([_i32, _vp, _i32, _i32, _i64, ctypes.POINTER(_vp)], _i32),
+    "surge_device_framer_destroy": ([_vp], _i32),
+    "surge_device_framer_last_error": ([_vp], ctypes.c_char_p),
+    "surge_device_framer_set_compression": ([_vp, _i32], _i32),
+    "surge_device_framer_frame": ([_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _i32),
+    "surge_device_framer_next_offsets": ([_vp, _vp], _i32),
+    "surge_device_framer_uncompressed_bytes": ([_vp], _i64),
+}
 
 #: the host half of the state decoder (declared in ``include/surge_replay.h``; needs no handle and no device)
 STATE_EXPORTS = ("surge_decode_json_state", "surge_decode_protobuf_state", "surge_unescape_json_string")
-
-#: which event class carries which string (declared in ``include/surge_ingest.h`` beside the two exports above that use it)
+#: which event class carries which string (declared in ``include/surge_ingest.h`` beside the two exports that use it)
 EVENT_STRINGS_EXPORTS = ("surge_event_strings_validate",)
+#: what each header declares beside those
+EXPORTS = tuple(n for n in REPLAY_H if n not in STATE_EXPORTS)
+INGEST_EXPORTS = tuple(n for n in INGEST_H if n not in EVENT_STRINGS_EXPORTS)
+SNAPSHOT_EXPORTS = tuple(SNAPSHOT_H)
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -306,193 +320,12 @@ def load() -> ctypes.CDLL:
         L = ctypes.CDLL(lib_path)
     except OSError as e:
         raise NativeLibraryError(f"cannot load {lib_path}: {e}") from e
-    vp, i64, i32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
-    sig = {
-        "surge_replay_default_schema": ([ctypes.POINTER(CSchema)], i32),
-        "surge_replay_create": ([ctypes.POINTER(CSchema), i32, ctypes.POINTER(vp)], i32),
-        "surge_replay_create_v2": ([vp, i32, ctypes.POINTER(vp)], i32),
-        "surge_replay_kernel_info": ([vp, ctypes.POINTER(CKernelInfo)], i32),
-        "surge_replay_compile_schema_v2": ([vp, ctypes.c_char_p, vp, i64, ctypes.POINTER(i64)], i32),
-        "surge_replay_compile_schema": ([vp, ctypes.c_char_p, vp, i64, ctypes.POINTER(i64)], i32),
-        "surge_replay_destroy": ([vp], i32),
-        "surge_replay_last_error": ([vp], ctypes.c_char_p),
-        "surge_replay_set_stream": ([vp, vp], i32),
-        "surge_replay_get_stream": ([vp, ctypes.POINTER(vp)], i32),
-        "surge_replay_synchronize": ([vp], i32),
-        "surge_replay_load_csr": ([vp, vp, i64, vp, i64, vp], i32),
-        "surge_replay_bind_device_csr": ([vp, vp, i64, vp, i64, vp, vp], i32),
-        "surge_replay_fold": ([vp, i32], i32),
-        "surge_replay_prepare": ([vp, i32], i32),
-        "surge_replay_layout_info": ([vp, ctypes.POINTER(CLayoutInfo)], i32),
-        "surge_replay_index_order": ([vp, i32, vp, i64, ctypes.POINTER(i64)], i32),
-        "surge_replay_stage_reserve": ([vp, i64], i32),
-        "surge_replay_stage_events_device": ([vp, vp, vp, i64], i32),
-        "surge_replay_staged": ([vp, ctypes.POINTER(i64)], i32),
-        "surge_replay_pack_staged": ([vp, i64], i32),
-        "surge_replay_bound_log": ([vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
-        "surge_replay_append_fold": ([vp, vp, vp, i64, vp, i64], i32),
-        "surge_replay_append_fold_device": ([vp, vp, vp, i64, vp, i64], i32),
-        "surge_replay_append_events": ([vp, vp, vp, i64], i32),
-        "surge_replay_append_events_device": ([vp, vp, vp, i64], i32),
-        "surge_replay_get": ([vp, i64, vp, ctypes.POINTER(ctypes.c_uint8)], i32),
-        "surge_replay_gather": ([vp, vp, i64, vp], i32),
-        "surge_replay_snapshot": ([vp, vp, vp], i32),
-        "surge_replay_device_state": ([vp, ctypes.POINTER(vp), ctypes.POINTER(i64)], i32),
-        "surge_replay_snapshot_delta": ([vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64), i32], i32),
-        "surge_replay_set_encode_filter": ([vp, vp], i32),
-        "surge_replay_snapshot_commit": ([vp, vp], i32),
-        "surge_replay_snapshot_invalidate": ([vp, vp], i32),
-        "surge_replay_set_encode_strings": ([vp, i32, vp, vp], i32),
-        "surge_format_f64_json": ([ctypes.c_uint64, vp, i32], i32),
-        "surge_format_f64_json_many": ([vp, i64, vp, i64, vp], i64),
-        "surge_replay_encode_json": ([vp, vp, vp, vp, vp, i64, vp, ctypes.POINTER(i64)], i32),
-        "surge_replay_encode_protobuf_state": ([vp, vp, vp, vp, vp, i64, vp, ctypes.POINTER(i64)], i32),
-        "surge_replay_encode_json_rows": ([vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, ctypes.POINTER(i64)], i32),
-        "surge_replay_encode_protobuf_state_rows": ([vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, ctypes.POINTER(i64)], i32),
-        "surge_replay_decode_json_states": ([vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, ctypes.POINTER(i64 * 4)], i32),
-        "surge_replay_set_decode_base": ([vp, vp], i32),
-        "surge_replay_decode_protobuf_states": ([vp, vp, vp, vp, i64, vp, vp, vp, i64, vp, vp, vp, ctypes.POINTER(i64 * 4)], i32),
-        "surge_decode_json_state": ([vp, vp, i64, vp, i64, vp, vp], i32),
-        "surge_decode_protobuf_state": ([vp, vp, i64, vp, i64, vp, vp], i32),
-        "surge_unescape_json_string": ([vp, i64, vp, i64], i64),
-        "surge_replay_merge_state_strings": ([vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, i64, vp, ctypes.POINTER(i64)], i32),
-        "surge_replay_pack_states": ([vp, vp, i64, vp, vp], i32),
-        "surge_replay_unpack_states": ([vp, vp, i64, vp, vp], i32),
-        "surge_replay_partition_hash": ([vp, vp, i64, i32, vp], i32),
-        "surge_replay_partition_hash_device": ([vp, vp, vp, i64, i32, vp], i32),
-        "surge_replay_partition_hash_up_to_colon": ([vp, vp, i64, i32, vp], i32),
-        "surge_replay_partition_hash_up_to_colon_device": ([vp, vp, vp, i64, i32, vp], i32),
-        "surge_replay_set_state_out": ([vp, vp], i32),
-        "surge_replay_grow": ([vp, i64], i32),
-        "surge_replay_comm_unique_id": ([vp], i32),
-        "surge_replay_comm_init": ([vp, i32, i32, vp], i32),
-        "surge_replay_comm_destroy": ([vp], i32),
-        "surge_replay_comm_info": ([vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_char_p)], i32),
-        "surge_replay_comm_counts": ([vp, i64, vp, ctypes.POINTER(i64)], i32),
-        "surge_replay_allgather_snapshot": ([vp, vp, i64, vp, i64, i32, i32], i32),
-        "surge_replay_allgather": ([vp, i32, vp, vp, i64, i32], i32),
-        "surge_replay_comm_wait": ([vp, i32, i32], i32),
-        "surge_replay_gathered": ([vp, i32, ctypes.POINTER(vp), ctypes.POINTER(i64)], i32),
-        "surge_replay_gathered_read": ([vp, i32, i32, i64, i64, vp], i32),
-        "surge_replay_stats": ([vp, ctypes.POINTER(CStats)], i32),
-        "surge_replay_stats_reset": ([vp], i32),
-        "surge_replay_fold_times": ([vp, vp, i64, ctypes.POINTER(i64)], i32),
-        "surge_replay_stream_probe": ([vp, vp, i64, ctypes.POINTER(ctypes.c_double)], i32),
-    }
-    u8p = ctypes.POINTER(ctypes.c_uint8)
-    sig.update({
-        "surge_ingest_create": ([i32, ctypes.POINTER(vp)], i32),
-        "surge_ingest_destroy": ([vp], i32),
-        "surge_ingest_last_error": ([vp], ctypes.c_char_p),
-        "surge_ingest_feed": ([vp, vp, i64, ctypes.POINTER(i64)], i32),
-        "surge_ingest_set_threads": ([vp, i32], i32),
-        "surge_ingest_ready": ([vp], i64),
-        "surge_ingest_drain": ([vp, i64, vp, ctypes.POINTER(i64)], i32),
-        "surge_ingest_arena": ([vp], vp),
-        "surge_ingest_drain_fixed16": ([vp, i64, vp, vp, vp, ctypes.POINTER(i64)], i32),
-        "surge_ingest_drain_json": ([vp, i64, vp, vp, vp, vp, ctypes.POINTER(i64)], i32),
-        "surge_ingest_drain_sections": ([vp, i64, vp, ctypes.POINTER(i64)], i32),
-        "surge_ingest_group_create": ([i32, i32, ctypes.POINTER(vp)], i32),
-        "surge_ingest_group_destroy": ([vp], i32),
-        "surge_ingest_group_last_error": ([vp], ctypes.c_char_p),
-        "surge_ingest_group_feed": ([vp, vp, vp, i32, vp, i64, vp, ctypes.POINTER(i64), ctypes.POINTER(vp)], i32),
-        "surge_ingest_group_receive_buffer": ([vp, i64, ctypes.POINTER(vp)], i32),
-        "surge_ingest_group_receive_copy": ([vp, vp, vp, i32, vp], i32),
-        "surge_ingest_group_cpu_seconds": ([vp, ctypes.POINTER(ctypes.c_double * 2)], i32),
-        "surge_ingest_group_slab_bytes": ([vp, ctypes.POINTER(i64), ctypes.POINTER(i32)], i32),
-        "surge_ingest_group_queued_sections": ([vp], i64),
-        "surge_ingest_group_counters": ([vp, ctypes.POINTER(i64 * 8)], i32),
-        "surge_ingest_group_set_allocator": ([vp, vp, vp], i32),
-        "surge_ingest_group_use_pinned_slabs": ([vp], i32),
-        "surge_ingest_set_allocator": ([vp, vp, vp], i32),
-        "surge_ingest_use_pinned_arena": ([vp], i32),
-        "surge_device_decoder_create": ([i32, vp, vp, ctypes.POINTER(vp)], i32),
-        "surge_device_decoder_create_states": ([i32, vp, ctypes.POINTER(vp)], i32),
-        "surge_device_decoder_destroy": ([vp], i32),
-        "surge_device_decoder_last_error": ([vp], ctypes.c_char_p),
-        "surge_device_decoder_push": ([vp, vp, vp, i64], i32),
-        "surge_device_decoder_push_records": ([vp, vp, vp, vp, vp, vp, i64], i32),
-        "surge_device_decoder_push_async": ([vp, vp, vp, i64], i32),
-        "surge_device_decoder_push_parts_async": ([vp, i32, vp, vp, vp], i32),
-        "surge_device_decoder_push_parts_floored_async": ([vp, i32, vp, vp, vp, i64, vp], i32),
-        "surge_device_decoder_push_floored": ([vp, vp, vp, i64, i64, vp], i32),
-        "surge_device_decoder_below_floor": ([vp, ctypes.POINTER(i64)], i32),
-        "surge_device_decoder_continue_as_events": ([vp, vp], i32),
-        "surge_device_decoder_push_finish": ([vp], i32),
-        "surge_device_decoder_push_finish_async": ([vp], i32),
-        "surge_device_decoder_pending": ([vp], i32),
-        "surge_device_decoder_reserve": ([vp, i64, i64], i32),
-        "surge_device_decoder_result": ([vp, ctypes.POINTER(i64), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64)], i32),
-        "surge_device_decoder_state_result": ([vp, ctypes.POINTER(i64), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp),
-                                               ctypes.POINTER(i64)], i32),
-        "surge_device_decoder_clear": ([vp], i32),
-        "surge_device_decoder_load_states": ([vp, vp, vp, ctypes.POINTER(i64 * 4)], i32),
-        "surge_device_decoder_load_protobuf_states": ([vp, vp, vp, ctypes.POINTER(i64 * 4)], i32),
-        "surge_device_decoder_keep_strings": ([vp, i32], i32),
-        "surge_device_decoder_state_strings": ([vp, i32, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64)], i32),
-        "surge_device_decoder_keep_event_strings": ([vp, vp], i32),
-        "surge_device_decoder_event_strings_next_column": ([vp, i32, ctypes.POINTER(i64 * 3), ctypes.POINTER(vp), ctypes.POINTER(vp)], i32),
-        "surge_device_decoder_event_strings_pending": ([vp, ctypes.POINTER(i64 * 4), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp)], i32),
-        "surge_event_strings_validate": ([vp, vp], i32),
-        "surge_event_json_string_spans": ([vp, vp, vp, i64, vp, vp], i32),
-        "surge_replay_append_decoded": ([vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
-        "surge_replay_append_decoded_async": ([vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
-        "surge_replay_stage_decoded": ([vp, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
-        "surge_device_decoder_keys": ([vp, vp, i64, vp, ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
-        "surge_device_decoder_key_table": ([vp, ctypes.POINTER(vp), ctypes.POINTER(vp)], i32),
-        "surge_device_decoder_lookup": ([vp, vp, vp, i64, vp], i32),
-        "surge_device_decoder_lookup_device": ([vp, vp, vp, i64, vp], i32),
-        "surge_device_decoder_range_device": ([vp, vp, i64, vp, i64, vp, i64, ctypes.POINTER(i64)], i32),
-        "surge_device_decoder_gather_keys_device": ([vp, vp, i64, vp, i64, vp, ctypes.POINTER(i64)], i32),
-        "surge_device_decoder_key_order": ([vp, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
-        "surge_device_decoder_counters": ([vp, ctypes.POINTER(i64 * 4)], i32),
-        "surge_device_decoder_stats": ([vp, ctypes.POINTER(i64 * 8)], i32),
-        "surge_event_json_validate": ([vp], i32),
-        "surge_event_json_decode": ([vp, vp, i64, vp], i32),
-        "surge_event_json_decode_keyed": ([vp, vp, i64, vp, i64, vp], i32),
-        "surge_event_json_last_error": ([], ctypes.c_char_p),
-        "surge_parse_f64_json": ([vp, i64, ctypes.POINTER(ctypes.c_uint64)], i32),
-        "surge_ingest_key_count": ([vp], i64),
-        "surge_ingest_key": ([vp, i64, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(i64)], i32),
-        "surge_ingest_counters": ([vp, ctypes.POINTER(i64 * 8)], i32),
-        "surge_ingest_set_start_offset": ([vp, i64], i32),
-        "surge_ingest_take_floors": ([vp, i64, vp, ctypes.POINTER(i64)], i32),
-        "surge_ingest_position": ([vp], i64),
-        "surge_ingest_below_start": ([vp, ctypes.POINTER(i64 * 2)], i32),
-        "surge_ingest_group_set_start_offsets": ([vp, vp], i32),
-        "surge_ingest_group_take_floors": ([vp, i64, vp, ctypes.POINTER(i64)], i32),
-        "surge_ingest_group_positions": ([vp, vp], i32),
-        "surge_ingest_group_below_start": ([vp, ctypes.POINTER(i64 * 2)], i32),
-        "surge_crc32c": ([vp, i64], ctypes.c_uint32),
-        "surge_crc32c_portable": ([vp, i64], ctypes.c_uint32),
-        "surge_lz4_frame_decompress": ([vp, i64, vp, i64], i64),
-        "surge_lz4_frame_bound": ([i64], i64),
-        "surge_lz4_frame_compress": ([vp, i64, vp, i64], i64),
-        "surge_xxh32": ([vp, i64, ctypes.c_uint32], ctypes.c_uint32),
-    })
-    sig.update({
-        "surge_snapshot_writer_create": ([i32, i32, i64, ctypes.POINTER(vp)], i32),
-        "surge_snapshot_writer_destroy": ([vp], i32),
-        "surge_snapshot_writer_last_error": ([vp], ctypes.c_char_p),
-        "surge_snapshot_writer_append": ([vp, i64, vp, vp, vp, vp, vp, vp, i64], i32),
-        "surge_snapshot_writer_append_indexed": ([vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64], i32),
-        "surge_snapshot_writer_flush": ([vp], i32),
-        "surge_snapshot_writer_partition": ([vp, i32, ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
-        "surge_snapshot_writer_reset": ([vp], i32),
-        "surge_snapshot_writer_set_compression": ([vp, i32], i32),
-        "surge_device_framer_create": ([i32, vp, i32, i32, i64, ctypes.POINTER(vp)], i32),
-        "surge_device_framer_destroy": ([vp], i32),
-        "surge_device_framer_last_error": ([vp], ctypes.c_char_p),
-        "surge_device_framer_set_compression": ([vp, i32], i32),
-        "surge_device_framer_frame": ([vp, i64, vp, vp, vp, vp, vp, vp, i64, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(i64), ctypes.POINTER(i64)], i32),
-        "surge_device_framer_next_offsets": ([vp, vp], i32),
-        "surge_device_framer_uncompressed_bytes": ([vp], i64),
-    })
-    for name in EXPORTS + INGEST_EXPORTS + SNAPSHOT_EXPORTS + STATE_EXPORTS + EVENT_STRINGS_EXPORTS:
-        try:
-            fn = getattr(L, name)
-        except AttributeError as e:
-            raise NativeLibraryError(f"{LIB_PATH} does not export {name}") from e
-        fn.argtypes, fn.restype = sig[name]
+    for table in (REPLAY_H, INGEST_H, SNAPSHOT_H):
+        for name, signature in table.items():
+            try:
+                fn = getattr(L, name)
+            except AttributeError as e:
+                raise NativeLibraryError(f"{LIB_PATH} does not export {name}") from e
+            fn.argtypes, fn.restype = signature
     _lib = L
     return L

@@ -1,10 +1,11 @@
 // ingest_decoder.hip — SURVEY §8f N1 on the device: the records sections of Kafka record batches (message format v2,
 // uncompressed or already decompressed by the host framer) -> (aggregate index, 16-byte event, offset) arrays and a key
 // table, all resident in HBM, ready for surge_replay_append_events_device / a CSR build.  This unit is the host object
-// (surge_device_decoder, ingest_decoder_internal.h): its lifecycle, the slot queue and the plain extern "C" exports.  What a
-// push does is ingest_stage1.hip and ingest_stage2.hip, the hand-overs to a replay handle are ingest_handover.hip; the
-// kernels and what launches them are the stage units ingest_crc / ingest_lz4 / ingest_records / ingest_intern .hip
-// (ingest_device.h).
+// (surge_device_decoder, ingest_decoder_internal.h): its lifecycle and options, the slot queue, the push exports, reserve,
+// the results, clear, the switch from states to events, the counters and the pinned-memory helpers.  What a push does is
+// ingest_stage1.hip and ingest_stage2.hip, what reads the key table between pushes ingest_reads.hip, the kept string columns
+// ingest_columns.hip, the hand-overs to a replay handle ingest_handover.hip; the kernels and what launches them are the stage
+// units ingest_crc / ingest_lz4 / ingest_records / ingest_intern / ingest_order / ingest_strings .hip (ingest_device.h).
 //
 // Split of the work (include/surge_ingest.h, "device decode"): the HOST walks the 61-byte batch headers, verifies the
 // CRC-32C (one instruction stream per partition thread), applies read_committed and undoes LZ4 — sequential, cheap per
@@ -16,8 +17,7 @@
 // State mode (surge_device_decoder_create_states) reads the compacted STATE topic with the same stages: the id is the whole key,
 // a null value is a delivered tombstone, no value is decoded — stage 2 gathers the delivered records' value bytes into one
 // buffer behind value_off, and surge_device_decoder_load_states hands them to surge_replay_decode_json_states.
-// Between pushes the key table answers reads: surge_device_decoder_lookup[_device], id -> dense index or -1 (lookup_kernel), and
-// in key order surge_device_decoder_range_device / _gather_keys_device / _key_order (ingest_order.hip; the pass loop is here).
+// Between pushes the key table answers reads, by id and in key order (ingest_reads.hip).
 #include <cstdio>
 #include <cstdlib>
 
@@ -174,7 +174,7 @@ int32_t decoder_create(int32_t device_id, void* hip_stream, const surge_event_js
 // the slot a new push's stage 1 goes into (nullptr with the error set: every slot holds an unfinished push)
 PushSlot* claim_slot(surge_device_decoder* d, int32_t* rc) {
   if (d->poisoned) {
-    *rc = dfail(d, SURGE_E_STATE, "an earlier push failed on the device half way: destroy this decoder and create a new one");
+    *rc = refuse_poisoned(d);
     return nullptr;
   }
   PushSlot* s = nullptr;
@@ -309,7 +309,7 @@ int32_t surge_device_decoder_destroy(surge_device_decoder* d) {
 
 int32_t surge_device_decoder_push_parts_floored_async(surge_device_decoder* d, int32_t n_parts, const uint8_t* const* bytes, const surge_batch_section* const* sections,
                                                       const int64_t* n_sections, int64_t n_floors, const surge_section_floor* floors) {
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (!d) return refuse_null_decoder();
   if (n_parts < 0 || (n_parts > 0 && (!bytes || !sections || !n_sections)) || n_floors < 0 || (n_floors > 0 && !floors)) return dfail(d, E_INVALID, "bad argument");
   DeviceScope scope(d->device);
   return enqueue_push(d, [&](PushSlot& s) { return stage1_wire(d, s, n_parts, bytes, sections, n_sections, n_floors, floors); });
@@ -325,13 +325,13 @@ int32_t surge_device_decoder_push_async(surge_device_decoder* d, const uint8_t* 
 }
 
 int32_t surge_device_decoder_push_finish(surge_device_decoder* d) {
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (!d) return refuse_null_decoder();
   DeviceScope scope(d->device);
   return finish_oldest(d, true);
 }
 
 int32_t surge_device_decoder_push_finish_async(surge_device_decoder* d) {
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (!d) return refuse_null_decoder();
   DeviceScope scope(d->device);
   return finish_oldest(d, false);
 }
@@ -343,9 +343,9 @@ int32_t surge_device_decoder_pending(const surge_device_decoder* d) {
 }
 
 int32_t surge_device_decoder_reserve(surge_device_decoder* d, int64_t n_keys, int64_t key_bytes) {
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (!d) return refuse_null_decoder();
   if (n_keys < 0 || key_bytes < 0) return dfail(d, E_INVALID, "negative capacity");
-  if (d->n_pending != 0) return dfail(d, SURGE_E_STATE, "asynchronous pushes are pending");
+  if (d->n_pending != 0) return refuse_pending(d);
   DeviceScope scope(d->device);
   hipStream_t st = d->stream;
   const int64_t extra = n_keys > d->n_keys ? n_keys - d->n_keys : 0;
@@ -362,9 +362,9 @@ int32_t surge_device_decoder_reserve(surge_device_decoder* d, int64_t n_keys, in
 
 int32_t surge_device_decoder_push_floored(surge_device_decoder* d, const uint8_t* bytes, const surge_batch_section* sections, int64_t n_sections, int64_t n_floors,
                                           const surge_section_floor* floors) {
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (!d) return refuse_null_decoder();
   if (n_sections < 0 || (n_sections > 0 && (!bytes || !sections))) return dfail(d, E_INVALID, "bad argument");
-  if (d->n_pending != 0) return dfail(d, SURGE_E_STATE, "asynchronous pushes are pending: finish them first (results are appended in push order)");
+  if (d->n_pending != 0) return refuse_pending(d, kPushOrder);
   if (n_sections == 0) return OK;
   const int32_t rc = surge_device_decoder_push_parts_floored_async(d, 1, &bytes, &sections, &n_sections, n_floors, floors);
   return rc != OK ? rc : surge_device_decoder_push_finish(d);
@@ -377,11 +377,11 @@ int32_t surge_device_decoder_push(surge_device_decoder* d, const uint8_t* bytes,
 // A state decoder that has loaded its topic goes on as the events decoder of the same aggregates: the key table stays where it
 // is — its ids are the resident state's rows — and only what names the mode changes.
 int32_t surge_device_decoder_continue_as_events(surge_device_decoder* d, const surge_event_json_template* tmpl) {
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (!d) return refuse_null_decoder();
   if (!d->states) return dfail(d, SURGE_E_STATE, "not a state decoder (surge_device_decoder_create_states): an events decoder is one already, and the switch is one-way");
-  if (d->n_pending != 0) return dfail(d, SURGE_E_STATE, "asynchronous pushes are pending: finish and load them first");
+  if (d->n_pending != 0) return refuse_pending(d, kFinishAndLoad);
   if (d->n_records != 0) return dfail(d, SURGE_E_STATE, "delivered state records are waiting: load them (surge_device_decoder_load_states) or clear them first");
-  if (d->poisoned) return dfail(d, SURGE_E_STATE, "an earlier push failed on the device half way: destroy this decoder and create a new one");
+  if (d->poisoned) return refuse_poisoned(d);
   if (tmpl && surge_event_json_validate(tmpl) != 0) return dfail(d, E_INVALID, std::string("event template: ") + surge_event_json_last_error());
   DeviceScope scope(d->device);
   DCHK(d, hipStreamSynchronize(d->stream));  // (the last load read the value buffers on the handle's stream behind an event of this one; it has returned)
@@ -400,9 +400,9 @@ int32_t surge_device_decoder_continue_as_events(surge_device_decoder* d, const s
 
 int32_t surge_device_decoder_push_records(surge_device_decoder* d, const uint8_t* keys, const int64_t* key_off, const uint8_t* values,
                                           const int64_t* value_off, const int64_t* offsets, int64_t n) {
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (!d) return refuse_null_decoder();
   if (n < 0 || (n > 0 && (!key_off || !value_off))) return dfail(d, E_INVALID, "bad argument");
-  if (d->n_pending != 0) return dfail(d, SURGE_E_STATE, "asynchronous pushes are pending: finish them first (results are appended in push order)");
+  if (d->n_pending != 0) return refuse_pending(d, kPushOrder);
   if (n == 0) return OK;
   DeviceScope scope(d->device);
   const int32_t rc = enqueue_push(d, [&](PushSlot& s) { return stage1_records(d, s, keys, key_off, values, value_off, offsets, n); });
@@ -411,7 +411,7 @@ int32_t surge_device_decoder_push_records(surge_device_decoder* d, const uint8_t
 
 int32_t surge_device_decoder_result(surge_device_decoder* d, int64_t* n_records, const int64_t** d_agg_idx, const void** d_events16,
                                     const int64_t** d_offsets, int64_t* n_keys) {
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (!d) return refuse_null_decoder();
   if (d->states) return dfail(d, SURGE_E_STATE, "a state decoder has no events: see surge_device_decoder_state_result");
   if (n_records) *n_records = d->n_records;
   if (d_agg_idx) *d_agg_idx = (const int64_t*)d->r_agg.p;
@@ -423,7 +423,7 @@ int32_t surge_device_decoder_result(surge_device_decoder* d, int64_t* n_records,
 
 int32_t surge_device_decoder_state_result(surge_device_decoder* d, int64_t* n_records, const int64_t** d_agg_idx, const uint8_t** d_values,
                                           const int64_t** d_value_off, const int64_t** d_offsets, int64_t* n_keys) {
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (!d) return refuse_null_decoder();
   if (!d->states) return dfail(d, SURGE_E_STATE, "not a state decoder (surge_device_decoder_create_states): see surge_device_decoder_result");
   if (n_records) *n_records = d->n_records;
   if (d_agg_idx) *d_agg_idx = (const int64_t*)d->r_agg.p;
@@ -435,217 +435,10 @@ int32_t surge_device_decoder_state_result(surge_device_decoder* d, int64_t* n_re
 }
 
 int32_t surge_device_decoder_clear(surge_device_decoder* d) {
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
+  if (!d) return refuse_null_decoder();
   d->n_records = 0;
   d->val_bytes = 0;
-  d->ev_pend_n = 0;  // (kept event strings: what is pending and not merged goes with the records)
-  d->ev_pend_bytes = 0;
-  return OK;
-}
-
-int32_t surge_device_decoder_keys(surge_device_decoder* d, uint8_t* utf8_out, int64_t utf8_capacity, int64_t* key_off_out, int64_t* n_keys_out,
-                                  int64_t* utf8_bytes_out) {
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
-  if (n_keys_out) *n_keys_out = d->n_keys;
-  if (utf8_bytes_out) *utf8_bytes_out = d->arena_bytes;
-  if (!utf8_out && !key_off_out) return OK;  // size query
-  if (utf8_capacity < d->arena_bytes) return dfail(d, E_INVALID, "utf8_out is too small (see *utf8_bytes_out)");
-  DeviceScope scope(d->device);
-  DCHK(d, hipStreamSynchronize(d->stream));
-  if (utf8_out && d->arena_bytes > 0) DCHK(d, hipMemcpy(utf8_out, d->arena.p, (size_t)d->arena_bytes, hipMemcpyDeviceToHost));
-  if (key_off_out) DCHK(d, hipMemcpy(key_off_out, d->key_off.p, (size_t)(d->n_keys + 1) * 8, hipMemcpyDeviceToHost));
-  return OK;
-}
-
-int32_t surge_device_decoder_key_table(surge_device_decoder* d, const uint8_t** d_utf8, const int64_t** d_key_off) {
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
-  if (d_utf8) *d_utf8 = (const uint8_t*)d->arena.p;
-  if (d_key_off) *d_key_off = (const int64_t*)d->key_off.p;
-  return OK;
-}
-
-int32_t surge_device_decoder_lookup_device(surge_device_decoder* d, const uint8_t* d_ids_utf8, const int64_t* d_id_off, int64_t n, int64_t* d_idx_out) {
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
-  if (n < 0 || (n > 0 && (!d_ids_utf8 || !d_id_off || !d_idx_out))) return dfail(d, E_INVALID, "bad argument");
-  // (a slot the push in flight inserted has no id yet, and its stage 2 may move the table or its hash function)
-  if (d->n_pending != 0) return dfail(d, SURGE_E_STATE, "asynchronous pushes are pending: finish them first (their keys have no ids yet)");
-  if (d->poisoned) return dfail(d, SURGE_E_STATE, "an earlier push failed on the device half way: destroy this decoder and create a new one");
-  if (n == 0) return OK;
-  DeviceScope scope(d->device);
-  DCHK(d, launch_lookup(d_ids_utf8, d_id_off, n, keys_of(d), d->seed, d_idx_out, d->stream));
-  return OK;
-}
-
-int32_t surge_device_decoder_lookup(surge_device_decoder* d, const uint8_t* ids_utf8, const int64_t* id_off, int64_t n, int64_t* idx_out) {
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
-  if (n < 0 || (n > 0 && (!ids_utf8 || !id_off || !idx_out))) return dfail(d, E_INVALID, "bad argument");
-  if (d->n_pending != 0) return dfail(d, SURGE_E_STATE, "asynchronous pushes are pending: finish them first (their keys have no ids yet)");
-  if (n == 0) return OK;
-  const int64_t first = id_off[0];
-  if (first < 0) return dfail(d, E_INVALID, "id_off[0] is negative");
-  std::vector<int64_t> off;
-  try { off.resize((size_t)n + 1); } catch (const std::bad_alloc&) { return dfail(d, E_NOMEM, "out of host memory"); }
-  for (int64_t i = 0; i <= n; ++i) {  // (the staged bytes begin at the first id)
-    if (i > 0 && (id_off[i] < id_off[i - 1] || id_off[i] - id_off[i - 1] >= (1ll << 31))) return dfail(d, E_INVALID, "id_off must not decrease, and an id is shorter than 2^31 bytes");
-    off[(size_t)i] = id_off[i] - first;
-  }
-  const size_t bytes = (size_t)off[(size_t)n];
-  DeviceScope scope(d->device);
-  hipStream_t st = d->stream;
-  DCHK(d, d->lk_ids.reserve(bytes + 16, false, st));  // (the 16 bytes of slack keys_equal's loads may touch)
-  DCHK(d, d->lk_off.reserve((size_t)(n + 1) * 8, false, st));
-  DCHK(d, d->lk_idx.reserve((size_t)n * 8, false, st));
-  if (bytes) DCHK(d, hipMemcpyAsync(d->lk_ids.p, ids_utf8 + first, bytes, hipMemcpyHostToDevice, st));
-  DCHK(d, hipMemcpyAsync(d->lk_off.p, off.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, st));
-  const int32_t rc = surge_device_decoder_lookup_device(d, (const uint8_t*)d->lk_ids.p, (const int64_t*)d->lk_off.p, n, (int64_t*)d->lk_idx.p);
-  if (rc == OK) DCHK(d, hipMemcpyAsync(idx_out, d->lk_idx.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
-  DCHK(d, hipStreamSynchronize(st));  // (off is this call's)
-  return rc;
-}
-
-// ---- reads in key order (ingest_order.hip) -------------------------------------------------------------------------------------
-namespace {
-
-int32_t readable(surge_device_decoder* d) {
-  if (d->n_pending != 0) return dfail(d, SURGE_E_STATE, "asynchronous pushes are pending: finish them first (their keys have no ids yet)");
-  if (d->poisoned) return dfail(d, SURGE_E_STATE, "an earlier push failed on the device half way: destroy this decoder and create a new one");
-  return OK;
-}
-
-// d->ord = the dense indices in key order, built when the table has grown since the last build.  Most significant chunk first:
-// a pass sorts every key by (its group, its next four bytes, how many it has left), then the groups are re-numbered; the loop
-// ends when every group is one key.  (Unique keys: a group of several holds only keys that go on, so that is after at most
-// ceil(max_len / 4) + 1 passes; a pass in which no key had a byte left ends it whatever the table holds.)  Eight bytes come
-// back per pass.  The scratch — 28 bytes per key and rocPRIM's — goes when the build is over; ord stays, 8 bytes per key.
-int32_t ensure_order(surge_device_decoder* d) {
-  const int64_t n = d->n_keys;
-  if (d->ord_keys == n) return OK;
-  if (n > kOrderMaxKeys) return dfail(d, E_UNSUPPORTED, "more than 2^29 aggregate ids: the key order sorts 29 bits of group");
-  hipStream_t st = d->stream;
-  d->ord_keys = -1;
-  int64_t passes = 0;
-  if (n > 0) {
-    DCHK(d, d->ord.reserve((size_t)n * 8, false, st));
-    Buf key_a, key_b, idx_a, idx_b, grp, flag, live, temp;
-    OrderScratch sc{};
-    DCHK(d, order_temp_bytes(n, &sc.temp_bytes, st));
-    DCHK(d, key_a.reserve((size_t)n * 8, false, st));
-    DCHK(d, key_b.reserve((size_t)n * 8, false, st));
-    for (Buf* b : {&idx_a, &idx_b, &grp, &flag}) DCHK(d, b->reserve((size_t)n * 4, false, st));
-    DCHK(d, live.reserve(4, false, st));
-    DCHK(d, temp.reserve(sc.temp_bytes ? sc.temp_bytes : 1, false, st));
-    sc.key_in = (unsigned long long*)key_a.p;
-    sc.key_out = (unsigned long long*)key_b.p;
-    sc.idx_in = (uint32_t*)idx_a.p;
-    sc.idx_out = (uint32_t*)idx_b.p;
-    sc.grp = (uint32_t*)grp.p;
-    sc.flag = (uint32_t*)flag.p;
-    sc.live = (uint32_t*)live.p;
-    sc.temp = temp.p;
-    DCHK(d, launch_order_init(sc, n, st));
-    int64_t groups = 1;
-    while (groups < n) {
-      int group_bits = 0;
-      while ((1ll << group_bits) < groups) ++group_bits;
-      DCHK(d, launch_order_pass(keys_of(d), passes, group_bits, sc, st));
-      ++passes;
-      uint32_t last_group = 0, had_bytes = 0;
-      DCHK(d, hipMemcpyAsync(&last_group, sc.grp + (n - 1), 4, hipMemcpyDeviceToHost, st));
-      DCHK(d, hipMemcpyAsync(&had_bytes, sc.live, 4, hipMemcpyDeviceToHost, st));
-      DCHK(d, hipStreamSynchronize(st));
-      groups = (int64_t)last_group + 1;
-      if (!had_bytes) break;
-    }
-    DCHK(d, launch_order_finish(sc, n, (int64_t*)d->ord.p, st));
-    DCHK(d, hipStreamSynchronize(st));  // (the scratch is freed on the way out)
-    if (groups < n) return dfail(d, SURGE_E_CORRUPT, "the key table holds the same id twice");
-  }
-  d->ord_keys = n;
-  d->ord_passes = passes;
-  return OK;
-}
-
-}  // namespace
-
-int32_t surge_device_decoder_key_order(surge_device_decoder* d, const int64_t** d_order, int64_t* n_keys_out, int64_t* passes_out) {
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
-  int32_t rc = readable(d);
-  if (rc != OK) return rc;
-  DeviceScope scope(d->device);
-  if ((rc = ensure_order(d)) != OK) return rc;
-  if (d_order) *d_order = d->n_keys ? (const int64_t*)d->ord.p : nullptr;
-  if (n_keys_out) *n_keys_out = d->n_keys;
-  if (passes_out) *passes_out = d->ord_passes;
-  return OK;
-}
-
-int32_t surge_device_decoder_range_device(surge_device_decoder* d, const uint8_t* from_utf8, int64_t from_len, const uint8_t* to_utf8, int64_t to_len,
-                                          int64_t* d_rows_out, int64_t capacity, int64_t* n_out) {
-  // (what the numbers alone decide comes first: it is refused the same with and without a decoder)
-  if (from_len < 0 || to_len < 0 || capacity < 0) return dfail(d, E_INVALID, "a negative length or capacity");
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
-  if (!n_out) return dfail(d, E_INVALID, "bad argument");
-  if (from_len >= (1ll << 31) || to_len >= (1ll << 31)) return dfail(d, E_INVALID, "a bound is shorter than 2^31 bytes");
-  int32_t rc = readable(d);
-  if (rc != OK) return rc;
-  *n_out = 0;
-  if (d->n_keys == 0) return OK;
-  DeviceScope scope(d->device);
-  if ((rc = ensure_order(d)) != OK) return rc;
-  hipStream_t st = d->stream;
-  // the two bounds, each with the 16 bytes behind it that the compare's loads may touch; a NULL bound has the length -1
-  const int64_t fl = from_utf8 ? from_len : -1, tl = to_utf8 ? to_len : -1;
-  const int64_t to_at = ((fl > 0 ? fl : 0) + 15) / 16 * 16 + 16;
-  DCHK(d, d->rd_bounds.reserve((size_t)(to_at + (tl > 0 ? tl : 0) + 16), false, st));
-  DCHK(d, d->rd_lo_hi.reserve(16, false, st));
-  if (fl > 0) DCHK(d, hipMemcpyAsync(d->rd_bounds.p, from_utf8, (size_t)fl, hipMemcpyHostToDevice, st));
-  if (tl > 0) DCHK(d, hipMemcpyAsync((uint8_t*)d->rd_bounds.p + to_at, to_utf8, (size_t)tl, hipMemcpyHostToDevice, st));
-  DCHK(d, launch_order_bounds(keys_of(d), (const int64_t*)d->ord.p, (const uint8_t*)d->rd_bounds.p, fl, to_at, tl, (int64_t*)d->rd_lo_hi.p, st));
-  int64_t lo_hi[2] = {0, 0};
-  DCHK(d, hipMemcpyAsync(lo_hi, d->rd_lo_hi.p, 16, hipMemcpyDeviceToHost, st));
-  DCHK(d, hipStreamSynchronize(st));
-  if (lo_hi[0] < 0 || lo_hi[1] > d->n_keys) return dfail(d, E_DEVICE, "the bound search left the key order");
-  const int64_t n = lo_hi[1] > lo_hi[0] ? lo_hi[1] - lo_hi[0] : 0;  // (from > to: nothing)
-  *n_out = n;
-  if (n > capacity) return dfail(d, SURGE_E_RANGE, "d_rows_out is too small (see *n_out)");
-  if (n == 0) return OK;
-  if (!d_rows_out) return dfail(d, E_INVALID, "d_rows_out is NULL");
-  DCHK(d, hipMemcpyAsync(d_rows_out, (const int64_t*)d->ord.p + lo_hi[0], (size_t)n * 8, hipMemcpyDeviceToDevice, st));
-  DCHK(d, hipStreamSynchronize(st));
-  return OK;
-}
-
-int32_t surge_device_decoder_gather_keys_device(surge_device_decoder* d, const int64_t* d_rows, int64_t n, uint8_t* d_utf8_out, int64_t utf8_capacity,
-                                                int64_t* d_off_out, int64_t* total_bytes_out) {
-  if (n < 0 || utf8_capacity < 0) return dfail(d, E_INVALID, "a negative length or capacity");
-  if (!d) return dfail(nullptr, E_INVALID, "decoder is NULL");
-  if (!d_off_out || (n > 0 && !d_rows)) return dfail(d, E_INVALID, "bad argument");
-  const int32_t rc = readable(d);
-  if (rc != OK) return rc;
-  DeviceScope scope(d->device);
-  hipStream_t st = d->stream;
-  KeyGatherScratch sc{};
-  DCHK(d, key_gather_temp_bytes(n, &sc.temp_bytes, st));
-  DCHK(d, d->gk_len.reserve((size_t)(n + 1) * 8, false, st));
-  DCHK(d, d->gk_at.reserve((size_t)(n + 1) * 8, false, st));
-  DCHK(d, d->gk_bad.reserve(4, false, st));
-  DCHK(d, d->gk_temp.reserve(sc.temp_bytes ? sc.temp_bytes : 1, false, st));
-  sc.len = (unsigned long long*)d->gk_len.p;
-  sc.at = (unsigned long long*)d->gk_at.p;
-  sc.bad = (uint32_t*)d->gk_bad.p;
-  sc.temp = d->gk_temp.p;
-  DCHK(d, launch_key_lengths(keys_of(d), d_rows, n, sc, st));
-  unsigned long long total = 0;
-  uint32_t bad = 0;
-  DCHK(d, hipMemcpyAsync(&total, sc.at + n, 8, hipMemcpyDeviceToHost, st));
-  DCHK(d, hipMemcpyAsync(&bad, sc.bad, 4, hipMemcpyDeviceToHost, st));
-  DCHK(d, hipStreamSynchronize(st));
-  if (bad) return dfail(d, E_INVALID, "a row is outside [0, n_keys)");
-  if (total_bytes_out) *total_bytes_out = (int64_t)total;
-  if ((int64_t)total > utf8_capacity) return dfail(d, SURGE_E_RANGE, "d_utf8_out is too small (see *total_bytes_out)");
-  if (total > 0 && !d_utf8_out) return dfail(d, E_INVALID, "d_utf8_out is NULL");
-  DCHK(d, launch_key_gather(keys_of(d), d_rows, n, sc, d_utf8_out, d_off_out, st));
-  DCHK(d, hipStreamSynchronize(st));
+  d->strings.ev.drop_pending();  // (ingest_columns.hip: what was kept and not merged goes with the records)
   return OK;
 }
 

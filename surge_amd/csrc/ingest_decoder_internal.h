@@ -1,7 +1,9 @@
 // ingest_decoder_internal.h — what the units of the device decoder's host object share (ingest_decoder.hip: lifecycle,
-// slot queue, plain exports; ingest_stage1.hip; ingest_stage2.hip; ingest_handover.hip): the object itself, device memory,
-// error reporting and the few helpers that cross units.  Host only and internal, like engine_internal.h: not part of the
-// C ABI (that is include/surge_ingest.h).  The kernels and what launches them know none of this (ingest_device.h).
+// slot queue, the push exports; ingest_stage1.hip; ingest_stage2.hip; ingest_reads.hip: the key table's reads between pushes;
+// ingest_columns.hip: the kept string columns; ingest_handover.hip: the hand-overs to a replay handle): the object itself —
+// every feature's state in a member struct that names the unit it belongs to — device memory, error reporting, the refusals
+// every export words alike and the few helpers that cross units.  Host only and internal, like engine_internal.h: not part
+// of the C ABI (that is include/surge_ingest.h).  The kernels and what launches them know none of this (ingest_device.h).
 #pragma once
 
 #include <sys/prctl.h>
@@ -87,6 +89,76 @@ struct PushSlot {
 };
 constexpr int kSlots = 5;
 
+// ---- ingest_reads.hip: what the reads of the key table between pushes keep ---------------------------------------------------
+struct ReadsState {
+  struct Lookup { Buf ids, off, idx; } lookup;  // surge_device_decoder_lookup: the staged queries and their indices
+  // the key order (ingest_order.hip): valid while keys == n_keys — a push that interns an id leaves it stale, the next read
+  // rebuilds it whole; clear and a re-seed do not touch the keys' bytes, so they do not touch it
+  struct Order {
+    Buf idx;  // n_keys dense indices in key order
+    int64_t keys = -1, passes = 0;
+  } order;
+  struct Range { Buf bounds, lo_hi; } range;      // surge_device_decoder_range_device: the staged bounds and their two positions
+  struct Gather { Buf len, at, bad, temp; } gather;  // surge_device_decoder_gather_keys_device: lengths, their scan, the bad-row word
+};
+
+// ---- ingest_columns.hip: the kept string columns, a state decoder's (surge_device_decoder_keep_strings) and an events ---------
+// decoder's (surge_device_decoder_keep_event_strings) alike
+// One STR column: two buffers of bytes and of offsets, of which `cur` holds the column (-1: nothing has named it).  The rule
+// of a merge, written once: it reads buffer cur and writes the OTHER one, which has n_keys + 1 offsets and room for the bytes
+// of the column so far plus those that come in (an unescaped string is never longer than its span, and the spans lie inside
+// the incoming values: the merge always fits) and 16 of slack; then the column flips to what was written.
+struct StrColumn {
+  Buf utf8[2], off[2];
+  int cur = -1;
+  int64_t n = 0, bytes = 0;
+  int next() const { return cur < 0 ? 0 : 1 - cur; }
+  int64_t next_capacity(int64_t incoming) const { return bytes + incoming + 16; }
+  hipError_t reserve_next(int64_t n_keys, int64_t incoming, hipStream_t st) {
+    const hipError_t e = off[next()].reserve((size_t)(n_keys + 1) * 8, false, st);
+    return e != hipSuccess ? e : utf8[next()].reserve((size_t)next_capacity(incoming), false, st);
+  }
+  void flip(int64_t n_keys, int64_t total) {
+    cur = next();
+    n = n_keys;
+    bytes = total;
+  }
+  const uint8_t* cur_utf8() const { return cur < 0 ? nullptr : (const uint8_t*)utf8[cur].p; }
+  const int64_t* cur_off() const { return cur < 0 ? nullptr : (const int64_t*)off[cur].p; }
+  int64_t cur_n() const { return cur < 0 ? 0 : n; }
+};
+
+// Events mode (ingest_strings.hip has the kernels; stage 2 selects, validates and gathers, ingest_columns.hip arms and merges):
+// the rule on the device, the event types that select a record and the columns the rule names; a push's select / list / spans
+// scratch; the selected records of the pushes since the last merge (values, n + 1 offsets, rows, spans, a status array per
+// column), merged into the columns when they are asked for or more than `bound` records are pending; the merge's scratch
+struct EventStringsState {
+  bool armed = false;
+  EvsTypes types{};
+  bool named[SURGE_JSON_STRING_COLUMNS] = {};
+  Buf rule;
+  struct Select { Buf seg, count, base, cell, sel, lens, totals; } select;
+  struct Pending {
+    Buf val, off, rows, spans, status[SURGE_JSON_STRING_COLUMNS];
+    int64_t n = 0, bytes = 0, bound = 1 << 20;
+  } pend;
+  struct Merge {
+    Buf win, bad, totals;
+    int64_t count = 0;  // merges that had records pending
+  } merge;
+  void drop_pending() { pend.n = pend.bytes = 0; }  // (what is pending and not merged goes with the records: clear)
+  StringsPending pending() const {
+    StringsPending p{(uint8_t*)pend.val.p, (int64_t*)pend.off.p, (int64_t*)pend.rows.p, (int64_t*)pend.spans.p, {}, pend.n, pend.bytes};
+    for (int c = 0; c < SURGE_JSON_STRING_COLUMNS; ++c) p.status[c] = (uint8_t*)pend.status[c].p;
+    return p;
+  }
+};
+
+struct StringsState {
+  StrColumn col[SURGE_JSON_STRING_COLUMNS];
+  EventStringsState ev;
+};
+
 }  // namespace host
 }  // namespace ingest
 }  // namespace surge
@@ -100,6 +172,9 @@ struct surge_device_decoder {
   bool json = false;
   bool states = false;  // state mode (surge_device_decoder_create_states): values are kept (r_val / r_val_off), not decoded into events
   bool continued = false;  // was a state decoder (surge_device_decoder_continue_as_events): its key table and kept string columns are that decoder's
+  // state mode, set by ingest_columns.hip (surge_device_decoder_keep_strings) and read by ingest_handover.hip's loads: every load
+  // asks the decode for the string spans (st_spans) and has ingest_columns.hip merge the STR columns its template names into strings.col
+  bool keep_strings = false;
   // Two host threads may drive one decoder: one enqueues stage 1 (push_async / push_parts_async), the other finishes pushes
   // (push_finish*, result, clear, append_decoded*).  `mu` covers what both touch: the slot queue and the error text.
   std::mutex mu;
@@ -123,15 +198,10 @@ struct surge_device_decoder {
   std::atomic<int> n_pending{0};  // slots [head, head + n_pending) hold pushes whose stage 1 is enqueued (changes under `mu`)
   // stage 2 scratch
   Buf first, first_scan, keep, keep_pos, temp;
-  Buf vlen, vscan, val_src, long_runs, st_status;  // state mode: the value scan and gather's scratch; load_states' per-record statuses
+  Buf vlen, vscan, val_src, long_runs;  // state mode: the value scan and gather's scratch
+  Buf st_status, st_spans;              // ... load_states' per-record statuses and, with keep_strings, the decode's string spans
   // hash table + key table
   Buf t_slots, arena, key_off, key_hash;
-  Buf lk_ids, lk_off, lk_idx;  // surge_device_decoder_lookup: the staged queries and their indices
-  // the key order (ingest_order.hip): valid while ord_keys == n_keys — a push that interns an id leaves it stale, the next read
-  // rebuilds it whole; clear and a re-seed do not touch the keys' bytes, so they do not touch it
-  Buf ord, rd_bounds, rd_lo_hi;  // n_keys dense indices in key order; a range's staged bounds and its two positions
-  Buf gk_len, gk_at, gk_bad, gk_temp;  // surge_device_decoder_gather_keys_device: lengths, their scan, the bad-row word
-  int64_t ord_keys = -1, ord_passes = 0;
   uint64_t t_cap = 0;
   std::atomic<uint64_t> seed{0};  // (stage 1 reads it once per push; stage 2 of an earlier push may move it on: PushSlot::seed)
   int64_t n_keys = 0, arena_bytes = 0;
@@ -140,30 +210,10 @@ struct surge_device_decoder {
   Buf r_val, r_val_off;   // state mode: the delivered records' value bytes, one after the other, and n_records + 1 offsets into them
   int64_t val_bytes = 0;  // ... bytes of r_val in use
   int64_t n_records = 0;
-  // state mode, surge_device_decoder_keep_strings: the STR columns of the loaded states (surge_replay_merge_state_strings
-  // writes buffer 1 - cur from buffer cur), and the decode's spans
-  struct StrColumn {
-    Buf utf8[2], off[2];
-    int cur = -1;  // -1: no load has named the column
-    int64_t n = 0, bytes = 0;
-  };
-  StrColumn str_cols[SURGE_JSON_STRING_COLUMNS];
-  Buf st_spans;
-  bool keep_strings = false;
-  int64_t state_loads = 0;
-  // events mode, surge_device_decoder_keep_event_strings (ingest_strings.hip): the rule on the device, the event types that
-  // select a record and the columns the rule names; a push's select / list / spans scratch; the selected records of the pushes
-  // since the last merge (values, n + 1 offsets, rows, spans, a status array per column), merged into str_cols when the
-  // columns are asked for or more than ev_pend_bound records are pending; the merge's scratch
-  bool ev_strings = false;
-  surge::ingest::EvsTypes ev_types{};
-  bool ev_named[SURGE_JSON_STRING_COLUMNS] = {};
-  Buf d_evs_rule;
-  Buf es_seg, es_count, es_base, es_cell, es_sel, es_lens, es_totals;
-  Buf ev_pend_val, ev_pend_off, ev_pend_rows, ev_pend_spans, ev_pend_status[SURGE_JSON_STRING_COLUMNS];
-  int64_t ev_pend_n = 0, ev_pend_bytes = 0, ev_pend_bound = 1 << 20, ev_merges = 0;
-  Buf es_win, es_bad, es_merge_totals;
-  uint64_t events_from_push = 0;  // push_seq when the decoder became an events decoder: arming comes before the push behind it
+  int64_t state_loads = 0;  // state mode: loads so far (counted by ingest_handover.hip; ingest_columns.hip refuses keep_strings behind the first)
+  uint64_t events_from_push = 0;  // push_seq when the decoder became an events decoder: arming kept event strings comes before the push behind it
+  surge::ingest::host::ReadsState reads;      // ingest_reads.hip
+  surge::ingest::host::StringsState strings;  // ingest_columns.hip (stage 2 fills strings.ev.pend; a state decoder's loads merge into strings.col)
   // hand-over of the result arrays to a consumer on another stream (surge_replay_append_decoded_async): `consumed` is
   // recorded on the consumer's stream behind its last read, the next stage 2 waits for it before it writes the arrays
   hipEvent_t ready = nullptr, consumed = nullptr;
@@ -191,6 +241,19 @@ inline int32_t dfail(surge_device_decoder* d, int32_t code, const std::string& m
   }
   g_dec_err = m;
   return code;
+}
+
+// The refusals most exports share, each worded in one place.  What is pending is refused with one of four endings: none
+// (reserve), and the three below.
+inline int32_t refuse_null_decoder() { return dfail(nullptr, E_INVALID, "decoder is NULL"); }
+inline int32_t refuse_poisoned(surge_device_decoder* d) {
+  return dfail(d, SURGE_E_STATE, "an earlier push failed on the device half way: destroy this decoder and create a new one");
+}
+constexpr const char* kPushOrder = ": finish them first (results are appended in push order)";
+constexpr const char* kNoIdsYet = ": finish them first (their keys have no ids yet)";
+constexpr const char* kFinishAndLoad = ": finish and load them first";
+inline int32_t refuse_pending(surge_device_decoder* d, const char* ending = "") {
+  return dfail(d, SURGE_E_STATE, std::string("asynchronous pushes are pending") + ending);
 }
 
 #define DCHK(d, call)                                                                                   \
@@ -258,13 +321,10 @@ int32_t stage1_records(surge_device_decoder* d, PushSlot& s, const uint8_t* keys
                        const int64_t* offsets, int64_t n);
 // ---- ingest_stage2.hip: interning, compaction, append on the decoder's stream; wait = false leaves the closing wait out -----
 int32_t stage2(surge_device_decoder* d, PushSlot& s, bool wait);
-// ---- ingest_handover.hip: what is pending of the kept event strings merged into str_cols, every column brought to n_keys ------
-inline surge::ingest::StringsPending strings_pending_of(surge_device_decoder* d) {
-  surge::ingest::StringsPending p{(uint8_t*)d->ev_pend_val.p, (int64_t*)d->ev_pend_off.p, (int64_t*)d->ev_pend_rows.p, (int64_t*)d->ev_pend_spans.p, {}, d->ev_pend_n, d->ev_pend_bytes};
-  for (int c = 0; c < SURGE_JSON_STRING_COLUMNS; ++c) p.status[c] = (uint8_t*)d->ev_pend_status[c].p;
-  return p;
-}
+// ---- ingest_columns.hip: what is pending of the kept event strings merged into the columns, every column brought to n_keys;
+// and a state load's strings (the decode's spans in st_spans) merged into the columns its template names
 int32_t merge_event_strings(surge_device_decoder* d);
+int32_t merge_state_strings(surge_device_decoder* d, surge_replay_handle* h, const surge_json_template* tmpl);
 
 }  // namespace host
 }  // namespace ingest

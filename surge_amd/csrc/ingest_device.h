@@ -1,8 +1,9 @@
 // ingest_device.h — what the translation units of the device decoder share.  Internal, like replay_internal.h: not part of
 // the C ABI.  Each stage is a unit of its own that knows the plain structs below and nothing of the decoder around it
-// (the host object: ingest_decoder.hip and its units ingest_stage1.hip, ingest_stage2.hip, ingest_handover.hip, which share
-// ingest_decoder_internal.h): ingest_crc.hip, ingest_lz4.hip, ingest_records.hip, ingest_intern.hip, ingest_order.hip.  Their launch_* functions
-// enqueue on the stream they are given and return what the runtime said; none of them waits for the device.
+// (the host object: ingest_decoder.hip and its units ingest_stage1.hip, ingest_stage2.hip, ingest_reads.hip, ingest_columns.hip,
+// ingest_handover.hip, which share ingest_decoder_internal.h): ingest_crc.hip, ingest_lz4.hip, ingest_records.hip, ingest_intern.hip,
+// ingest_order.hip, ingest_strings.hip.  Their launch_* functions enqueue on the stream they are given and return what the runtime
+// said; none of them waits for the device.
 #pragma once
 
 #include <hip/hip_runtime.h>

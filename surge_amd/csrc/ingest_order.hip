@@ -9,7 +9,7 @@
 //              (rocPRIM) inclusive scan of the flags
 //   bounds     two threads: lower_bound(from) and upper_bound(to) over the order, bytes compared with the arena
 //   gather     the ids of a row list, back to back: lengths (a row outside the table raises a flag), a scan, the copy
-// The pass loop — most significant chunk first, until every group is one key — is the host object's (ingest_decoder.hip): this
+// The pass loop — most significant chunk first, until every group is one key — is the host object's (ingest_reads.hip): this
 // unit launches what it is told to and waits for nothing.  Keys are unique, so a group of several keys holds only keys that go
 // on behind the bytes compared so far: the loop ends after at most ceil(max_len / 4) + 1 passes.  Keys that are alone in their
 // group stay in the later passes (they sort by their group alone): see DESIGN §7.

@@ -59,6 +59,7 @@ bool malformed_record_offset(const PushSlot& s, int64_t rec, int64_t* offset) {
 struct Stage2 {
   surge_device_decoder* const d;
   PushSlot& s;
+  EventStringsState& ev;  // kept event strings (ingest_columns.hip arms and merges them)
   const int64_t n_rec;
   const hipStream_t st;  // the decoder's
   const size_t R;
@@ -77,7 +78,7 @@ struct Stage2 {
   int64_t n_sel = 0, sel_bytes = 0;
 
   Stage2(surge_device_decoder* d_, PushSlot& s_)
-      : d(d_), s(s_), n_rec(s_.n_rec), st(d_->stream), R((size_t)s_.n_rec), dby((const uint8_t*)s_.d_bytes.p), derr((ErrorCell*)s_.d_err.p), dmeta((RecMeta*)s_.meta.p) {}
+      : d(d_), s(s_), ev(d_->strings.ev), n_rec(s_.n_rec), st(d_->stream), R((size_t)s_.n_rec), dby((const uint8_t*)s_.d_bytes.p), derr((ErrorCell*)s_.d_err.p), dmeta((RecMeta*)s_.meta.p) {}
 
   // scratch (nothing of the push is in the table yet: an allocation failure here needs no rollback)
   int32_t reserve_scratch() {
@@ -92,12 +93,12 @@ struct Stage2 {
       DCHK(d, d->vlen.reserve((R + 1) * 8, false, st));
       DCHK(d, d->vscan.reserve((R + 1) * 8, false, st));
     }
-    if (d->ev_strings) {
+    if (ev.armed) {
       const size_t n_blocks = (R + kStringsBlock - 1) / kStringsBlock;
-      DCHK(d, d->es_seg.reserve(n_blocks * kStringsBlock * 4, false, st));
-      DCHK(d, d->es_count.reserve(n_blocks * 4, false, st));
-      DCHK(d, d->es_base.reserve(n_blocks * 4, false, st));
-      DCHK(d, d->es_cell.reserve(sizeof(StringsCell), false, st));
+      DCHK(d, ev.select.seg.reserve(n_blocks * kStringsBlock * 4, false, st));
+      DCHK(d, ev.select.count.reserve(n_blocks * 4, false, st));
+      DCHK(d, ev.select.base.reserve(n_blocks * 4, false, st));
+      DCHK(d, ev.select.cell.reserve(sizeof(StringsCell), false, st));
     }
     const int32_t rc = ensure_table(d, n_rec);
     if (rc != OK) return rc;
@@ -117,10 +118,10 @@ struct Stage2 {
         PCHK(d, launch_value_scan(dmeta, n_rec, scratch, values, st));
         PCHK(d, hipMemcpyAsync(&val_total, values.vscan + R, 8, hipMemcpyDeviceToHost, st));
       }
-      if (d->ev_strings) {  // the kept records whose class carries a string, and how many they are
-        PCHK(d, hipMemsetAsync(d->es_cell.p, 0, sizeof(StringsCell), st));
-        PCHK(d, launch_strings_select(scratch.keep, (const uint4*)s.ev_tmp.p, n_rec, d->ev_types, strings_select(), st));
-        PCHK(d, hipMemcpyAsync(&strings_cell, d->es_cell.p, sizeof(strings_cell), hipMemcpyDeviceToHost, st));
+      if (ev.armed) {  // the kept records whose class carries a string, and how many they are
+        PCHK(d, hipMemsetAsync(ev.select.cell.p, 0, sizeof(StringsCell), st));
+        PCHK(d, launch_strings_select(scratch.keep, (const uint4*)s.ev_tmp.p, n_rec, ev.types, strings_select(), st));
+        PCHK(d, hipMemcpyAsync(&strings_cell, ev.select.cell.p, sizeof(strings_cell), hipMemcpyDeviceToHost, st));
       }
       PCHK(d, hipMemcpyAsync(&ec, derr, sizeof(ec), hipMemcpyDeviceToHost, st));
       PCHK(d, hipMemcpyAsync(&first_total, (unsigned long long*)d->first_scan.p + R, 8, hipMemcpyDeviceToHost, st));
@@ -142,29 +143,29 @@ struct Stage2 {
     d->counters[0] += n_rec;
     n_new = (int64_t)(first_total >> 40);
     new_bytes = (int64_t)(first_total & ((1ull << 40) - 1));
-    n_sel = d->ev_strings ? (int64_t)strings_cell.n_sel : 0;
+    n_sel = ev.armed ? (int64_t)strings_cell.n_sel : 0;
     return OK;
   }
 
-  StringsSelect strings_select() const { return StringsSelect{(uint32_t*)d->es_seg.p, (uint32_t*)d->es_count.p, (uint32_t*)d->es_base.p, (StringsCell*)d->es_cell.p}; }
+  StringsSelect strings_select() const { return StringsSelect{(uint32_t*)ev.select.seg.p, (uint32_t*)ev.select.count.p, (uint32_t*)ev.select.base.p, (StringsCell*)ev.select.cell.p}; }
 
   // kept event strings, a push that selected records: their list, their strings validated by the rule where stage 1 left the
   // values — spans and statuses go straight behind what is pending — and the bytes their values take; the wait brings a refusal
   // back while nothing of the push is committed (a push that selected nothing has none of this)
   int32_t validate_strings() {
-    const size_t keep_n = (size_t)(d->ev_pend_n + n_sel);
-    hipError_t e = d->es_sel.reserve((size_t)n_sel * 4, false, st);
-    if (e == hipSuccess) e = d->es_lens.reserve((size_t)n_sel * 8, false, st);
-    if (e == hipSuccess) e = d->es_totals.reserve((((size_t)n_sel + 1023) / 1024 + 1) * 8, false, st);
-    if (e == hipSuccess) e = d->ev_pend_off.reserve((keep_n + 1) * 8, true, st);
-    if (e == hipSuccess) e = d->ev_pend_rows.reserve(keep_n * 8, true, st);
-    if (e == hipSuccess) e = d->ev_pend_spans.reserve(keep_n * (2 * SURGE_JSON_STRING_COLUMNS) * 8, true, st);
-    for (int c = 0; c < SURGE_JSON_STRING_COLUMNS && e == hipSuccess; ++c) e = d->ev_pend_status[c].reserve(keep_n, true, st);
+    const size_t keep_n = (size_t)(ev.pend.n + n_sel);
+    hipError_t e = ev.select.sel.reserve((size_t)n_sel * 4, false, st);
+    if (e == hipSuccess) e = ev.select.lens.reserve((size_t)n_sel * 8, false, st);
+    if (e == hipSuccess) e = ev.select.totals.reserve((((size_t)n_sel + 1023) / 1024 + 1) * 8, false, st);
+    if (e == hipSuccess) e = ev.pend.off.reserve((keep_n + 1) * 8, true, st);
+    if (e == hipSuccess) e = ev.pend.rows.reserve(keep_n * 8, true, st);
+    if (e == hipSuccess) e = ev.pend.spans.reserve(keep_n * (2 * SURGE_JSON_STRING_COLUMNS) * 8, true, st);
+    for (int c = 0; c < SURGE_JSON_STRING_COLUMNS && e == hipSuccess; ++c) e = ev.pend.status[c].reserve(keep_n, true, st);
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? E_NOMEM : E_DEVICE, std::string("growing the kept event strings: ") + hipGetErrorString(e));
-    int64_t* const lens = (int64_t*)d->es_lens.p;
-    int64_t* const totals = (int64_t*)d->es_totals.p;
-    PCHK(d, launch_strings_list(dmeta, n_rec, strings_select(), (uint32_t*)d->es_sel.p, lens, st));
-    PCHK(d, launch_strings_spans(d->d_evs_rule.p, dmeta, dby, (const uint32_t*)d->es_sel.p, n_sel, strings_pending_of(d), derr, st));
+    int64_t* const lens = (int64_t*)ev.select.lens.p;
+    int64_t* const totals = (int64_t*)ev.select.totals.p;
+    PCHK(d, launch_strings_list(dmeta, n_rec, strings_select(), (uint32_t*)ev.select.sel.p, lens, st));
+    PCHK(d, launch_strings_spans(ev.rule.p, dmeta, dby, (const uint32_t*)ev.select.sel.p, n_sel, ev.pending(), derr, st));
     PCHK(d, launch_strings_scan(lens, n_sel, totals, st));
     PCHK(d, hipMemcpyAsync(&sel_bytes, totals + (n_sel + 1023) / 1024, 8, hipMemcpyDeviceToHost, st));
     PCHK(d, hipMemcpyAsync(&ec, derr, sizeof(ec), hipMemcpyDeviceToHost, st));
@@ -217,7 +218,7 @@ struct Stage2 {
       if (e == hipSuccess) e = d->long_runs.reserve((n_runs + 1) * 4, false, st);
     }
     if (e == hipSuccess) e = d->r_off.reserve((size_t)(d->n_records + kept) * 8 + 16, true, st);
-    if (e == hipSuccess && n_sel > 0) e = d->ev_pend_val.reserve((size_t)(d->ev_pend_bytes + sel_bytes) + 64, true, st);
+    if (e == hipSuccess && n_sel > 0) e = ev.pend.val.reserve((size_t)(ev.pend.bytes + sel_bytes) + 64, true, st);
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? E_NOMEM : E_DEVICE, std::string("growing the key table / result arrays: ") + hipGetErrorString(e));
     return OK;
   }
@@ -238,10 +239,10 @@ struct Stage2 {
       d->val_bytes += (int64_t)val_total;
     }
     if (n_sel > 0) {  // the selected records' values leave the slot's bytes too, their rows beside them
-      PCHK(d, launch_strings_gather(dmeta, dby, (const uint32_t*)d->es_sel.p, (const int64_t*)d->es_lens.p, n_sel, sel_bytes, (const uint32_t*)d->keep_pos.p,
-                                    (const int64_t*)d->r_agg.p + d->n_records, strings_pending_of(d), st));
-      d->ev_pend_n += n_sel;
-      d->ev_pend_bytes += sel_bytes;
+      PCHK(d, launch_strings_gather(dmeta, dby, (const uint32_t*)ev.select.sel.p, (const int64_t*)ev.select.lens.p, n_sel, sel_bytes, (const uint32_t*)d->keep_pos.p,
+                                    (const int64_t*)d->r_agg.p + d->n_records, ev.pending(), st));
+      ev.pend.n += n_sel;
+      ev.pend.bytes += sel_bytes;
     }
     d->n_keys += n_new;
     d->arena_bytes += new_bytes;
@@ -311,6 +312,6 @@ int32_t surge::ingest::host::stage2(surge_device_decoder* d, PushSlot& s, bool w
   if (rc == OK) rc = push.patch_host_doubles();
   if (rc == OK) rc = push.close(wait);
   // more pending than the bound: the columns are merged now (the merge waits for the stream)
-  if (rc == OK && d->ev_strings && d->ev_pend_n > d->ev_pend_bound) rc = merge_event_strings(d);
+  if (rc == OK && push.ev.armed && push.ev.pend.n > push.ev.pend.bound) rc = merge_event_strings(d);
   return rc;
 }

@@ -20,7 +20,7 @@
 // array: SURGE_EVENT_STRING_ABSENT is not OK, so such a record is never a winner).  It rewrites a whole column — once per fetch
 // would be quadratic on a 10^7-aggregate topic — so the gathered records ACCUMULATE across pushes and the merge runs when the
 // columns are asked for (surge_device_decoder_state_strings, the end of a recovery) or when more than the bound of
-// records are pending (surge_device_decoder::ev_pend_bound, 2^20: at BankAccount's ~100 bytes a value 100 MB of device memory; SURGE_INGEST_EVENT_STRINGS_PENDING
+// records are pending (EventStringsState::Pending::bound, 2^20: at BankAccount's ~100 bytes a value 100 MB of device memory; SURGE_INGEST_EVENT_STRINGS_PENDING
 // sets another bound, the tests a low one).  clear drops what is pending; a re-seed or a growth of the key table does not touch
 // it: rows do not move.
 #include "event_strings_parse.h"

@@ -59,6 +59,22 @@ def _dev_ptr(t, nbytes_min: int = 0):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def device_view(ptr, shape, typestr: str, device):
+    """A CUDA tensor over ``shape`` elements of ``typestr`` (``"<i8"`` / ``"|u1"``) at the device address ``ptr`` holds, on the
+    device of index ``device`` (``__cuda_array_interface__``: no copy, the memory stays its owner's) — or, where there is
+    nothing to view, the empty tensor of that dtype and shape."""
+    import torch
+
+    dtypes = {"<i8": torch.int64, "|u1": torch.uint8}
+    if typestr not in dtypes:
+        raise ValueError(f"device_view: typestr {typestr!r} is not one of {sorted(dtypes)}")
+    dev = torch.device("cuda", device)
+    if 0 in shape:
+        return torch.zeros(shape, dtype=dtypes[typestr], device=dev)
+    iface = {"shape": shape, "typestr": typestr, "data": (ptr.value or 0, False), "version": 2}
+    return torch.as_tensor(type("_Span", (), {"__cuda_array_interface__": iface})(), device=dev)
+
+
 def default_schema_from_library() -> CSchema:
     s = CSchema()
     rc = _native.load().surge_replay_default_schema(ctypes.byref(s))
@@ -283,20 +299,10 @@ class ReplayEngine:
 
     def bound_log(self):
         """``(seg_off, events[n, 2] int64)`` CUDA tensor views of the bound log (valid until the next load / bind / pack)."""
-        import torch
-
         po, pe = ctypes.c_void_p(), ctypes.c_void_p()
         na, ne = ctypes.c_int64(), ctypes.c_int64()
         self._check(self._lib.surge_replay_bound_log(self._h, ctypes.byref(po), ctypes.byref(pe), ctypes.byref(na), ctypes.byref(ne)))
-        dev = torch.device("cuda", self.device)
-
-        def view(ptr, shape):
-            iface = {"shape": shape, "typestr": "<i8", "data": (ptr.value or 0, False), "version": 2}
-            return torch.as_tensor(type("_Span", (), {"__cuda_array_interface__": iface})(), device=dev)
-
-        so = view(po, (na.value + 1,))
-        ev = view(pe, (ne.value, 2)) if ne.value else torch.zeros((0, 2), dtype=torch.int64, device=dev)
-        return so, ev
+        return device_view(po, (na.value + 1,), "<i8", self.device), device_view(pe, (ne.value, 2), "<i8", self.device)
 
     def grow(self, new_n_agg: int) -> None:
         """Extend the resident state to ``new_n_agg`` aggregates (the new ones ``None``); see ``surge_replay_grow``."""
@@ -356,10 +362,7 @@ class ReplayEngine:
         for t in self._keep:
             if t is not None and _is_torch(t) and t.data_ptr() == ptr.value:
                 return t.view(torch.uint8).reshape(-1)[: n.value * 64].view(n.value, 64)
-        # handle-owned buffer: wrap through the CUDA array interface
-        iface = {"shape": (n.value, 64), "typestr": "|u1", "data": (ptr.value or 0, False), "version": 3}
-        holder = type("_DevView", (), {"__cuda_array_interface__": iface})()
-        return torch.as_tensor(holder, device=f"cuda:{self.device}")
+        return device_view(ptr, (n.value, 64), "|u1", self.device)  # a buffer of the handle's own
 
     def pack_states(self, states64, packed40, stream=None) -> None:
         """``n x 64`` -> ``n x 40`` bytes (snapshot wire form), on ``stream`` (default: the engine's)."""

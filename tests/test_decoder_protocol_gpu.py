@@ -138,3 +138,29 @@ def test_counters_and_stats_after_each_of_three_pushes():
         d.reserve(5000, 5000 * 8)
         print("decoder accounting, reserve(5000):", d.stats())
         assert d.stats()["table_slots"] == TABLE_SLOTS_RESERVED and d.stats()["pushes"] == 0
+
+
+# ---- 4: the reads between pushes refuse in a fixed order ---------------------------------------------------------------------
+def test_every_read_of_the_key_table_is_refused_while_a_push_is_pending():
+    """include/surge_ingest.h: the lookups, the key order, the range and the key gather need every push finished
+    (SURGE_E_STATE).  The pending test comes before anything a read decides from its arguments: ``lookup`` of no id at all is
+    refused too while a push is pending, and is an empty answer once it is finished."""
+    import torch
+
+    recs = [(b"id0:0", event(0)), (b"id1:1", event(1)), (b"id0:2", event(2))]
+    with EventsTopicIngest(frames=True) as g, DeviceDecoder(None) as d:
+        g.feed(kw.record_batch(0, recs))
+        sections, arena = g.drain_sections()
+        d.push_async((sections, arena))
+        assert d.pending == 1
+        refused(E_STATE, d.lookup, [])
+        refused(E_STATE, d.lookup, [b"id0"])
+        refused(E_STATE, d.key_order)
+        refused(E_STATE, d.range_rows)
+        refused(E_STATE, d.gather_keys, torch.zeros(1, dtype=torch.int64, device="cuda"))
+        assert d.pending == 1
+        d.finish()
+        none = d.lookup([])
+        assert none.dtype == np.int64 and none.shape == (0,)
+        assert d.range_rows().cpu().tolist() == [0, 1]
+        assert d.key_order().cpu().tolist() == [0, 1]
