@@ -182,8 +182,9 @@ int32_t surge_replay_create_v2(const surge_replay_schema_v2* sc, int32_t device_
     // any failure leaves the generic interpreter in charge and is reported by surge_replay_kernel_info, not here
     DeviceGuard g(device_id);
     surge_replay_handle* h = *out;
-    slot_kernels_acquire(*sc, *(const SlotParams*)h->slot_params, device_id, &h->spec, &h->spec_compile_ms, &h->spec_why);
-    if (h->spec) h->spec_why = std::string("compiled by ") + rtc_library_path();
+    h->spec.tried = true;
+    h->spec.have = slot_kernels_acquire(*(const SlotParams*)h->slot_params, device_id, &h->spec.k, &h->spec.why);
+    if (h->spec.have) h->spec.why = std::string("compiled by ") + rtc_library_path();
   }
   return SURGE_OK;
 }

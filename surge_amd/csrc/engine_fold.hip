@@ -12,26 +12,18 @@ using namespace surge;
 
 namespace {
 
-// the flat kernel for this handle's op table: compiled (hiprtc, ~1 s) the first time a process folds with the table, shared
-// by every handle with the same table; nullptr = the ahead-of-time kernel (why: surge_replay_kernel_info)
-const V1Kernels* flat_spec(surge_replay_handle* h, const FoldParams& p) {
-  if (!h->spec1_tried) {
-    h->spec1_tried = true;
-    v1_kernels_acquire(p.table, h->device, V1_FLAT, &h->spec1, &h->spec1_compile_ms, &h->spec1_why);
-    if (h->spec1) h->spec1_why = std::string("flat kernel compiled for the op table by ") + rtc_library_path();
+// The kernels for this handle's op table: compiled (hiprtc, ~1 s) the first time a process folds with the table, shared by
+// every handle with the same table; nullptr = the ahead-of-time kernels (why: surge_replay_kernel_info).  V1_FLAT: the flat
+// kernel.  V1_LANES: the lane-per-row kernels (SORTED / CHUNKED / ROWS), compiled at surge_replay_prepare or the first such
+// fold — like the per-log index, before the fold's timing events, never between them.
+const V1Kernels* v1_spec(surge_replay_handle* h, const FoldParams& p, int kind) {
+  Compiled<V1Kernels>& c = kind == V1_FLAT ? h->spec1 : h->lanes1;
+  if (!c.tried) {
+    c.tried = true;
+    c.have = v1_kernels_acquire(p.table, h->device, kind, &c.k, &c.why);
+    if (c.have) c.why = kind == V1_FLAT ? std::string("flat kernel compiled for the op table by ") + rtc_library_path() : "compiled for the op table";
   }
-  return h->spec1;
-}
-
-// ... and the lane-per-row kernels (SORTED / CHUNKED / ROWS): compiled at surge_replay_prepare or the first such fold — like
-// the per-log index, before the fold's timing events, never between them
-const V1Kernels* lane_spec(surge_replay_handle* h, const FoldParams& p) {
-  if (!h->lanes1_tried) {
-    h->lanes1_tried = true;
-    v1_kernels_acquire(p.table, h->device, V1_LANES, &h->lanes1, &h->lanes1_compile_ms, &h->lanes1_why);
-    if (h->lanes1) h->lanes1_why = "compiled for the op table";
-  }
-  return h->lanes1;
+  return c.get();
 }
 
 // Wave-task size in events: a multiple of one tile (64 * lane_events events), about kTaskBytes of
@@ -82,7 +74,7 @@ int32_t next_fold_events(surge_replay_handle* h, hipEvent_t* e0, hipEvent_t* e1)
 
 // The one way a fold's dominant kernel is launched: between the fold's next event pair, nothing else.  `launch` enqueues
 // the kernel(s) and returns a SURGE_* status (nothing at all for a log with nothing to fold).  Whoever needs kernels
-// compiled at run time (flat_spec, lane_spec) acquires them BEFORE calling this: a process's first fold with an op table
+// compiled at run time (v1_spec) acquires them BEFORE calling this: a process's first fold with an op table
 // compiles it (hiprtc, ~1 s), and that must land before the timed region, not inside it.
 template <class Launch>
 int32_t timed_launch(surge_replay_handle* h, int64_t n_tasks, Launch launch) {
@@ -247,7 +239,7 @@ int32_t run_flat(surge_replay_handle* h, FoldParams& p, const int64_t* off, int6
   p.seg_off = off;
   p.plan = (const int64_t*)h->plan.ptr;
   p.n_seg = n_seg;  // (0 with d_n_seg: FLAT takes its segments from the plan)
-  const V1Kernels* spec = flat_spec(h, p);  // (a process's first fold with this op table compiles it: before the timed region, not inside it)
+  const V1Kernels* spec = v1_spec(h, p, V1_FLAT);  // (a process's first fold with this op table compiles it: before the timed region, not inside it)
   return timed_launch(h, n_tasks, [&]() -> int32_t {
     HIPCHK(h, launch_fold_flat(p, spec, n_tasks, le, h->stream));
     return SURGE_OK;
@@ -265,10 +257,10 @@ int32_t run_slots(surge_replay_handle* h, FoldParams& p, const int64_t* off, int
   p.n_seg = n_seg;
   // the interpreter is VALU-bound and light on registers (93 VGPRs): 8 KiB tiles and as many resident waves as LDS
   // allows; the schema-specialised kernels keep their tile in registers like the v1 sorted-rows kernel: 16 KiB tiles, 8 waves
-  const int le = env_lane_events("SURGE_REPLAY_LE_SLOTS", h->spec ? 16 : 8) == 16 ? 16 : 8;
-  const int64_t n_waves = resident_waves(h, n_seg, le == 8 ? (h->spec ? 12 : 14) : 8, "SURGE_REPLAY_SLOTS_WAVES");
+  const int le = env_lane_events("SURGE_REPLAY_LE_SLOTS", h->spec.have ? 16 : 8) == 16 ? 16 : 8;
+  const int64_t n_waves = resident_waves(h, n_seg, le == 8 ? (h->spec.have ? 12 : 14) : 8, "SURGE_REPLAY_SLOTS_WAVES");
   return timed_launch(h, n_waves, [&]() -> int32_t {
-    HIPCHK(h, launch_fold_slots(p, *(const SlotParams*)h->slot_params, h->spec, n_waves, le, h->stream));
+    HIPCHK(h, launch_fold_slots(p, *(const SlotParams*)h->slot_params, h->spec.get(), n_waves, le, h->stream));
     return SURGE_OK;
   });
 }
@@ -377,28 +369,31 @@ int32_t build_chunk_index(surge_replay_handle* h, surge_replay_handle::ChunkInde
   for (int k = 0; k < 3; ++k)
     HIPCHK(h, hipMemcpyAsync(&totals[k], cnt + (int64_t)k * (n_seg + 1) + n_seg, 8, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
-  ci.n_vrows = totals[0];
-  ci.n_cut_rows = totals[1];
+  ci.rows.n_vrows = totals[0];
+  ci.cut.n_cut = totals[1];
   // phase 2: the table itself (one allocation) ...
-  const size_t rows = (size_t)(ci.n_vrows > 0 ? ci.n_vrows : 1), cut = (size_t)(totals[1] > 0 ? totals[1] : 1), slots = (size_t)(totals[2] > 0 ? totals[2] : 1);
+  const size_t rows = (size_t)(totals[0] > 0 ? totals[0] : 1), cut = (size_t)(totals[1] > 0 ? totals[1] : 1), slots = (size_t)(totals[2] > 0 ? totals[2] : 1);
+  // the four arrays of `rows` virtual rows, carved from b: starts, destinations, lengths, infos
+  auto carve_rows = [&](char* b, ChunkRows& r) {
+    r.v_start = (int64_t*)b; r.v_dest = (int64_t*)(b + up(rows * 8)); r.v_len = (uint32_t*)(b + 2 * up(rows * 8));
+    r.v_info = (uint32_t*)(b + 2 * up(rows * 8) + up(rows * 4));
+  };
+  const size_t rows_bytes = 2 * up(rows * 8) + 2 * up(rows * 4);
   {
-    const size_t o_start = 0, o_seg = o_start + up(rows * 8), o_len = o_seg + up(rows * 8), o_info = o_len + up(rows * 4), o_side = o_info + up(rows * 4),
-                 o_slot0 = o_side + up(slots * 80), o_out = o_slot0 + up(cut * 8), o_c = o_out + up(cut * 8), total = o_c + up(cut * 4);
+    const size_t o_side = rows_bytes, o_slot0 = o_side + up(slots * 80), o_out = o_slot0 + up(cut * 8), o_c = o_out + up(cut * 8), total = o_c + up(cut * 4);
     HIPCHK(h, ci.arena.reserve(total));
     char* b = (char*)ci.arena.ptr;
-    ci.v_start = b + o_start; ci.v_seg = b + o_seg; ci.v_len = b + o_len; ci.v_info = b + o_info; ci.v_side = b + o_side;
-    ci.r_slot0 = b + o_slot0; ci.r_out = b + o_out; ci.r_c = b + o_c;
+    carve_rows(b, ci.rows);
+    ci.rows.side = ci.cut.side = (uint32_t*)(b + o_side);
+    ci.cut.r_slot0 = (int64_t*)(b + o_slot0); ci.cut.r_out = (int64_t*)(b + o_out); ci.cut.r_c = (uint32_t*)(b + o_c);
   }
   // ... and the scratch of its build (one allocation): the sort's, then the rows in aggregate order
   IndexScratch sc;
   void* extra = nullptr;
-  const size_t o_ustart = 0, o_udest = o_ustart + up(rows * 8), o_ulen = o_udest + up(rows * 8), o_uinfo = o_ulen + up(rows * 4), u_total = o_uinfo + up(rows * 4);
-  SURGE_TRY(index_scratch(h, ci.n_vrows, true, max_row, 0, &sc, u_total, &extra));  // the rows (>= aggregates) are what gets sorted
-  char* u = (char*)extra;
-  HIPCHK(h, launch_chunk_table(csr.off, n_seg, csr.out_map, T, align, cnt, ci.n_vrows, sc,
-                               (int64_t*)(u + o_ustart), (uint32_t*)(u + o_ulen), (uint32_t*)(u + o_uinfo), (int64_t*)(u + o_udest),
-                               (int64_t*)ci.v_start, (uint32_t*)ci.v_len, (uint32_t*)ci.v_info, (int64_t*)ci.v_seg,
-                               (int64_t*)ci.r_slot0, (uint32_t*)ci.r_c, (int64_t*)ci.r_out, h->stream));
+  SURGE_TRY(index_scratch(h, ci.rows.n_vrows, true, max_row, 0, &sc, rows_bytes, &extra));  // the rows (>= aggregates) are what gets sorted
+  ChunkRows u;
+  carve_rows((char*)extra, u);
+  HIPCHK(h, launch_chunk_table(csr, T, align, cnt, sc, u, ci.rows, ci.cut, h->stream));
   ci.T = T;
   return SURGE_OK;
 }
@@ -426,9 +421,10 @@ int32_t ensure_index(surge_replay_handle* h, const FoldPlan& pl) {
     h->tiled_valid = false;
     HIPCHK(h, hipEventRecord(h->ev_i0, h->stream));
     SURGE_TRY(build_chunk_index(h, h->tidx, csr, pl.chunk_T, false));
-    const int64_t n_groups = (h->tidx.n_vrows + kWave - 1) / kWave;
+    const ChunkRows& rows = h->tidx.rows;
+    const int64_t n_groups = (rows.n_vrows + kWave - 1) / kWave;
     HIPCHK(h, h->t_gsub.reserve((size_t)(n_groups + 1) * 8));
-    HIPCHK(h, launch_tile_index((const uint32_t*)h->tidx.v_len, h->tidx.n_vrows, (int64_t*)h->t_gsub.ptr, h->stream));
+    HIPCHK(h, launch_tile_index(rows.v_len, rows.n_vrows, (int64_t*)h->t_gsub.ptr, h->stream));
     HIPCHK(h, launch_exclusive_scan_i64((int64_t*)h->t_gsub.ptr, n_groups, h->stream));
     int64_t n_sub = 0;
     HIPCHK(h, hipMemcpyAsync(&n_sub, (int64_t*)h->t_gsub.ptr + n_groups, 8, hipMemcpyDeviceToHost, h->stream));
@@ -437,12 +433,11 @@ int32_t ensure_index(surge_replay_handle* h, const FoldPlan& pl) {
     h->t_n_sub = n_sub;
     HIPCHK(h, h->t_tiles.reserve((size_t)n_sub * kTileSubBytes));
     HIPCHK(h, hipEventRecord(h->ev_r0, h->stream));
-    HIPCHK(h, launch_relayout(h->d_events, (const int64_t*)h->tidx.v_start, (const uint32_t*)h->tidx.v_len, h->tidx.n_vrows,
-                              (const int64_t*)h->t_gsub.ptr, n_sub, (uint4*)h->t_tiles.ptr, h->stream));
+    HIPCHK(h, launch_relayout(h->d_events, rows.v_start, rows.v_len, rows.n_vrows, (const int64_t*)h->t_gsub.ptr, n_sub, (uint4*)h->t_tiles.ptr, h->stream));
     HIPCHK(h, hipEventRecord(h->ev_r1, h->stream));
     if (std::getenv("SURGE_DBG_PRINT"))
       std::fprintf(stderr, "[surge dbg] tiles %p (%lld subtiles) v_len %p v_info %p v_dest %p g_sub %p state %p events %p\n", h->t_tiles.ptr,
-                   (long long)n_sub, h->tidx.v_len, h->tidx.v_info, h->tidx.v_seg, h->t_gsub.ptr, (void*)h->d_state, (const void*)h->d_events);
+                   (long long)n_sub, (void*)rows.v_len, (void*)rows.v_info, (void*)rows.v_dest, h->t_gsub.ptr, (void*)h->d_state, (const void*)h->d_events);
     h->tiled_valid = true;
     h->index_timed = h->relayout_timed = true;
     h->index_algo = SURGE_ALGO_TILED;
@@ -453,28 +448,115 @@ int32_t ensure_index(surge_replay_handle* h, const FoldPlan& pl) {
   return SURGE_OK;
 }
 
-// TILED, v1 and v2 (whose rows are whole aggregates, never cut) alike: the tile-major copy as the kernels see it, the
-// subtiles per step and the waves that walk it
-struct TiledLaunch {
-  TileTable t;
-  int subs;
-  int64_t n_waves;
-};
+// ---- one function per fold of the bound log (beside run_flat and run_slots above): each sets its parameters, acquires its
+// compiled kernels before the timed region and launches between the fold's event pair ---------------------------------------
 
-int32_t tiled_launch(surge_replay_handle* h, FoldParams& p, TiledLaunch* tl) {
-  tl->subs = 2;  // subtiles (8 events per lane) per step: 16 KiB in flight per wave
-  if (const char* v = std::getenv("SURGE_REPLAY_TILED_SUBS")) tl->subs = std::atoi(v) == 1 ? 1 : 2;
-  const auto& ci = h->tidx;
+int32_t run_rows(surge_replay_handle* h, FoldParams& p) {
+  const int le = env_lane_events("SURGE_REPLAY_LE_ROWS", 8);
+  // a task = G groups of 64 aggregates, about kTaskBytes of events
+  // Measured on MI355X: this access pattern runs fastest as ONE resident generation of waves (no
+  // re-dispatch, every wave streams from start to end): G groups of 64 aggregates per wave so that
+  // the grid just fits the chip's wave slots (CUs x 16 waves at 8 KiB tiles, x 9 at 16 KiB tiles).
+  const int64_t groups = (h->n_agg + kWave - 1) / kWave;
+  const int64_t slots = (int64_t)h->n_cus * (le == 8 ? 16 : (le == 16 ? 9 : 4));
+  int64_t G = (groups + slots - 1) / slots;
+  if (const char* v = std::getenv("SURGE_REPLAY_ROWS_GROUPS")) G = std::atoi(v);
+  if (G < 1) G = 1;
+  const int64_t per_task = G * kWave;
+  const int64_t n_tasks = (h->n_agg + per_task - 1) / per_task;
+  p.n_seg = h->n_agg;
+  p.fixed_len = h->an.len0;
+  p.segs_per_task = per_task;
+  const V1Kernels* lanes = v1_spec(h, p, V1_LANES);
+  return timed_launch(h, n_tasks, [&]() -> int32_t {
+    HIPCHK(h, launch_fold_rows(p, lanes, n_tasks, le, h->stream));
+    return SURGE_OK;
+  });
+}
+
+int32_t run_fixed(surge_replay_handle* h, FoldParams& p, int64_t span) {
+  const int le = env_lane_events("SURGE_REPLAY_LE_FIXED", 16);
+  const int64_t L = h->an.len0;
+  const int64_t task_events = choose_task_events(span, le);
+  int64_t G = task_events / L;
+  if (G < 1) G = 1;
+  const int64_t n_tasks = (h->n_agg + G - 1) / G;
+  p.n_seg = h->n_agg;
+  p.fixed_len = L;
+  p.segs_per_task = G;
+  return timed_launch(h, n_tasks, [&]() -> int32_t {
+    HIPCHK(h, launch_fold_fixed(p, n_tasks, le, h->stream));
+    return SURGE_OK;
+  });
+}
+
+int32_t run_short(surge_replay_handle* h, FoldParams& p) {
+  p.seg_off = h->d_seg_off;  // every aggregate is a row, the empty ones too
+  p.n_seg = h->n_agg;
+  return timed_launch(h, (h->n_agg + 63) / 64, [&]() -> int32_t {
+    HIPCHK(h, launch_fold_short(p, h->stream));
+    return SURGE_OK;
+  });
+}
+
+int32_t run_sorted(surge_replay_handle* h, FoldParams& p, const KernelCsr& csr) {
+  const int le = env_lane_events("SURGE_REPLAY_LE_SORTED", 16);
+  p.out_map = csr.out_map;
+  p.seg_off = csr.off;
+  p.plan = (const int64_t*)h->perm.ptr;
   SURGE_TRY(dispenser_begin(h, p));
-  p.n_seg = h->csr().n_seg;
+  p.n_seg = csr.n_seg;
+  // resident waves per CU = min(LDS, registers): 8 KiB tiles 12 (136 VGPRs), 16 KiB tiles 8 (18.6 KB LDS), 32 KiB tiles 4
+  const int64_t n_waves = resident_waves(h, csr.n_seg, le == 8 ? 12 : (le == 16 ? 8 : 4), "SURGE_REPLAY_SORTED_WAVES");  // (experiments)
+  const V1Kernels* lanes = v1_spec(h, p, V1_LANES);
+  // round 5: the walk that fetches the next group's first tile during this group's last one (fold_sorted_pf_kernel);
+  // SURGE_REPLAY_SORTED_KERNEL=plain keeps fold_sorted_kernel for a same-box comparison, and 32-event lanes are its only
+  static const bool plain = [] { const char* v = std::getenv("SURGE_REPLAY_SORTED_KERNEL"); return v && std::strcmp(v, "plain") == 0; }();
+  return timed_launch(h, n_waves, [&]() -> int32_t {
+    if (plain || (le == 32 && !lanes)) HIPCHK(h, launch_fold_sorted(p, n_waves, le, h->stream));
+    else HIPCHK(h, launch_fold_sorted_pf(p, lanes, n_waves, le, h->stream));
+    return SURGE_OK;
+  });
+}
+
+int32_t run_chunked(surge_replay_handle* h, FoldParams& p, const KernelCsr& csr) {
+  const int le = env_lane_events("SURGE_REPLAY_LE_CHUNKED", 16) == 8 ? 8 : 16;
+  const auto& ci = h->cidx;
+  SURGE_TRY(dispenser_begin(h, p));
+  p.n_seg = csr.n_seg;
+  // resident waves per CU: 16 KiB tiles 8 (2 per SIMD, 8 x 18.7 KB of LDS), 8 KiB tiles 12 (3 per SIMD)
+  const int64_t n_waves = resident_waves(h, ci.rows.n_vrows, le == 8 ? 12 : 8, nullptr);
+  const V1Kernels* lanes = v1_spec(h, p, V1_LANES);
+  return timed_launch(h, n_waves, [&]() -> int32_t {  // the stitch kernel is timed with the fold: it is part of it
+    HIPCHK(h, launch_fold_chunked(p, ci.rows, ci.cut, lanes, n_waves, le, h->stream));
+    return SURGE_OK;
+  });
+}
+
+// TILED, v1 and v2 (whose rows are whole aggregates, never cut) alike: the fold over the tile-major copy
+int32_t run_tiled(surge_replay_handle* h, FoldParams& p, const KernelCsr& csr) {
+  const auto& ci = h->tidx;
+  if (h->v2) p.out_map = csr.out_map;
+  int subs = 2;  // subtiles (8 events per lane) per step: 16 KiB in flight per wave
+  if (const char* v = std::getenv("SURGE_REPLAY_TILED_SUBS")) subs = std::atoi(v) == 1 ? 1 : 2;
+  SURGE_TRY(dispenser_begin(h, p));
+  p.n_seg = csr.n_seg;
   // resident waves per CU.  Measured (round 3, same handle, Zipf(1..4096) logs of 9 / 30 / 74 GB and config C2): with
   // 16 KiB steps 6 waves per CU beat 8 and 9 by 0.3-7 % and 4 by 0-5 %; 8 KiB steps are 0.5-4 % behind at any count
-  tl->n_waves = resident_waves(h, ci.n_vrows, tl->subs == 1 ? 8 : 6, "SURGE_REPLAY_TILED_WAVES");
-  TileTable& t = tl->t;
-  t.tiles = (const uint4*)h->t_tiles.ptr; t.g_sub0 = (const int64_t*)h->t_gsub.ptr; t.v_len = (const uint32_t*)ci.v_len;
-  t.v_info = (const uint32_t*)ci.v_info; t.v_dest = (const int64_t*)ci.v_seg; t.n_vrows = ci.n_vrows;
-  t.side = h->v2 ? nullptr : (uint32_t*)ci.v_side;
-  return SURGE_OK;
+  const int64_t n_waves = resident_waves(h, ci.rows.n_vrows, subs == 1 ? 8 : 6, "SURGE_REPLAY_TILED_WAVES");
+  TileTable t;  // (the one place the kernels' table is made: the chunk table's rows over the tile-major copy)
+  t.tiles = (const uint4*)h->t_tiles.ptr; t.g_sub0 = (const int64_t*)h->t_gsub.ptr; t.v_len = ci.rows.v_len;
+  t.v_info = ci.rows.v_info; t.v_dest = ci.rows.v_dest; t.n_vrows = ci.rows.n_vrows;
+  t.side = h->v2 ? nullptr : ci.rows.side;
+  return timed_launch(h, n_waves, [&]() -> int32_t {  // the stitch kernel is timed with the fold: it is part of it
+    if (h->v2) {
+      HIPCHK(h, launch_fold_slots_tiled(p, *(const SlotParams*)h->slot_params, h->spec.get(), t, n_waves, subs, h->stream));
+      return SURGE_OK;
+    }
+    HIPCHK(h, launch_fold_tiled(p, t, n_waves, subs, h->stream));
+    HIPCHK(h, launch_chunk_stitch(p, ci.cut, h->stream));
+    return SURGE_OK;
+  });
 }
 
 // surge_replay_compile_schema(_v2): the program through hiprtc for `arch`, the code object to the caller
@@ -502,13 +584,13 @@ int32_t surge_replay_kernel_info(surge_replay_handle* h, surge_replay_kernel_inf
     DeviceGuard g(h->device);
     FoldParams p;
     fill_params(h, p);
-    (void)flat_spec(h, p);
+    (void)v1_spec(h, p, V1_FLAT);
   }
-  out->specialised = h->v2 ? (h->spec ? 1 : 0) : (h->spec1 ? 1 : 0);
-  out->compile_ms = h->v2 ? h->spec_compile_ms : h->spec1_compile_ms;
-  std::string d = h->v2 ? h->spec_why
-                        : (h->spec1 ? h->spec1_why : "v1 schema, ahead-of-time kernels interpret the op table: " + h->spec1_why);
-  if (!h->v2 && h->lanes1_tried) d = "lane kernels " + (h->lanes1 ? h->lanes1_why : "ahead of time (" + h->lanes1_why.substr(0, 60) + ")") + "; " + d;
+  out->specialised = (h->v2 ? h->spec.have : h->spec1.have) ? 1 : 0;
+  out->compile_ms = h->v2 ? h->spec.k.compile_ms : h->spec1.k.compile_ms;
+  std::string d = h->v2 ? h->spec.why
+                        : (h->spec1.have ? h->spec1.why : "v1 schema, ahead-of-time kernels interpret the op table: " + h->spec1.why);
+  if (!h->v2 && h->lanes1.tried) d = "lane kernels " + (h->lanes1.have ? h->lanes1.why : "ahead of time (" + h->lanes1.why.substr(0, 60) + ")") + "; " + d;
   std::snprintf(out->detail, sizeof(out->detail), "%s", d.c_str());
   return SURGE_OK;
 }
@@ -549,7 +631,7 @@ int32_t surge_replay_prepare(surge_replay_handle* h, int32_t algo) {
   if (!h->v2 && (pl.use == SURGE_ALGO_SORTED || pl.use == SURGE_ALGO_CHUNKED || pl.use == SURGE_ALGO_ROWS)) {
     FoldParams p;
     fill_params(h, p);
-    (void)lane_spec(h, p);  // the kernels for this op table (hiprtc, or the code-object cache on disk)
+    (void)v1_spec(h, p, V1_LANES);  // the kernels for this op table (hiprtc, or the code-object cache on disk)
   }
   return ensure_index(h, pl);
 }
@@ -561,12 +643,12 @@ int32_t surge_replay_layout_info(surge_replay_handle* h, surge_replay_layout_inf
   std::memset(out, 0, sizeof(*out));
   out->algo = h->index_algo;
   if (h->index_algo == SURGE_ALGO_CHUNKED) {
-    out->virtual_rows = h->cidx.n_vrows;
-    out->cut_aggregates = h->cidx.n_cut_rows;
+    out->virtual_rows = h->cidx.rows.n_vrows;
+    out->cut_aggregates = h->cidx.cut.n_cut;
     out->chunk_events = h->cidx.T;
   } else if (h->index_algo == SURGE_ALGO_TILED) {
-    out->virtual_rows = h->tidx.n_vrows;
-    out->cut_aggregates = h->tidx.n_cut_rows;
+    out->virtual_rows = h->tidx.rows.n_vrows;
+    out->cut_aggregates = h->tidx.cut.n_cut;
     out->chunk_events = h->tidx.T;
     out->tiled_bytes = h->t_n_sub * kTileSubBytes;
     out->padding_events = h->t_n_sub * (kTileSubBytes / 16) - (h->an.last - h->an.first);
@@ -600,8 +682,8 @@ int32_t surge_replay_index_order(surge_replay_handle* h, int32_t algo, int64_t* 
     src = h->perm.ptr;
     n = h->csr().n_seg;
   } else if (algo == SURGE_ALGO_CHUNKED && h->cidx.T != 0) {
-    src = h->cidx.v_start;
-    n = h->cidx.n_vrows;
+    src = h->cidx.rows.v_start;
+    n = h->cidx.rows.n_vrows;
   } else {
     return fail(h, SURGE_E_STATE, "the bound log has no index of that kind (surge_replay_prepare / fold with SURGE_ALGO_SORTED or _CHUNKED first)");
   }
@@ -634,103 +716,21 @@ int32_t surge_replay_fold(surge_replay_handle* h, int32_t algo) {
 
   SURGE_TRY(fold_begin(h));
   if (h->n_agg > 0 && span > 0) {
-    if (use == SURGE_ALGO_ROWS) {
-      const int le = env_lane_events("SURGE_REPLAY_LE_ROWS", 8);
-      // a task = G groups of 64 aggregates, about kTaskBytes of events
-      // Measured on MI355X: this access pattern runs fastest as ONE resident generation of waves (no
-      // re-dispatch, every wave streams from start to end): G groups of 64 aggregates per wave so that
-      // the grid just fits the chip's wave slots (CUs x 16 waves at 8 KiB tiles, x 9 at 16 KiB tiles).
-      const int64_t groups = (h->n_agg + kWave - 1) / kWave;
-      const int64_t slots = (int64_t)h->n_cus * (le == 8 ? 16 : (le == 16 ? 9 : 4));
-      int64_t G = (groups + slots - 1) / slots;
-      if (const char* v = std::getenv("SURGE_REPLAY_ROWS_GROUPS")) G = std::atoi(v);
-      if (G < 1) G = 1;
-      const int64_t per_task = G * kWave;
-      const int64_t n_tasks = (h->n_agg + per_task - 1) / per_task;
-      p.n_seg = h->n_agg;
-      p.fixed_len = h->an.len0;
-      p.segs_per_task = per_task;
-      const V1Kernels* lanes = lane_spec(h, p);
-      SURGE_TRY(timed_launch(h, n_tasks, [&]() -> int32_t {
-        HIPCHK(h, launch_fold_rows(p, lanes, n_tasks, le, h->stream));
-        return SURGE_OK;
-      }));
-    } else if (use == SURGE_ALGO_FIXED) {
-      const int le = env_lane_events("SURGE_REPLAY_LE_FIXED", 16);
-      const int64_t L = h->an.len0;
-      const int64_t task_events = choose_task_events(span, le);
-      int64_t G = task_events / L;
-      if (G < 1) G = 1;
-      const int64_t n_tasks = (h->n_agg + G - 1) / G;
-      p.n_seg = h->n_agg;
-      p.fixed_len = L;
-      p.segs_per_task = G;
-      SURGE_TRY(timed_launch(h, n_tasks, [&]() -> int32_t {
-        HIPCHK(h, launch_fold_fixed(p, n_tasks, le, h->stream));
-        return SURGE_OK;
-      }));
-    } else if (use == SURGE_ALGO_SHORT) {
-      p.seg_off = h->d_seg_off;  // every aggregate is a row, the empty ones too
-      p.n_seg = h->n_agg;
-      SURGE_TRY(timed_launch(h, (h->n_agg + 63) / 64, [&]() -> int32_t {
-        HIPCHK(h, launch_fold_short(p, h->stream));
-        return SURGE_OK;
-      }));
-    } else if (use == SURGE_ALGO_SORTED) {
-      const int le = env_lane_events("SURGE_REPLAY_LE_SORTED", 16);
-      p.out_map = csr.out_map;
-      p.seg_off = csr.off;
-      p.plan = (const int64_t*)h->perm.ptr;
-      SURGE_TRY(dispenser_begin(h, p));
-      p.n_seg = csr.n_seg;
-      // resident waves per CU = min(LDS, registers): 8 KiB tiles 12 (136 VGPRs), 16 KiB tiles 8 (18.6 KB LDS), 32 KiB tiles 4
-      const int64_t n_waves = resident_waves(h, csr.n_seg, le == 8 ? 12 : (le == 16 ? 8 : 4), "SURGE_REPLAY_SORTED_WAVES");  // (experiments)
-      const V1Kernels* lanes = lane_spec(h, p);
-      // round 5: the walk that fetches the next group's first tile during this group's last one (fold_sorted_pf_kernel);
-      // SURGE_REPLAY_SORTED_KERNEL=plain keeps fold_sorted_kernel for a same-box comparison, and 32-event lanes are its only
-      static const bool plain = [] { const char* v = std::getenv("SURGE_REPLAY_SORTED_KERNEL"); return v && std::strcmp(v, "plain") == 0; }();
-      SURGE_TRY(timed_launch(h, n_waves, [&]() -> int32_t {
-        if (plain || (le == 32 && !lanes)) HIPCHK(h, launch_fold_sorted(p, n_waves, le, h->stream));
-        else HIPCHK(h, launch_fold_sorted_pf(p, lanes, n_waves, le, h->stream));
-        return SURGE_OK;
-      }));
-    } else if (use == SURGE_ALGO_CHUNKED) {
-      const int le = env_lane_events("SURGE_REPLAY_LE_CHUNKED", 16) == 8 ? 8 : 16;
-      const auto& ci = h->cidx;
-      SURGE_TRY(dispenser_begin(h, p));
-      p.n_seg = csr.n_seg;
-      // resident waves per CU: 16 KiB tiles 8 (2 per SIMD, 8 x 18.7 KB of LDS), 8 KiB tiles 12 (3 per SIMD)
-      const int64_t n_waves = resident_waves(h, ci.n_vrows, le == 8 ? 12 : 8, nullptr);
-      const V1Kernels* lanes = lane_spec(h, p);
-      SURGE_TRY(timed_launch(h, n_waves, [&]() -> int32_t {  // the stitch kernel is timed with the fold: it is part of it
-        HIPCHK(h, launch_fold_chunked(p, (const int64_t*)ci.v_start, (const uint32_t*)ci.v_len, (const uint32_t*)ci.v_info,
-                                      (const int64_t*)ci.v_seg, ci.n_vrows, (uint32_t*)ci.v_side, (const int64_t*)ci.r_slot0,
-                                      (const uint32_t*)ci.r_c, (const int64_t*)ci.r_out, ci.n_cut_rows, lanes, n_waves, le, h->stream));
-        return SURGE_OK;
-      }));
-    } else if (use == SURGE_ALGO_TILED) {
-      const auto& ci = h->tidx;
-      TiledLaunch tl;
-      if (h->v2) p.out_map = csr.out_map;
-      SURGE_TRY(tiled_launch(h, p, &tl));
-      const TileTable& t = tl.t;
-      SURGE_TRY(timed_launch(h, tl.n_waves, [&]() -> int32_t {  // the stitch kernel is timed with the fold: it is part of it
-        if (h->v2) {
-          HIPCHK(h, launch_fold_slots_tiled(p, *(const SlotParams*)h->slot_params, h->spec, t, tl.n_waves, tl.subs, h->stream));
-          return SURGE_OK;
-        }
-        HIPCHK(h, launch_fold_tiled(p, t.tiles, t.g_sub0, t.v_len, t.v_info, t.v_dest, t.n_vrows, t.side, tl.n_waves, tl.subs, h->stream));
-        HIPCHK(h, launch_chunk_stitch(p, (const uint32_t*)ci.v_side, (const int64_t*)ci.r_slot0, (const uint32_t*)ci.r_c,
-                                      (const int64_t*)ci.r_out, ci.n_cut_rows, h->stream));
-        return SURGE_OK;
-      }));
-    } else if (use == SURGE_ALGO_SLOTS) {
-      if (h->an.max_len >= (1ll << 31)) return fail(h, SURGE_E_UNSUPPORTED, "segments must be shorter than 2^31 events");
-      p.out_map = csr.out_map;
-      SURGE_TRY(run_slots(h, p, csr.off, csr.n_seg, true));
-    } else {
-      p.out_map = csr.out_map;
-      SURGE_TRY(run_flat(h, p, csr.off, csr.n_seg, span));
+    switch (use) {
+      case SURGE_ALGO_ROWS: SURGE_TRY(run_rows(h, p)); break;
+      case SURGE_ALGO_FIXED: SURGE_TRY(run_fixed(h, p, span)); break;
+      case SURGE_ALGO_SHORT: SURGE_TRY(run_short(h, p)); break;
+      case SURGE_ALGO_SORTED: SURGE_TRY(run_sorted(h, p, csr)); break;
+      case SURGE_ALGO_CHUNKED: SURGE_TRY(run_chunked(h, p, csr)); break;
+      case SURGE_ALGO_TILED: SURGE_TRY(run_tiled(h, p, csr)); break;
+      case SURGE_ALGO_SLOTS:
+        if (h->an.max_len >= (1ll << 31)) return fail(h, SURGE_E_UNSUPPORTED, "segments must be shorter than 2^31 events");
+        p.out_map = csr.out_map;
+        SURGE_TRY(run_slots(h, p, csr.off, csr.n_seg, true));
+        break;
+      default:
+        p.out_map = csr.out_map;
+        SURGE_TRY(run_flat(h, p, csr.off, csr.n_seg, span));
     }
   } else {
     SURGE_TRY(timed_launch(h, 0, [] { return (int32_t)SURGE_OK; }));  // nothing to fold: an empty timed region

@@ -49,11 +49,14 @@ struct DeviceGuard {
   }
 };
 
-// the kernel-facing CSR of the bound log (surge_replay_handle::csr)
-struct KernelCsr {
-  const int64_t* off;      // n_seg + 1 offsets, no empty segment among them
-  int64_t n_seg;
-  const int64_t* out_map;  // segment -> aggregate, or nullptr: segment i is aggregate i
+// One run-time compiled program of a handle (K: V1Kernels, SlotKernels): its kernels once acquired, else why the
+// ahead-of-time ones run (what surge_replay_kernel_info reports).
+template <class K>
+struct Compiled {
+  K k;  // (k.compile_ms stays 0 when nothing was compiled)
+  bool have = false, tried = false;
+  std::string why;
+  const K* get() const { return have ? &k : nullptr; }
 };
 
 }  // namespace surge
@@ -67,17 +70,11 @@ struct surge_replay_handle {
   bool v2 = false;                     // ABI v2 slot schema: folds only through fold_slots.hip
   surge_replay_schema_v2 schema2{};
   alignas(16) unsigned char slot_params[surge::kSlotParamsBytes] = {};
-  surge::SlotKernels* spec = nullptr;  // v2: the kernels hiprtc compiled for this schema (process-wide cache); nullptr = interpreter
-  surge::V1Kernels* spec1 = nullptr;   // v1: the flat kernel compiled for this handle's op table (acquired at the first flat fold)
-  bool spec1_tried = false;
-  double spec1_compile_ms = 0.0;
-  std::string spec1_why;
-  surge::V1Kernels* lanes1 = nullptr;  // v1: the lane-per-row kernels (SORTED / CHUNKED / ROWS) compiled for the op table (first lane fold / prepare)
-  bool lanes1_tried = false;
-  double lanes1_compile_ms = 0.0;
-  std::string lanes1_why;
-  double spec_compile_ms = 0.0;
-  std::string spec_why;                // why the interpreter runs instead / which libhiprtc compiled the kernels
+  // the kernels compiled for this handle's schema (process-wide modules, rtc_module.hip); `why`: which libhiprtc compiled them,
+  // or why the ahead-of-time kernels run instead
+  surge::Compiled<surge::SlotKernels> spec;  // v2: acquired when the handle is created; none = the interpreter
+  surge::Compiled<surge::V1Kernels> spec1;   // v1: the flat kernel (acquired at the first flat fold)
+  surge::Compiled<surge::V1Kernels> lanes1;  // v1: the lane-per-row kernels, SORTED / CHUNKED / ROWS (first lane fold / prepare)
   std::string err;
   std::mutex err_mu;  // concurrent point readers may fail at the same time
 
@@ -109,14 +106,14 @@ struct surge_replay_handle {
   bool perm_valid = false;
   // CHUNKED / TILED: the chunk table (built lazily, per bound log), the chunk summaries and the list of cut aggregates
   struct ChunkIndex {
-    surge::DevBuf arena;  // one allocation; the pointers below are views into it
-    void *v_start = nullptr, *v_len = nullptr, *v_info = nullptr, *v_seg = nullptr, *v_side = nullptr, *r_slot0 = nullptr, *r_c = nullptr, *r_out = nullptr;
-    int64_t n_vrows = 0, n_cut_rows = 0;
+    surge::DevBuf arena;      // one allocation; the pointers below are views into it
+    surge::ChunkRows rows;
+    surge::StitchTable cut;
     uint32_t T = 0;  // the chunk target the table was built for (0 = none built)
     void release() {
       arena.release();
-      v_start = v_len = v_info = v_seg = v_side = r_slot0 = r_c = r_out = nullptr;
-      n_vrows = n_cut_rows = 0;
+      rows = {};
+      cut = {};
       T = 0;
     }
   };

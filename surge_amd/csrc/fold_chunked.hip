@@ -35,7 +35,6 @@
 // arithmetic are the sorted-rows kernel's (fold_device.h).  Integer adds wrap exactly like JVM Int/Long under
 // any association and min/max/set are exact, so the result is bit-identical to the sequential fold.
 #include <cstdlib>
-#include <cstring>
 
 #include "fold_lane_device.h"
 
@@ -84,65 +83,61 @@ fold_sorted_pf_kernel(const FoldParams p) {
   chunk_walk<LE, true, CONC>(p, t);
 }
 
-bool concrete_walk() {
-  static const bool v = [] { const char* e = std::getenv("SURGE_REPLAY_WALK"); return !(e && std::strcmp(e, "transformer") == 0); }();
-  return v;
+// LDS of a lane kernel compiled for the op table: no table in LDS — the tile and the row table only
+unsigned compiled_lane_lds(int lane_events) {
+  return lane_events == 8 ? Geo<8>::kTileBytes + Geo<8>::kAuxSorted
+                          : (lane_events == 32 ? Geo<32>::kTileBytes + Geo<32>::kAuxSorted : Geo<16>::kTileBytes + Geo<16>::kAuxSorted);
+}
+
+void launch_stitch(const FoldParams& p, const StitchTable& cut, hipStream_t stream) {
+  hipLaunchKernelGGL(chunk_stitch_kernel, dim3((unsigned)((cut.n_cut + 127) / 128)), dim3(128), 0, stream, p, cut.side, cut.r_slot0, cut.r_c, cut.r_out,
+                     cut.n_cut);
 }
 
 }  // namespace
 
 hipError_t launch_fold_sorted_pf(const FoldParams& p, const V1Kernels* lanes, int64_t n_waves, int lane_events, hipStream_t stream) {
   if (n_waves <= 0) return hipSuccess;
-  if (lanes) {  // compiled for the op table: no table in LDS — the tile and the row table only
+  if (lanes) {
     const char* padv = std::getenv("SURGE_REPLAY_RTC_LDS_PAD");  // (experiments: extra dynamic LDS = fewer resident waves per CU)
     const unsigned pad = padv ? (unsigned)std::atoi(padv) : 0u;
-    if (lane_events == 32) return launch_v1_lane(lanes->sorted32, &p, sizeof(p), n_waves, Geo<32>::kTileBytes + Geo<32>::kAuxSorted + pad, stream);
-    return launch_v1_lane(lane_events == 8 ? lanes->sorted8 : lanes->sorted16, &p, sizeof(p), n_waves,
-                          (lane_events == 8 ? Geo<8>::kTileBytes + Geo<8>::kAuxSorted : Geo<16>::kTileBytes + Geo<16>::kAuxSorted) + pad, stream);
+    const hipFunction_t fn = lane_events == 32 ? lanes->sorted32 : (lane_events == 8 ? lanes->sorted8 : lanes->sorted16);
+    return launch_module_kernel(fn, n_waves, compiled_lane_lds(lane_events) + pad, stream, &p, sizeof(p));
   }
-  const bool conc = concrete_walk();
-  if (lane_events == 8) {
-    if (conc) hipLaunchKernelGGL((fold_sorted_pf_kernel<8, true>), dim3((unsigned)n_waves), dim3(kWave), Geo<8>::lds_bytes(Geo<8>::kAuxSorted), stream, p);
-    else hipLaunchKernelGGL((fold_sorted_pf_kernel<8, false>), dim3((unsigned)n_waves), dim3(kWave), Geo<8>::lds_bytes(Geo<8>::kAuxSorted), stream, p);
-  } else {
-    if (conc) hipLaunchKernelGGL((fold_sorted_pf_kernel<16, true>), dim3((unsigned)n_waves), dim3(kWave), Geo<16>::lds_bytes(Geo<16>::kAuxSorted), stream, p);
-    else hipLaunchKernelGGL((fold_sorted_pf_kernel<16, false>), dim3((unsigned)n_waves), dim3(kWave), Geo<16>::lds_bytes(Geo<16>::kAuxSorted), stream, p);
-  }
+  for_lane_walk(lane_events, [&](auto w) {
+    using W = decltype(w);
+    hipLaunchKernelGGL((fold_sorted_pf_kernel<W::LE, W::CONC>), dim3((unsigned)n_waves), dim3(kWave), Geo<W::LE>::lds_bytes(Geo<W::LE>::kAuxSorted), stream, p);
+  });
   return hipGetLastError();
 }
 
 // the fold over the chunk table + the stitch of the cut aggregates
-hipError_t launch_fold_chunked(const FoldParams& p, const int64_t* v_start, const uint32_t* v_len, const uint32_t* v_info,
-                               const int64_t* v_dest, int64_t n_vrows, uint32_t* side, const int64_t* r_slot0, const uint32_t* r_c,
-                               const int64_t* r_out, int64_t n_cut, const V1Kernels* lanes, int64_t n_waves, int lane_events, hipStream_t stream) {
-  if (n_waves <= 0 || n_vrows <= 0) return hipSuccess;
-  ChunkTable t;
-  t.v_start = v_start; t.v_len = v_len; t.v_info = v_info; t.v_dest = v_dest; t.n_vrows = n_vrows; t.side = side;
-  const bool conc = concrete_walk();
+hipError_t launch_fold_chunked(const FoldParams& p, const ChunkRows& rows, const StitchTable& cut, const V1Kernels* lanes, int64_t n_waves,
+                               int lane_events, hipStream_t stream) {
+  if (n_waves <= 0 || rows.n_vrows <= 0) return hipSuccess;
+  ChunkTable t;  // (the one place the kernels' table is made from the host's)
+  t.v_start = rows.v_start; t.v_len = rows.v_len; t.v_info = rows.v_info; t.v_dest = rows.v_dest; t.n_vrows = rows.n_vrows; t.side = rows.side;
   if (lanes) {
     ChunkArgs a;
     a.p = p;
     a.t = t;
-    const hipError_t e = launch_v1_lane(lane_events == 8 ? lanes->chunked8 : lanes->chunked16, &a, sizeof(a), n_waves,
-                                        lane_events == 8 ? Geo<8>::kTileBytes + Geo<8>::kAuxSorted : Geo<16>::kTileBytes + Geo<16>::kAuxSorted, stream);
+    const hipError_t e = launch_module_kernel(lane_events == 8 ? lanes->chunked8 : lanes->chunked16, n_waves, compiled_lane_lds(lane_events == 8 ? 8 : 16),
+                                              stream, &a, sizeof(a));
     if (e != hipSuccess) return e;
-  } else if (lane_events == 8) {
-    if (conc) hipLaunchKernelGGL((fold_chunked_kernel<8, true>), dim3((unsigned)n_waves), dim3(kWave), Geo<8>::lds_bytes(Geo<8>::kAuxSorted), stream, p, t);
-    else hipLaunchKernelGGL((fold_chunked_kernel<8, false>), dim3((unsigned)n_waves), dim3(kWave), Geo<8>::lds_bytes(Geo<8>::kAuxSorted), stream, p, t);
   } else {  // 32-event lanes spill (337 VGPRs): 16 is the widest tile of this kernel
-    if (conc) hipLaunchKernelGGL((fold_chunked_kernel<16, true>), dim3((unsigned)n_waves), dim3(kWave), Geo<16>::lds_bytes(Geo<16>::kAuxSorted), stream, p, t);
-    else hipLaunchKernelGGL((fold_chunked_kernel<16, false>), dim3((unsigned)n_waves), dim3(kWave), Geo<16>::lds_bytes(Geo<16>::kAuxSorted), stream, p, t);
+    for_lane_walk(lane_events, [&](auto w) {
+      using W = decltype(w);
+      hipLaunchKernelGGL((fold_chunked_kernel<W::LE, W::CONC>), dim3((unsigned)n_waves), dim3(kWave), Geo<W::LE>::lds_bytes(Geo<W::LE>::kAuxSorted), stream, p, t);
+    });
   }
-  if (n_cut > 0)
-    hipLaunchKernelGGL(chunk_stitch_kernel, dim3((unsigned)((n_cut + 127) / 128)), dim3(128), 0, stream, p, side, r_slot0, r_c, r_out, n_cut);
+  if (cut.n_cut > 0) launch_stitch(p, cut, stream);
   return hipGetLastError();
 }
 
 // the stitch alone (the tile-major fold, fold_tiled.hip, leaves the same side entries)
-hipError_t launch_chunk_stitch(const FoldParams& p, const uint32_t* side, const int64_t* r_slot0, const uint32_t* r_c, const int64_t* r_out,
-                               int64_t n_cut, hipStream_t stream) {
-  if (n_cut <= 0) return hipSuccess;
-  hipLaunchKernelGGL(chunk_stitch_kernel, dim3((unsigned)((n_cut + 127) / 128)), dim3(128), 0, stream, p, side, r_slot0, r_c, r_out, n_cut);
+hipError_t launch_chunk_stitch(const FoldParams& p, const StitchTable& cut, hipStream_t stream) {
+  if (cut.n_cut <= 0) return hipSuccess;
+  launch_stitch(p, cut, stream);
   return hipGetLastError();
 }
 

@@ -29,14 +29,8 @@
 //     plan kernel from the CSR offsets, so waves never exchange carries through memory: the
 //     running state of a segment that spans tiles is carried in scalar registers.
 //   * No MFMA: this is an HBM-bound fold (16 B in per event, 64 B out per aggregate).
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <vector>
 
 #include "fold_flat_device.h"
 #include "fold_lane_device.h"
@@ -229,144 +223,12 @@ __global__ void __launch_bounds__(256) fold_short_kernel(const FoldParams p) {
   if (mine) store_state(p.out, r, a);
 }
 
-// ---- plan: task k owns segments [lower_bound(off, off[0] + k*T), lower_bound(off, off[0] + (k+1)*T)) ----
-__global__ void plan_kernel(const int64_t* __restrict__ off, int64_t n_seg, int64_t task_events,
-                            int64_t n_tasks, int64_t* __restrict__ plan) {
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k > n_tasks) return;
-  if (k == n_tasks) { plan[k] = n_seg; return; }
-  const int64_t target = off[0] + k * task_events;
-  int64_t lo = 0, hi = n_seg;  // first s in [0, n_seg] with off[s] >= target
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (off[mid] < target) lo = mid + 1; else hi = mid;
-  }
-  plan[k] = lo;
-}
-
-// the same plan over a segment count that only the device knows yet (micro-batches: the group count the device group-by
-// has just produced — no host round trip between the group-by and the fold)
-__global__ void plan_dev_kernel(const int64_t* __restrict__ off, const uint32_t* __restrict__ d_n_seg, int64_t task_events,
-                                int64_t n_tasks, int64_t* __restrict__ plan) {
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k > n_tasks) return;
-  const int64_t n_seg = (int64_t)d_n_seg[0];
-  if (k == n_tasks || n_seg == 0) { plan[k] = n_seg; return; }  // no segments: every task is empty
-  const int64_t target = off[0] + k * task_events;
-  int64_t lo = 0, hi = n_seg;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (off[mid] < target) lo = mid + 1; else hi = mid;
-  }
-  plan[k] = lo;
-}
-
-__global__ void analyze_csr_kernel(const int64_t* __restrict__ off, int64_t n_seg, CsrAnalysis* res) {
-  __shared__ unsigned long long s_empty;
-  __shared__ long long s_max;
-  __shared__ int s_bad, s_nonuni;
-  if (threadIdx.x == 0) { s_empty = 0; s_max = 0; s_bad = 0; s_nonuni = 0; }
-  __syncthreads();
-  const int64_t len0 = n_seg > 0 ? off[1] - off[0] : 0;
-  unsigned long long empty = 0;
-  long long mx = 0;
-  int bad = 0, nonuni = 0;
-  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n_seg; s += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t len = off[s + 1] - off[s];
-    if (len < 0) bad = 1;
-    if (len == 0) ++empty;
-    if (len != len0) nonuni = 1;
-    if (len > mx) mx = len;
-  }
-  if (empty) atomicAdd(&s_empty, empty);
-  if (mx) atomicMax(&s_max, mx);
-  if (bad) atomicOr(&s_bad, 1);
-  if (nonuni) atomicOr(&s_nonuni, 1);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    if (s_empty) atomicAdd((unsigned long long*)&res->n_empty, s_empty);
-    if (s_max) atomicMax((long long*)&res->max_len, s_max);
-    if (s_bad) atomicOr(&res->bad, 1);
-    if (s_nonuni) atomicOr(&res->nonuniform, 1);
-    if (blockIdx.x == 0) {
-      res->len0 = len0;
-      res->first = off[0];
-      res->last = off[n_seg];
-    }
-  }
-}
-
-// Aggregates without events keep their prior snapshot (or stay None).
-__global__ void fill_empty_kernel(const int64_t* __restrict__ off, int64_t n_seg, const uint4* __restrict__ init,
-                                  uint4* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // one 16 B quarter of a state per thread
-  const int64_t s = i >> 2;
-  if (s >= n_seg) return;
-  if (off[s + 1] != off[s]) return;
-  uint4 v;
-  v.x = v.y = v.z = v.w = 0u;
-  if (init) v = init[i];
-  out[i] = v;
-}
-
-constexpr int kCompactBlock = 1024;
-
-__global__ void __launch_bounds__(kCompactBlock) compact_count_kernel(const int64_t* __restrict__ off, int64_t n_seg,
-                                                                       int64_t* __restrict__ block_counts) {
-  __shared__ int s_cnt;
-  if (threadIdx.x == 0) s_cnt = 0;
-  __syncthreads();
-  const int64_t s = (int64_t)blockIdx.x * kCompactBlock + threadIdx.x;
-  const bool nz = s < n_seg && off[s + 1] != off[s];
-  const int c = __popcll(__ballot(nz));
-  if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt, c);
-  __syncthreads();
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = s_cnt;
-}
-
-// single block: exclusive scan of block_counts[0..nb) in place, total appended at [nb]
-__global__ void __launch_bounds__(1024) compact_scan_kernel(int64_t* block_counts, int64_t nb) {
-  __shared__ int64_t s_part[1024];
-  const int tid = threadIdx.x;
-  const int64_t per = (nb + 1023) / 1024;
-  const int64_t b0 = tid * per, b1 = (b0 + per < nb) ? b0 + per : nb;
-  int64_t sum = 0;
-  for (int64_t b = b0; b < b1; ++b) sum += block_counts[b];
-  s_part[tid] = sum;
-  __syncthreads();
-  if (tid == 0) {
-    int64_t run = 0;
-    for (int i = 0; i < 1024; ++i) { const int64_t v = s_part[i]; s_part[i] = run; run += v; }
-    block_counts[nb] = run;
-  }
-  __syncthreads();
-  int64_t run = s_part[tid];
-  for (int64_t b = b0; b < b1; ++b) { const int64_t v = block_counts[b]; block_counts[b] = run; run += v; }
-}
-
-__global__ void __launch_bounds__(kCompactBlock) compact_scatter_kernel(const int64_t* __restrict__ off, int64_t n_seg,
-                                                                         const int64_t* __restrict__ block_counts,
-                                                                         int64_t* __restrict__ nz_off,
-                                                                         int64_t* __restrict__ nz_map) {
-  __shared__ int s_wave[kCompactBlock / 64];
-  const int64_t s = (int64_t)blockIdx.x * kCompactBlock + threadIdx.x;
-  const bool nz = s < n_seg && off[s + 1] != off[s];
-  const unsigned long long bal = __ballot(nz);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) s_wave[wave] = __popcll(bal);
-  __syncthreads();
-  int base = 0;
-  for (int w = 0; w < wave; ++w) base += s_wave[w];
-  if (nz) {
-    const int64_t r = block_counts[blockIdx.x] + base + __popcll(bal & ((1ull << lane) - 1ull));
-    nz_off[r] = off[s];
-    nz_map[r] = s;
-  }
-  const int64_t nb = (n_seg + kCompactBlock - 1) / kCompactBlock;
-  if (blockIdx.x == 0 && threadIdx.x == 0) nz_off[block_counts[nb]] = off[n_seg];
-}
-
 }  // namespace
+
+bool concrete_walk() {
+  static const bool v = [] { const char* e = std::getenv("SURGE_REPLAY_WALK"); return !(e && std::strcmp(e, "transformer") == 0); }();
+  return v;
+}
 
 hipError_t launch_fold_fixed(const FoldParams& p, int64_t n_tasks, int lane_events, hipStream_t stream) {
   if (n_tasks <= 0) return hipSuccess;
@@ -377,19 +239,29 @@ hipError_t launch_fold_fixed(const FoldParams& p, int64_t n_tasks, int lane_even
   return hipGetLastError();
 }
 
+hipError_t launch_fold_flat(const FoldParams& p, const V1Kernels* spec, int64_t n_tasks, int lane_events, hipStream_t stream) {
+  if (n_tasks <= 0) return hipSuccess;
+  if (spec) {  // no op table in LDS: the tile and the head bitmask only
+    const unsigned lds = lane_events == 8 ? Geo<8>::kTileBytes + Geo<8>::kAuxFlat : Geo<16>::kTileBytes + Geo<16>::kAuxFlat;
+    return launch_module_kernel(lane_events == 8 ? spec->flat8 : spec->flat16, n_tasks, lds, stream, &p, sizeof(p));
+  }
+  if (lane_events == 8)
+    hipLaunchKernelGGL((fold_kernel<MODE_FLAT, 8>), dim3((unsigned)n_tasks), dim3(kWave), Geo<8>::lds_bytes(Geo<8>::kAuxFlat), stream, p);
+  else
+    hipLaunchKernelGGL((fold_kernel<MODE_FLAT, 16>), dim3((unsigned)n_tasks), dim3(kWave), Geo<16>::lds_bytes(Geo<16>::kAuxFlat), stream, p);
+  return hipGetLastError();
+}
+
 hipError_t launch_fold_rows(const FoldParams& p, const V1Kernels* spec, int64_t n_tasks, int lane_events, hipStream_t stream) {
   if (n_tasks <= 0) return hipSuccess;
-  if (spec && lane_events != 32) return launch_v1_lane(lane_events == 8 ? spec->rows8 : spec->rows16, &p, sizeof(p), n_tasks, 0, stream);
-  static const bool conc = [] { const char* e = std::getenv("SURGE_REPLAY_WALK"); return !(e && std::strcmp(e, "transformer") == 0); }();
+  if (spec && lane_events != 32) return launch_module_kernel(lane_events == 8 ? spec->rows8 : spec->rows16, n_tasks, 0, stream, &p, sizeof(p));
   // LDS is static in the kernel
-  if (lane_events == 8) {
-    if (conc) hipLaunchKernelGGL((fold_rows_kernel<8, true>), dim3((unsigned)n_tasks), dim3(kWave), 0, stream, p);
-    else hipLaunchKernelGGL((fold_rows_kernel<8, false>), dim3((unsigned)n_tasks), dim3(kWave), 0, stream, p);
-  } else if (lane_events == 32) {
+  if (lane_events == 32) {
     hipLaunchKernelGGL((fold_rows_kernel<32, false>), dim3((unsigned)n_tasks), dim3(kWave), 0, stream, p);
   } else {
-    if (conc) hipLaunchKernelGGL((fold_rows_kernel<16, true>), dim3((unsigned)n_tasks), dim3(kWave), 0, stream, p);
-    else hipLaunchKernelGGL((fold_rows_kernel<16, false>), dim3((unsigned)n_tasks), dim3(kWave), 0, stream, p);
+    for_lane_walk(lane_events, [&](auto w) {
+      hipLaunchKernelGGL((fold_rows_kernel<decltype(w)::LE, decltype(w)::CONC>), dim3((unsigned)n_tasks), dim3(kWave), 0, stream, p);
+    });
   }
   return hipGetLastError();
 }
@@ -408,286 +280,6 @@ hipError_t launch_fold_sorted(const FoldParams& p, int64_t n_waves, int lane_eve
     hipLaunchKernelGGL((fold_sorted_kernel<32>), dim3((unsigned)n_waves), dim3(kWave), Geo<32>::lds_bytes(Geo<32>::kAuxSorted), stream, p);
   else
     hipLaunchKernelGGL((fold_sorted_kernel<16>), dim3((unsigned)n_waves), dim3(kWave), Geo<16>::lds_bytes(Geo<16>::kAuxSorted), stream, p);
-  return hipGetLastError();
-}
-
-// ---- the flat kernel compiled for one v1 schema (hiprtc) ---------------------------------------------------------------
-// What fold_slots.hip does for ABI v2, for the op table of ABI v1: the kernel's own device source (fold_flat_device.h),
-// compiled once per distinct op table and process with the table's words as compile-time masks (fold_device.h,
-// SURGE_V1_SPEC).  The flat kernel is the one of the v1 folds that is bound by its instruction stream (lane transformers:
-// ~97 VALU instructions per event against 55 in the lane-per-aggregate kernels); the others run at the transport's pace.
-namespace {
-
-struct V1Masks {
-  uint32_t word[kTableWords];  // [k] bit e: word k of entry e is non-zero (k < 15)
-  uint32_t throws, deletes;    // TW_FLAGS bit 0 / bit 16 per entry
-};
-
-// false: a word holds something a bit per entry cannot express (not an op table fill_params writes)
-bool v1_masks(const uint32_t (*table)[kTableWords], V1Masks* m) {
-  std::memset(m, 0, sizeof(*m));
-  for (int e = 0; e < kTableEntries; ++e) {
-    for (int k = 0; k < TW_FLAGS; ++k) {
-      const uint32_t w = table[e][k];
-      if (w != 0u && w != (k == TW_EVC ? 1u : ~0u)) return false;
-      if (w) m->word[k] |= 1u << e;
-    }
-    const uint32_t f = table[e][TW_FLAGS];
-    if (f & ~0x10001u) return false;
-    if (f & 1u) m->throws |= 1u << e;
-    if (f & 0x10000u) m->deletes |= 1u << e;
-  }
-  return true;
-}
-
-std::mutex g_v1_mu;
-std::map<std::string, std::unique_ptr<V1Kernels>> g_v1_cache;  // key: kind + device + masks; entries live as long as the process
-std::map<std::string, std::string> g_v1_failed;
-
-}  // namespace
-
-// The program handed to hiprtc for one op table: the masks, then either the flat kernel (V1_FLAT: fold_flat_device.h — K3
-// appends, AUTO on logs of few long rows) or the lane-per-row kernels (V1_LANES: fold_lane_device.h — SORTED, CHUNKED, ROWS).
-// Two programs, not one: a handle that only ever appends micro-batches never pays for the lane kernels' compile and the
-// other way round; each is cached on disk by its text (rtc.cpp).
-std::string v1_spec_source(const uint32_t (*table)[kTableWords], int kind) {
-  V1Masks m;
-  if (!v1_masks(table, &m)) return std::string();
-  std::string s = "#define SURGE_V1_SPEC 1\n#define SURGE_V1_MASK(k) (";
-  char b[64];
-  for (int k = 0; k < TW_FLAGS; ++k) {
-    std::snprintf(b, sizeof b, "(k) == %d ? 0x%xu : ", k, m.word[k]);
-    s += b;
-  }
-  s += "0u)\n";
-  std::snprintf(b, sizeof b, "#define SURGE_V1_THROWS 0x%xu\n", m.throws);
-  s += b;
-  std::snprintf(b, sizeof b, "#define SURGE_V1_DELETES 0x%xu\n", m.deletes);
-  s += b;
-#ifdef SURGE_EXPERIMENTS  // experiment builds of the library only (scripts/build_experiments_lib.py): extra #defines for the program, "A=1;B=2"
-  if (const char* extra = std::getenv("SURGE_REPLAY_RTC_EXTRA")) {
-    std::string e = extra;
-    size_t pos = 0;
-    while (pos < e.size()) {
-      size_t semi = e.find(';', pos);
-      if (semi == std::string::npos) semi = e.size();
-      std::string d = e.substr(pos, semi - pos);
-      const size_t eq = d.find('=');
-      if (!d.empty()) s += "#define " + (eq == std::string::npos ? d : d.substr(0, eq) + " " + d.substr(eq + 1)) + "\n";
-      pos = semi + 1;
-    }
-  }
-#endif
-  if (kind == V1_FLAT) {
-    s += R"SRC(
-#include "fold_flat_device.h"
-using namespace surge;
-extern "C" __global__ void __launch_bounds__(64) surge_v1_flat8(const FoldParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  fold_flat_body<MODE_FLAT, 8>(p, smem);
-}
-extern "C" __global__ void __launch_bounds__(64) surge_v1_flat16(const FoldParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  fold_flat_body<MODE_FLAT, 16>(p, smem);
-}
-)SRC";
-  } else {
-    // (register budgets as in fold_chunked.hip: two waves per SIMD with 16 KiB tiles, three with 8 KiB tiles)
-    s += R"SRC(
-#include "fold_lane_device.h"
-using namespace surge;
-extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) surge_v1_sorted8(const FoldParams p) {
-  ChunkTable t;
-  t.v_start = nullptr; t.v_len = nullptr; t.v_info = nullptr; t.v_dest = nullptr; t.n_vrows = 0; t.side = nullptr;
-  chunk_walk<8, true, true>(p, t);
-}
-extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) surge_v1_sorted16(const FoldParams p) {
-  ChunkTable t;
-  t.v_start = nullptr; t.v_len = nullptr; t.v_info = nullptr; t.v_dest = nullptr; t.n_vrows = 0; t.side = nullptr;
-  chunk_walk<16, true, true>(p, t);
-}
-extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1))) surge_v1_sorted32(const FoldParams p) {
-  ChunkTable t;
-  t.v_start = nullptr; t.v_len = nullptr; t.v_info = nullptr; t.v_dest = nullptr; t.n_vrows = 0; t.side = nullptr;
-  chunk_walk<32, true, true>(p, t);
-}
-extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) surge_v1_chunked8(const ChunkArgs a) {
-  chunk_walk<8, false, true>(a.p, a.t);
-}
-extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) surge_v1_chunked16(const ChunkArgs a) {
-  chunk_walk<16, false, true>(a.p, a.t);
-}
-extern "C" __global__ void __launch_bounds__(64) surge_v1_rows8(const FoldParams p) {
-  __shared__ __attribute__((aligned(16))) char lds_ev[Geo<8>::kTileBytes];
-  fold_rows_body<8, true>(p, lds_ev, nullptr);
-}
-extern "C" __global__ void __launch_bounds__(64) surge_v1_rows16(const FoldParams p) {
-  __shared__ __attribute__((aligned(16))) char lds_ev[Geo<16>::kTileBytes];
-  fold_rows_body<16, true>(p, lds_ev, nullptr);
-}
-)SRC";
-  }
-  return s;
-}
-
-void v1_kernels_acquire(const uint32_t (*table)[kTableWords], int device, int kind, V1Kernels** out, double* compile_ms, std::string* why) {
-  *out = nullptr;
-  *compile_ms = 0.0;
-  if (const char* v = std::getenv("SURGE_REPLAY_RTC")) {
-    if (std::atoi(v) == 0) {
-      *why = "disabled by SURGE_REPLAY_RTC=0";
-      return;
-    }
-  }
-  if (kind == V1_LANES) {
-    // Opt-in (SURGE_REPLAY_RTC_LANES=1).  Measured in round 6 on the 10 M-aggregate log, one box, A/B/A
-    // (profiles/r06_lane_spec_*.jsonl): SORTED takes 12.2 ms whatever its walk costs — compiled for the built-in schema (53 VALU
-    // per event), for the Counter fixture's own schema (20), or with the arithmetic REMOVED (an experiment build that only moves
-    // the events): 12.19 / 12.22 / 12.20 ms, at 8- and 16-event lanes, from six resident waves per CU up.  The kernel runs at
-    // the pace of its transport — 64 row pieces per load instruction, gathered from anywhere in the log — not of its
-    // instruction stream; compiling the walk buys nothing there (CHUNKED on one GPU's C4 shard: -1 %; ROWS on C2: +1.5 %).
-    // So the default stays the ahead-of-time kernels; the compiled ones are kept, fuzzed against the oracle, for hosts whose
-    // schemas or shapes differ.  (Their first version was 13 - 29 % SLOWER: hiprtc's compiler puts an s_waitcnt vmcnt(0) in front
-    // of every LDS read that follows an LDS-DMA load, which serialised the sixteen loads of a tile — fold_lane_device.h, issue().)
-    const char* v = std::getenv("SURGE_REPLAY_RTC_LANES");
-    if (!v || std::atoi(v) == 0) {
-      *why = "off (SURGE_REPLAY_RTC_LANES=1 compiles them)";
-      return;
-    }
-  }
-  V1Masks m;
-  if (!v1_masks(table, &m)) {
-    *why = "the op table holds words the specialised build cannot express";
-    return;
-  }
-  std::string key((const char*)&m, sizeof(m));
-  key += "@" + std::to_string(device) + "/" + std::to_string(kind);
-#ifdef SURGE_EXPERIMENTS
-  if (const char* extra = std::getenv("SURGE_REPLAY_RTC_EXTRA")) key += std::string("+") + extra;
-#endif
-  std::lock_guard<std::mutex> lk(g_v1_mu);
-  auto hit = g_v1_cache.find(key);
-  if (hit != g_v1_cache.end()) {
-    *out = hit->second.get();
-    *compile_ms = hit->second->compile_ms;
-    return;
-  }
-  auto miss = g_v1_failed.find(key);
-  if (miss != g_v1_failed.end()) {
-    *why = miss->second;
-    return;
-  }
-  auto give_up = [&](const std::string& msg) {
-    g_v1_failed[key] = msg;
-    *why = msg;
-  };
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess) return give_up("hipGetDeviceProperties failed");
-  std::string arch = prop.gcnArchName;  // "gfx950:sramecc+:xnack-"
-  const size_t colon = arch.find(':');
-  if (colon != std::string::npos) arch.resize(colon);
-  std::vector<char> code;
-  std::string log;
-  double ms = 0.0;
-  if (!rtc_compile(v1_spec_source(table, kind), arch.c_str(), &code, &log, &ms)) return give_up(log);
-  auto k = std::make_unique<V1Kernels>();
-  k->device = device;
-  k->compile_ms = ms;
-  hipError_t e = hipModuleLoadData(&k->module, code.data());
-  if (e != hipSuccess) return give_up(std::string("hipModuleLoadData: ") + hipGetErrorString(e));
-  struct Fn { hipFunction_t* f; const char* name; };
-  std::vector<Fn> fns;
-  if (kind == V1_FLAT) fns = {{&k->flat8, "surge_v1_flat8"}, {&k->flat16, "surge_v1_flat16"}};
-  else fns = {{&k->sorted8, "surge_v1_sorted8"}, {&k->sorted16, "surge_v1_sorted16"}, {&k->sorted32, "surge_v1_sorted32"}, {&k->chunked8, "surge_v1_chunked8"},
-              {&k->chunked16, "surge_v1_chunked16"}, {&k->rows8, "surge_v1_rows8"}, {&k->rows16, "surge_v1_rows16"}};
-  for (auto& f : fns) {
-    e = hipModuleGetFunction(f.f, k->module, f.name);
-    if (e != hipSuccess) {
-      (void)hipModuleUnload(k->module);
-      return give_up(std::string("hipModuleGetFunction(") + f.name + "): " + hipGetErrorString(e));
-    }
-  }
-  *compile_ms = ms;
-  *out = k.get();
-  g_v1_cache[key] = std::move(k);
-}
-
-// one launch of a kernel of a V1_LANES / V1_FLAT module: the argument block by value
-hipError_t launch_v1_lane(hipFunction_t fn, const void* args, size_t args_bytes, int64_t grid, unsigned lds, hipStream_t stream) {
-  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, const_cast<void*>(args), HIP_LAUNCH_PARAM_BUFFER_SIZE, &args_bytes, HIP_LAUNCH_PARAM_END};
-  return hipModuleLaunchKernel(fn, (unsigned)grid, 1, 1, kWave, 1, 1, lds, stream, nullptr, config);
-}
-
-hipFunction_t v1_lane_fn(const V1Kernels* k, int which, int lane_events) {
-  if (!k) return nullptr;
-  if (which == 0) return lane_events == 8 ? k->sorted8 : k->sorted16;
-  if (which == 1) return lane_events == 8 ? k->chunked8 : k->chunked16;
-  return lane_events == 8 ? k->rows8 : k->rows16;
-}
-
-hipError_t launch_fold_flat(const FoldParams& p, const V1Kernels* spec, int64_t n_tasks, int lane_events, hipStream_t stream) {
-  if (n_tasks <= 0) return hipSuccess;
-  if (spec) {  // no op table in LDS: the tile and the head bitmask only
-    FoldParams args = p;
-    size_t args_bytes = sizeof(args);
-    void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &args_bytes, HIP_LAUNCH_PARAM_END};
-    const unsigned lds = lane_events == 8 ? Geo<8>::kTileBytes + Geo<8>::kAuxFlat : Geo<16>::kTileBytes + Geo<16>::kAuxFlat;
-    return hipModuleLaunchKernel(lane_events == 8 ? spec->flat8 : spec->flat16, (unsigned)n_tasks, 1, 1, kWave, 1, 1, lds, stream, nullptr, config);
-  }
-  if (lane_events == 8)
-    hipLaunchKernelGGL((fold_kernel<MODE_FLAT, 8>), dim3((unsigned)n_tasks), dim3(kWave), Geo<8>::lds_bytes(Geo<8>::kAuxFlat), stream, p);
-  else
-    hipLaunchKernelGGL((fold_kernel<MODE_FLAT, 16>), dim3((unsigned)n_tasks), dim3(kWave), Geo<16>::lds_bytes(Geo<16>::kAuxFlat), stream, p);
-  return hipGetLastError();
-}
-
-hipError_t launch_plan(const int64_t* off, int64_t n_seg, int64_t task_events, int64_t n_tasks, int64_t* plan,
-                       hipStream_t stream) {
-  const int64_t n = n_tasks + 1;
-  hipLaunchKernelGGL(plan_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, off, n_seg, task_events,
-                     n_tasks, plan);
-  return hipGetLastError();
-}
-
-hipError_t launch_plan_dev(const int64_t* off, const uint32_t* d_n_seg, int64_t task_events, int64_t n_tasks, int64_t* plan,
-                           hipStream_t stream) {
-  const int64_t n = n_tasks + 1;
-  hipLaunchKernelGGL(plan_dev_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, off, d_n_seg, task_events, n_tasks, plan);
-  return hipGetLastError();
-}
-
-hipError_t launch_analyze_csr(const int64_t* off, int64_t n_seg, CsrAnalysis* d_result, hipStream_t stream) {
-  hipError_t e = hipMemsetAsync(d_result, 0, sizeof(CsrAnalysis), stream);
-  if (e != hipSuccess) return e;
-  int64_t blocks = (n_seg + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(analyze_csr_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, off, n_seg, d_result);
-  return hipGetLastError();
-}
-
-hipError_t launch_fill_empty(const int64_t* off, int64_t n_seg, const uint4* init, uint4* out, hipStream_t stream) {
-  if (n_seg <= 0) return hipSuccess;
-  const int64_t n = n_seg * 4;
-  hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, off, n_seg, init, out);
-  return hipGetLastError();
-}
-
-// in-place exclusive scan of v[0..n) with the total appended at v[n] (single block: index-time use only)
-hipError_t launch_exclusive_scan_i64(int64_t* v, int64_t n, hipStream_t stream) {
-  if (n < 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, stream, v, n);
-  return hipGetLastError();
-}
-
-hipError_t launch_compact_nonempty(const int64_t* off, int64_t n_seg, int64_t* d_block_counts, int64_t* nz_off,
-                                   int64_t* nz_map, hipStream_t stream) {
-  if (n_seg <= 0) return hipSuccess;
-  const int64_t nb = (n_seg + kCompactBlock - 1) / kCompactBlock;
-  hipLaunchKernelGGL(compact_count_kernel, dim3((unsigned)nb), dim3(kCompactBlock), 0, stream, off, n_seg, d_block_counts);
-  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, stream, d_block_counts, nb);
-  hipLaunchKernelGGL(compact_scatter_kernel, dim3((unsigned)nb), dim3(kCompactBlock), 0, stream, off, n_seg,
-                     d_block_counts, nz_off, nz_map);
   return hipGetLastError();
 }
 

@@ -1,14 +1,9 @@
 // fold_slots.hip — the fold of ABI v2 "slot" schemas (include/surge_replay.h): the kernels' device code lives in
 // fold_slots_device.h (read its header comment first); this file instantiates the GENERIC INTERPRETER ahead of time,
-// and builds, caches and launches the SCHEMA-SPECIALISED kernels that hiprtc compiles from the same source when a v2
-// handle is created (rtc.cpp).
+// and writes the program of, and launches, the SCHEMA-SPECIALISED kernels that hiprtc compiles from the same source when a
+// v2 handle is created (rtc.cpp compiles, rtc_module.hip loads and caches).
 #include <cstdio>
-#include <cstring>
-#include <map>
-#include <memory>
-#include <mutex>
 #include <string>
-#include <vector>
 
 #include "fold_slots_device.h"
 
@@ -61,13 +56,6 @@ void slot_params_from_schema(const surge_replay_schema_v2& sc, SlotParams* out) 
 }
 
 // ---- the schema-specialised build ---------------------------------------------------------------------------------
-struct SlotKernels {
-  hipModule_t module = nullptr;
-  hipFunction_t csr8 = nullptr, csr16 = nullptr, tiled1 = nullptr, tiled2 = nullptr;
-  int device = 0;
-  double compile_ms = 0.0;
-};
-
 // The program handed to hiprtc: the ABI constants the device code names, the schema as SURGE_SPEC_* macros (ternary
 // chains over an index that is a constant after unrolling), the shared device header, four extern "C" entry points.
 std::string slots_spec_source(const SlotParams& sp) {
@@ -133,93 +121,21 @@ extern "C" __global__ void __launch_bounds__(64) surge_slots_tiled2(const FoldPa
   return s;
 }
 
-namespace {
-
-std::mutex g_spec_mu;
-// key: device + the SlotParams bytes (everything the generated source depends on); entries live as long as the process
-// (a handful of schemas per host; a module is a few tens of KB)
-std::map<std::string, std::unique_ptr<SlotKernels>> g_spec_cache;
-std::map<std::string, std::string> g_spec_failed;  // key -> why (never retried: the answer will not change)
-
-}  // namespace
-
-void slot_kernels_acquire(const surge_replay_schema_v2& sc, const SlotParams& sp, int device, SlotKernels** out, double* compile_ms,
-                          std::string* why) {
-  (void)sc;
-  *out = nullptr;
-  *compile_ms = 0.0;
-  if (const char* v = std::getenv("SURGE_REPLAY_RTC")) {
-    if (std::atoi(v) == 0) {
-      *why = "disabled by SURGE_REPLAY_RTC=0";
-      return;
-    }
-  }
-  std::string key((const char*)&sp, sizeof(sp));
-  key += "@" + std::to_string(device);
-  std::lock_guard<std::mutex> lk(g_spec_mu);
-  auto hit = g_spec_cache.find(key);
-  if (hit != g_spec_cache.end()) {
-    *out = hit->second.get();
-    *compile_ms = hit->second->compile_ms;
-    return;
-  }
-  auto miss = g_spec_failed.find(key);
-  if (miss != g_spec_failed.end()) {
-    *why = miss->second;
-    return;
-  }
-  auto give_up = [&](const std::string& m) {
-    g_spec_failed[key] = m;
-    *why = m;
-  };
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) != hipSuccess) return give_up("hipGetDeviceProperties failed");
-  std::string arch = prop.gcnArchName;  // "gfx950:sramecc+:xnack-"
-  const size_t colon = arch.find(':');
-  if (colon != std::string::npos) arch.resize(colon);
-  std::vector<char> code;
-  std::string log;
-  double ms = 0.0;
-  if (!rtc_compile(slots_spec_source(sp), arch.c_str(), &code, &log, &ms)) return give_up(log);
-  auto k = std::make_unique<SlotKernels>();
-  k->device = device;
-  k->compile_ms = ms;
-  hipError_t e = hipModuleLoadData(&k->module, code.data());
-  if (e != hipSuccess) return give_up(std::string("hipModuleLoadData: ") + hipGetErrorString(e));
-  struct { hipFunction_t* f; const char* name; int lds; } fns[] = {
-      {&k->csr8, "surge_slots_csr8", Geo<8>::lds_bytes(Geo<8>::kAuxSorted)},
-      {&k->csr16, "surge_slots_csr16", Geo<16>::lds_bytes(Geo<16>::kAuxSorted)},
-      {&k->tiled1, "surge_slots_tiled1", 0},
-      {&k->tiled2, "surge_slots_tiled2", 0}};
-  for (auto& f : fns) {
-    e = hipModuleGetFunction(f.f, k->module, f.name);
-    if (e != hipSuccess) {
-      (void)hipModuleUnload(k->module);
-      return give_up(std::string("hipModuleGetFunction(") + f.name + "): " + hipGetErrorString(e));
-    }
-  }
-  *compile_ms = ms;
-  *out = k.get();
-  g_spec_cache[key] = std::move(k);
+// key: the SlotParams bytes — everything the generated source depends on
+bool slot_kernels_acquire(const SlotParams& sp, int device, SlotKernels* out, std::string* why) {
+  const RtcModule* mod = rtc_module_acquire("v2slots:" + std::string((const char*)&sp, sizeof(sp)), device, [&] { return slots_spec_source(sp); },
+                                            {"surge_slots_csr8", "surge_slots_csr16", "surge_slots_tiled1", "surge_slots_tiled2"}, why);
+  if (!mod) return false;
+  out->csr8 = mod->fn[0]; out->csr16 = mod->fn[1]; out->tiled1 = mod->fn[2]; out->tiled2 = mod->fn[3];
+  out->compile_ms = mod->compile_ms;
+  return true;
 }
-
-namespace {
-
-hipError_t launch_module_kernel(hipFunction_t f, unsigned grid, unsigned lds, hipStream_t stream, void* args, size_t args_bytes) {
-  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &args_bytes, HIP_LAUNCH_PARAM_END};
-  return hipModuleLaunchKernel(f, grid, 1, 1, kWave, 1, 1, lds, stream, nullptr, config);
-}
-
-}  // namespace
 
 hipError_t launch_fold_slots(const FoldParams& p, const SlotParams& sp, const SlotKernels* spec, int64_t n_waves, int lane_events,
                              hipStream_t stream) {
   if (n_waves <= 0) return hipSuccess;
   const unsigned lds = lane_events == 8 ? Geo<8>::lds_bytes(Geo<8>::kAuxSorted) : Geo<16>::lds_bytes(Geo<16>::kAuxSorted);
-  if (spec) {
-    FoldParams args = p;
-    return launch_module_kernel(lane_events == 8 ? spec->csr8 : spec->csr16, (unsigned)n_waves, lds, stream, &args, sizeof(args));
-  }
+  if (spec) return launch_module_kernel(lane_events == 8 ? spec->csr8 : spec->csr16, n_waves, lds, stream, &p, sizeof(p));
   if (lane_events == 8)
     hipLaunchKernelGGL((fold_slots_kernel<8>), dim3((unsigned)n_waves), dim3(kWave), lds, stream, p, sp);
   else
@@ -235,7 +151,7 @@ hipError_t launch_fold_slots_tiled(const FoldParams& p, const SlotParams& sp, co
     static_assert(sizeof(FoldParams) % 8 == 0, "TileTable must follow FoldParams without padding");
     args.p = p;
     args.t = t;
-    return launch_module_kernel(subs == 1 ? spec->tiled1 : spec->tiled2, (unsigned)n_waves, 0, stream, &args, sizeof(args));
+    return launch_module_kernel(subs == 1 ? spec->tiled1 : spec->tiled2, n_waves, 0, stream, &args, sizeof(args));
   }
   if (subs == 1)
     hipLaunchKernelGGL((fold_slots_tiled_kernel<1>), dim3((unsigned)n_waves), dim3(kWave), 0, stream, p, t, sp);

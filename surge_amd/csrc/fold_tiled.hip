@@ -288,13 +288,8 @@ hipError_t launch_relayout(const uint4* events, const int64_t* v_start, const ui
   return hipGetLastError();
 }
 
-hipError_t launch_fold_tiled(const FoldParams& p, const uint4* tiles, const int64_t* g_sub0, const uint32_t* v_len,
-                             const uint32_t* v_info, const int64_t* v_dest, int64_t n_vrows, uint32_t* side, int64_t n_waves, int subs,
-                             hipStream_t stream) {
-  if (n_waves <= 0 || n_vrows <= 0) return hipSuccess;
-  TileTable t;
-  t.tiles = tiles; t.g_sub0 = g_sub0; t.v_len = v_len; t.v_info = v_info; t.v_dest = v_dest;
-  t.n_vrows = n_vrows; t.side = side;
+hipError_t launch_fold_tiled(const FoldParams& p, const TileTable& t, int64_t n_waves, int subs, hipStream_t stream) {
+  if (n_waves <= 0 || t.n_vrows <= 0) return hipSuccess;
   if (subs == 1)
     hipLaunchKernelGGL((fold_tiled_kernel<1>), dim3((unsigned)n_waves), dim3(kWave), 0, stream, p, t);
   else

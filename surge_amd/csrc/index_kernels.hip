@@ -122,14 +122,13 @@ hipError_t launch_chunk_count(const int64_t* off, int64_t n_seg, uint32_t T, boo
   return launch_exclusive_scans_i64(cnt, stride, stride, 3, scan_scratch, stream);  // (scan_i64_scratch_bytes(stride, 3) bytes)
 }
 
-// Phase 2: rows in aggregate order (u_*), sorted by length (longest first, stable), gathered into v_*
-hipError_t launch_chunk_table(const int64_t* off, int64_t n_seg, const int64_t* out_map, uint32_t T, bool align, const int64_t* cnt,
-                              int64_t n_vrows, const IndexScratch& sc, int64_t* u_start, uint32_t* u_len, uint32_t* u_info, int64_t* u_dest,
-                              int64_t* v_start, uint32_t* v_len, uint32_t* v_info, int64_t* v_dest, int64_t* r_slot0, uint32_t* r_c,
-                              int64_t* r_out, hipStream_t stream) {
+// Phase 2: rows in aggregate order (u), sorted by length (longest first, stable), gathered into v
+hipError_t launch_chunk_table(const KernelCsr& csr, uint32_t T, bool align, const int64_t* cnt, const IndexScratch& sc, const ChunkRows& u,
+                              const ChunkRows& v, const StitchTable& cut, hipStream_t stream) {
+  const int64_t n_seg = csr.n_seg, n_vrows = v.n_vrows;
   if (n_seg <= 0 || n_vrows <= 0) return hipSuccess;
-  hipLaunchKernelGGL(chunk_emit_kernel, dim3((unsigned)((n_seg + 255) / 256)), dim3(256), 0, stream, off, n_seg, out_map, T, align, cnt,
-                     n_seg + 1, u_start, u_len, u_info, u_dest, sc.keys_a, sc.vals_a, r_slot0, r_c, r_out);
+  hipLaunchKernelGGL(chunk_emit_kernel, dim3((unsigned)((n_seg + 255) / 256)), dim3(256), 0, stream, csr.off, n_seg, csr.out_map, T, align, cnt,
+                     n_seg + 1, u.v_start, u.v_len, u.v_info, u.v_dest, sc.keys_a, sc.vals_a, cut.r_slot0, cut.r_c, cut.r_out);
   hipError_t e;
   if (sc.counting) {
     e = launch_count_sort_desc(sc.keys_a, nullptr, n_vrows, sc.max_key, sc.n_cus, sc.temp, sc.vals_b, stream);
@@ -137,8 +136,8 @@ hipError_t launch_chunk_table(const int64_t* off, int64_t n_seg, const int64_t* 
     e = launch_radix_sort_pairs_desc(sc.temp, sc.temp_bytes, sc.keys_a, sc.keys_b, sc.vals_a, sc.vals_b, n_vrows, stream);
   }
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(chunk_gather_kernel, dim3((unsigned)((n_vrows + 255) / 256)), dim3(256), 0, stream, sc.vals_b, n_vrows, u_start, u_len,
-                     u_info, u_dest, v_start, v_len, v_info, v_dest);
+  hipLaunchKernelGGL(chunk_gather_kernel, dim3((unsigned)((n_vrows + 255) / 256)), dim3(256), 0, stream, sc.vals_b, n_vrows, u.v_start, u.v_len,
+                     u.v_info, u.v_dest, v.v_start, v.v_len, v.v_info, v.v_dest);
   return hipGetLastError();
 }
 
