@@ -8,7 +8,8 @@
  * message format v2 / KIP-98; LZ4 frame format — "parity unpinned"):
  *   - RecordBatch v2 framing, CRC-32C over [attributes .. end], zig-zag varint records
  *   - compression.type = lz4 (the reference's producer setting,
- *     modules/common/src/main/resources/reference.conf:112) and none
+ *     modules/common/src/main/resources/reference.conf:112), snappy (raw blocks, alone or in snappy-java's framing: what a
+ *     producer, broker or mirror configured for it writes) and none; gzip and zstd are refused
  *   - isolation.level = read_committed (modules/common/src/main/scala/surge/kafka/streams/
  *     SurgeStateStoreConsumer.scala:38): transactional batches are held back until their producer's
  *     COMMIT / ABORT control marker; aborted ones are dropped; nothing after an open transaction is
@@ -151,7 +152,10 @@ int32_t surge_ingest_drain_json(surge_ingest* g, int64_t max, const surge_event_
 #define SURGE_INGEST_FRAMES     0x100 /* OR into surge_ingest_create's isolation_level */
 #define SURGE_INGEST_DEVICE_LZ4 0x200 /* FRAMES, and lz4 batches keep their LZ4 frame: the device decoder decodes the blocks on the
                                          GPU (one wave per 64 KiB block, assembled in LDS); frames kafka-clients would not write —
-                                         blocks above 64 KiB, dependent blocks — it decompresses on the host                       */
+                                         blocks above 64 KiB, dependent blocks — it decompresses on the host.  snappy batches keep
+                                         their chunks the same way (section codec 2): one wave parses a chunk, the LZ4 stage's second
+                                         pass applies its copies; chunks above 64 KiB or off the 16-byte grid go through the host    */
+#define SURGE_INGEST_DEVICE_DECOMPRESS SURGE_INGEST_DEVICE_LZ4 /* the same bit by the name of what it has come to mean                */
 #define SURGE_INGEST_DEVICE_CRC 0x400 /* FRAMES, and a data batch's CRC-32C is verified ON THE DEVICE: the host checksums only the 40
                                          header bytes the CRC covers in front of the records section (the state of the CRC register
                                          after them travels with the section), the device decoder continues over the section's bytes
@@ -174,7 +178,8 @@ typedef struct surge_batch_section {
   int64_t byte_len;
   int64_t base_offset; /* Kafka offset of the batch's first record                                     */
   int32_t n_records;
-  int32_t codec;       /* low byte 0: the records themselves; 3: one LZ4 frame that holds them (SURGE_INGEST_DEVICE_LZ4);
+  int32_t codec;       /* low byte 0: the records themselves; 3: one LZ4 frame that holds them, 2: snappy chunks or one raw
+                          snappy block (SURGE_INGEST_DEVICE_LZ4);
                           | SURGE_SECTION_CRC_PENDING                                                             */
 } surge_batch_section;
 /* Pops up to max deliverable batches (committed / non-transactional, before any open transaction), in offset order.
@@ -578,6 +583,11 @@ int32_t surge_device_decoder_counters(const surge_device_decoder* d, int64_t out
  * the push runs again; after four functions in a row the push fails with SURGE_E_UNSUPPORTED — [5] slots of the key table,
  * [6] pushes that delivered, [7] the hash function in use (0 = the first). */
 int32_t surge_device_decoder_stats(const surge_device_decoder* d, int64_t out[8]);
+/* What stands behind those eight (their positions do not move, and a caller's array of eight is never overrun): the routes
+ * compressed sections took — [0] snappy chunks decoded on the device, [1] snappy sections decompressed on the host (a chunk
+ * above 64 KiB, a chunk but the last that is no multiple of 16 bytes, a raw block above 64 KiB), both of the pushes that
+ * delivered. */
+int32_t surge_device_decoder_route_stats(const surge_device_decoder* d, int64_t out[2]);
 
 /* Key table: aggregate ids in first-DELIVERED order (a key is interned when its record is drained, so the
  * keys of aborted or still-open transactions never appear). */
@@ -600,6 +610,16 @@ int64_t surge_lz4_frame_bound(int64_t n);
 int64_t surge_lz4_frame_compress(const uint8_t* src, int64_t n, uint8_t* dst, int64_t dst_cap);
 /* XXH32 (the frame's header checksum is its second byte over the descriptor). */
 uint32_t surge_xxh32(const uint8_t* data, int64_t len, uint32_t seed);
+/* snappy, reading only (surge_amd/csrc/snappy_block.h).  One raw block: its preamble's length, and the block into dst.  A
+ * records section — snappy-java's framing (magic, version pair, [int32 BE length][raw block] chunks) or, without the magic,
+ * one raw block: the sum of its preambles (nothing decoded), and the section into dst.  Each returns the size, or -1 (bad
+ * argument), -6 (dst too small) or SURGE_E_CORRUPT; *status_out (nullable) then says which refusal it was, by the number
+ * surge_snappy_status_name gives a text for (0 = none). */
+int64_t surge_snappy_uncompressed_length(const uint8_t* src, int64_t src_len, int32_t* status_out);
+int64_t surge_snappy_uncompress(const uint8_t* src, int64_t src_len, uint8_t* dst, int64_t dst_cap, int32_t* status_out);
+int64_t surge_snappy_frame_bound(const uint8_t* src, int64_t src_len, int32_t* status_out);
+int64_t surge_snappy_frame_decompress(const uint8_t* src, int64_t src_len, uint8_t* dst, int64_t dst_cap, int32_t* status_out);
+const char* surge_snappy_status_name(int32_t status);
 
 #ifdef __cplusplus
 }

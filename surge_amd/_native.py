@@ -176,6 +176,7 @@ INGEST_H = {
     "surge_device_decoder_key_order": ([_vp, ctypes.POINTER(_vp), ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _i32),
     "surge_device_decoder_counters": ([_vp, ctypes.POINTER(_i64 * 4)], _i32),
     "surge_device_decoder_stats": ([_vp, ctypes.POINTER(_i64 * 8)], _i32),
+    "surge_device_decoder_route_stats": ([_vp, ctypes.POINTER(_i64 * 2)], _i32),
     "surge_event_json_validate": ([_vp], _i32),
     "surge_event_json_decode": ([_vp, _vp, _i64, _vp], _i32),
     "surge_event_json_decode_keyed": ([_vp, _vp, _i64, _vp, _i64, _vp], _i32),
@@ -198,6 +199,16 @@ INGEST_H = {
     "surge_lz4_frame_bound": ([_i64], _i64),
     "surge_lz4_frame_compress": ([_vp, _i64, _vp, _i64], _i64),
     "surge_xxh32": ([_vp, _i64, ctypes.c_uint32], ctypes.c_uint32),
+}
+
+#: the snappy reader: declared in ``include/surge_ingest.h`` behind the LZ4 frame's exports, in a table of its own (INGEST_H is
+#: what tests/test_abi.py finds in that header by the prefixes it has always looked for); needs no handle and no device
+SNAPPY_H = {
+    "surge_snappy_uncompressed_length": ([_vp, _i64, ctypes.POINTER(_i32)], _i64),
+    "surge_snappy_uncompress": ([_vp, _i64, _vp, _i64, ctypes.POINTER(_i32)], _i64),
+    "surge_snappy_frame_bound": ([_vp, _i64, ctypes.POINTER(_i32)], _i64),
+    "surge_snappy_frame_decompress": ([_vp, _i64, _vp, _i64, ctypes.POINTER(_i32)], _i64),
+    "surge_snappy_status_name": ([_i32], ctypes.c_char_p),
 }
 
 #: ``include/surge_snapshot.h``
@@ -227,6 +238,7 @@ EVENT_STRINGS_EXPORTS = ("surge_event_strings_validate",)
 #: what each header declares beside those
 EXPORTS = tuple(n for n in REPLAY_H if n not in STATE_EXPORTS)
 INGEST_EXPORTS = tuple(n for n in INGEST_H if n not in EVENT_STRINGS_EXPORTS)
+SNAPPY_EXPORTS = tuple(SNAPPY_H)
 SNAPSHOT_EXPORTS = tuple(SNAPSHOT_H)
 
 _lib: Optional[ctypes.CDLL] = None
@@ -320,7 +332,7 @@ def load() -> ctypes.CDLL:
         L = ctypes.CDLL(lib_path)
     except OSError as e:
         raise NativeLibraryError(f"cannot load {lib_path}: {e}") from e
-    for table in (REPLAY_H, INGEST_H, SNAPSHOT_H):
+    for table in (REPLAY_H, INGEST_H, SNAPSHOT_H, SNAPPY_H):
         for name, signature in table.items():
             try:
                 fn = getattr(L, name)

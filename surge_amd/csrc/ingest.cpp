@@ -6,6 +6,7 @@
 #include <thread>
 
 #include "ingest_internal.h"
+#include "snappy_block.h"
 
 using namespace surge::ingest::framer;
 
@@ -311,6 +312,26 @@ int32_t host_lz4(surge_ingest* g, const uint8_t** recs, int64_t* recs_len) {
   return OK;
 }
 
+// A snappy batch's records section (snappy_block.h: framed chunks or one raw block), decompressed on the host into g->scratch.
+// The preambles say what it holds before a byte is decoded, so there is no guess to grow; a refusal is worded by the header.
+int32_t host_snappy(surge_ingest* g, const uint8_t** recs, int64_t* recs_len) {
+  namespace sn = surge::snappy;
+  int64_t total = 0, got = 0;
+  sn::Status st = sn::frame_bound(*recs, *recs_len, &total);
+  if (st == sn::SN_OK) {
+    g->scratch.resize((size_t)total + 16);
+    st = sn::frame_decompress(*recs, *recs_len, g->scratch.data(), total, &got);
+  }
+  if (st != sn::SN_OK) {
+    const char* why = sn::status_name(st);
+    return fail(g, SURGE_E_CORRUPT, why);
+  }
+  g->counters[C_BYTES_DECOMPRESSED] += got;
+  *recs = g->scratch.data();
+  *recs_len = got;
+  return OK;
+}
+
 // FRAMES: a data batch's records section travels as it is (the device chains and parses the records): copied into the arena,
 // with defer_crc behind the 8-byte prefix; or, in place, left where the fetch response was received (inside the slab this
 // slice is a view of), with defer_crc together with the 44 bytes in front of it (Batch::crc_prefix).
@@ -362,21 +383,22 @@ int32_t take_batch(surge_ingest* g, const BatchHeader& h, const uint8_t* crc_ver
     return fail(g, SURGE_E_CORRUPT, "record batch CRC-32C mismatch");
   if (h.count < 0) return fail(g, SURGE_E_CORRUPT, "truncated batch header");
   // (a header that is only verified later, on the device, must not drive anything out of bounds before that: a record takes
-  // at least 7 bytes, and LZ4 expands at most 255 x)
+  // at least 7 bytes, and LZ4 expands at most 255 x — a snappy element less: 64 bytes from a 3-byte copy)
   if (defer_crc && (int64_t)h.count > (h.recs_len / 7 + 1) * (h.codec() ? 255 : 1))
     return fail(g, SURGE_E_CORRUPT, "recordCount impossible for the batch's size (damaged header)");
   const uint8_t* recs = h.recs;
   int64_t recs_len = h.recs_len;
   int sect_codec = 0;
-  if (h.codec() == 3 && g->device_lz4 && !h.control()) {
-    sect_codec = 3;  // the frame travels as it is: the device decoder walks its blocks and decodes them on the GPU
-  } else if (h.codec() == 3 && g->inplace && !h.control()) {
-    return fail(g, E_UNSUPPORTED, "an in-place feed leaves the sections where they were received: lz4 topics need SURGE_INGEST_DEVICE_LZ4");
-  } else if (h.codec() == 3) {
-    const int32_t rc = host_lz4(g, &recs, &recs_len);
+  const bool compressed = h.codec() == 3 || h.codec() == 2;  // lz4 (one frame) or snappy (chunks, or one raw block)
+  if (compressed && g->device_lz4 && !h.control()) {
+    sect_codec = h.codec();  // the section travels as it is: the device decoder walks its blocks / chunks and decodes them on the GPU
+  } else if (compressed && g->inplace && !h.control()) {
+    return fail(g, E_UNSUPPORTED, "an in-place feed leaves the sections where they were received: lz4 and snappy topics need SURGE_INGEST_DEVICE_LZ4");
+  } else if (compressed) {
+    const int32_t rc = h.codec() == 3 ? host_lz4(g, &recs, &recs_len) : host_snappy(g, &recs, &recs_len);
     if (rc != OK) return rc;
   } else if (h.codec() != 0) {
-    return fail(g, E_UNSUPPORTED, "compression codec not supported (only none and lz4; the reference publishes lz4)");
+    return fail(g, E_UNSUPPORTED, "compression codec not supported (none, lz4 and snappy are read; gzip and zstd are not; the reference publishes lz4)");
   }
   Batch b;
   b.producer_id = h.producer_id;
@@ -384,7 +406,7 @@ int32_t take_batch(surge_ingest* g, const BatchHeader& h, const uint8_t* crc_ver
   b.last_offset = h.base_offset + h.last_offset_delta;
   int control_type = -1;
   if (g->frames && !h.control()) {
-    if (defer_crc && recs != h.recs) return fail(g, E_UNSUPPORTED, "SURGE_INGEST_DEVICE_CRC needs the sections to travel as they are on the wire (SURGE_INGEST_DEVICE_LZ4 for lz4 topics)");
+    if (defer_crc && recs != h.recs) return fail(g, E_UNSUPPORTED, "SURGE_INGEST_DEVICE_CRC needs the sections to travel as they are on the wire (SURGE_INGEST_DEVICE_LZ4 for lz4 and snappy topics)");
     place_section(g, b, h, recs, recs_len, sect_codec, defer_crc);
   } else {
     const int32_t rc = parse_records(g, b, h, recs, recs_len, &control_type);

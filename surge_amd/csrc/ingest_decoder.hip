@@ -464,4 +464,11 @@ int32_t surge_device_decoder_stats(const surge_device_decoder* d, int64_t out[8]
   return OK;
 }
 
+int32_t surge_device_decoder_route_stats(const surge_device_decoder* d, int64_t out[2]) {
+  if (!d || !out) return E_INVALID;
+  out[0] = d->snappy_device_chunks;
+  out[1] = d->snappy_host_sections;
+  return OK;
+}
+
 }  // extern "C"

@@ -68,11 +68,14 @@ struct Buf {  // device memory, owned: freed with the buffer, which must happen 
 // latency-bound LZ4 kernels and the compute-bound decode of different fetches overlap on the chip.
 struct PushSlot {
   Buf lz4_blocks, lz4_sizes, lz4_nseq, lz4_seq, lz4_cls;
+  Buf sn_blocks, sn_sizes, sn_nseq, sn_seq, sn_cls;  // the same five for the snappy chunks (ingest_snappy.hip)
   Buf d_bytes, d_sections, rec_a, rec_b, rec_c, meta, ev_tmp, f64_list, d_err;
   void* pinned = nullptr;  // page-locked staging, the slot's own (slot_pinned)
   size_t pinned_cap = 0;
   std::vector<Section> h_secs;      // (sources of asynchronous copies: they live as long as the slot is busy)
   Lz4Plan lz4;                      // the LZ4 frames' blocks (ingest_lz4.hip plans them)
+  Lz4Plan snappy;                   // the snappy sections' chunks, in the same shapes (ingest_snappy.hip plans them)
+  int64_t snappy_host_sections = 0; // ... and the sections of this push it decompressed on the host instead
   std::vector<CrcSpan> h_crc;       // sections whose CRC-32C this push finishes on the device
   Buf crc_spans;
   std::vector<int64_t> h_floors;    // per section the offset its records must reach (INT64_MIN: none); empty: a push without floors
@@ -225,6 +228,7 @@ struct surge_device_decoder {
   int64_t below_floor = 0;             // records passed over below their section's floor (surge_device_decoder_below_floor)
   int64_t chain_fallbacks = 0;         // batches whose records the one-lane walk chained after the parallel recognition declined (SURGE_EXPERIMENTS builds print it)
   int64_t reseeds = 0, pushes = 0;
+  int64_t snappy_device_chunks = 0, snappy_host_sections = 0;  // of the pushes that delivered (surge_device_decoder_route_stats)
   bool slots_sized = false;  // the first wire push has sized every slot's buffers like its own
 };
 

@@ -57,7 +57,8 @@ struct ErrorCell {
   unsigned int reserved, n_f64_host;
   unsigned int lz4_bad;          // the first section whose LZ4 frame did not decode (~0 = none)
   unsigned int crc_bad;          // the first section whose bytes do not give the batch's CRC-32C (~0 = none; SURGE_INGEST_DEVICE_CRC)
-  unsigned int n_below, pad;     // records below their section's floor (RS_BELOW)
+  unsigned int n_below;          // records below their section's floor (RS_BELOW)
+  unsigned int snappy_bad;       // the first section with a snappy chunk that did not decode (~0 = none; ingest_snappy.hip)
 };
 
 __device__ __forceinline__ void report(ErrorCell* err, int64_t rec, uint32_t status) {
@@ -221,6 +222,24 @@ Lz4ScratchBytes lz4_scratch_bytes(const Lz4Plan& plan);
 // decodes the plan's blocks (d_blocks: their table on the device) from `bytes` into `area`; a frame's last block sets its
 // section's byte_len, a frame that does not decode zeroes it and lowers err->lz4_bad
 hipError_t launch_lz4(const Lz4Plan& plan, const uint8_t* bytes, uint8_t* area, const Lz4Block* d_blocks, Lz4Work w, Section* sections, ErrorCell* err, hipStream_t st);
+
+// the second pass alone (lz4_exec_kernel, one launch per LDS class) over a block table whose first pass has run: entries, sizes
+// and class lists in `w`.  It knows nothing of LZ4: ingest_snappy.hip runs it over the entries its own parse kernel wrote.
+hipError_t launch_lz4_exec(const uint8_t* bytes, uint8_t* area, const Lz4Block* d_blocks, int64_t n_blocks, Lz4Work w, hipStream_t st);
+
+// ---- ingest_snappy.hip: snappy sections (codec 2; the format: snappy_block.h) ------------------------------------------------------
+// A section's chunks in a plan and a block table of their own, in the LZ4 stage's shapes: Lz4Block::index holds the chunk's
+// output offset inside its section in units of 16 bytes (every chunk but a section's last is a multiple of 16 long, so chunk
+// k's output lies right behind chunk k - 1's and every destination is 16-byte aligned), src_off / src_len name the raw block
+// with its preamble, seq_off its room in the entry table (a copy takes at least 2 bytes: src_len / 2 + 2 entries).
+// plans the section [sec, sec + len) staged at src_off; LZ4_ON_HOST: a chunk above 64 KiB, a chunk but the last off the 16-byte
+// grid or a chunk longer than the parse kernel's LDS holds — decompressed here and appended to host_out; *why: the refusal's
+// text for LZ4_BAD_FRAME
+Lz4Route snappy_plan_section(Lz4Plan& plan, const uint8_t* sec, int64_t len, int64_t src_off, int32_t section, int64_t* area_off, std::vector<uint8_t>& host_out,
+                             const char** why);
+// parses the plan's chunks (snappy_parse_kernel: literals stored in place, one entry per copy), then applies the copies with the
+// LZ4 stage's second pass; a section's last chunk sets its byte_len, a chunk that does not decode lowers err->snappy_bad
+hipError_t launch_snappy(const Lz4Plan& plan, const uint8_t* bytes, uint8_t* area, const Lz4Block* d_blocks, Lz4Work w, Section* sections, ErrorCell* err, hipStream_t st);
 
 // ---- ingest_records.hip: meta / ev_tmp / f64_host_list per record ---------------------------------------------------------------
 // one workgroup per section, as wide as max_recs (the push's largest batch) needs; floors (nullable; events mode only): per section

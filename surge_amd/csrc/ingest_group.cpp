@@ -471,7 +471,8 @@ int32_t surge_ingest_group_feed(surge_ingest_group* grp, const uint8_t* const* d
   // slice, whose size is then only known afterwards: the feed is undone and run again with `expand` times the room.
   // (the trial starts from the factor the last feed needed, not from 1: a group without SURGE_INGEST_DEVICE_LZ4 on a compressed
   // topic otherwise framed — CRC, decompression and all — every fetch two or three times over, for ever; the factor is capped
-  // at 256: an LZ4 block expands at most 255 x)
+  // at 256: an LZ4 block expands at most 255 x, and a snappy block less — its densest element is a 3-byte copy of 64 bytes,
+  // under 22 x — so the same cap covers a group on a snappy topic)
   for (int64_t expand = grp->expand_hint;; expand *= 4) {
     const int32_t rc = prepare_slab(grp, slab, len, inplace, expand);
     if (rc != OK) return rc;

@@ -562,6 +562,16 @@ Lz4ScratchBytes lz4_scratch_bytes(const Lz4Plan& plan) {
   return n;
 }
 
+hipError_t launch_lz4_exec(const uint8_t* bytes, uint8_t* area, const Lz4Block* d_blocks, int64_t nb, Lz4Work w, hipStream_t st) {
+  for (int c = 0; c <= kLz4Classes; ++c) {
+    const int32_t cap = c < kLz4Classes ? kLz4ClassCapHost[c] : 0;
+    const size_t lds = cap ? (size_t)cap + (size_t)kLz4Map * 2 : 0;
+    const int64_t resident = 256ll * (lds ? (int64_t)(160 * 1024 / lds) : 16);  // waves the chip holds at this LDS size
+    hipLaunchKernelGGL(lz4_exec_kernel, dim3((unsigned)(nb < resident ? nb : resident)), dim3(64), lds, st, bytes, area, d_blocks, (int32_t)nb, w, c, cap);
+  }
+  return hipGetLastError();
+}
+
 hipError_t launch_lz4(const Lz4Plan& plan, const uint8_t* bytes, uint8_t* area, const Lz4Block* d_blocks, Lz4Work w, Section* sections, ErrorCell* err,
                       hipStream_t st) {
   const int64_t nb = (int64_t)plan.blocks.size();
@@ -579,12 +589,7 @@ hipError_t launch_lz4(const Lz4Plan& plan, const uint8_t* bytes, uint8_t* area, 
   for (int c = 0; c < 3; ++c)
     hipLaunchKernelGGL(lz4_parse_kernel, dim3((unsigned)nb), dim3(64), (size_t)parse_caps[c], st, bytes, area, d_blocks, (int32_t)nb, w, sections, err,
                        c == 0 ? -1 : parse_caps[c - 1], parse_caps[c]);
-  for (int c = 0; c <= kLz4Classes; ++c) {
-    const int32_t cap = c < kLz4Classes ? kLz4ClassCapHost[c] : 0;
-    const size_t lds = cap ? (size_t)cap + (size_t)kLz4Map * 2 : 0;
-    const int64_t resident = 256ll * (lds ? (int64_t)(160 * 1024 / lds) : 16);  // waves the chip holds at this LDS size
-    hipLaunchKernelGGL(lz4_exec_kernel, dim3((unsigned)(nb < resident ? nb : resident)), dim3(64), lds, st, bytes, area, d_blocks, (int32_t)nb, w, c, cap);
-  }
+  (void)launch_lz4_exec(bytes, area, d_blocks, nb, w, st);
   bool any_one_pass = false;  // blocks of exactly 64 KiB (or more) compressed
   for (const Lz4Block& b : plan.blocks) any_one_pass = any_one_pass || b.seq_off < 0;
   if (any_one_pass) {

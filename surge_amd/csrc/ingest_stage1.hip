@@ -17,7 +17,7 @@ int32_t slot_scratch(surge_device_decoder* d, PushSlot& s, int64_t n_rec) {
   DCHK(d, s.meta.reserve(R * sizeof(RecMeta), false, s.stream));
   if (!d->states) DCHK(d, s.ev_tmp.reserve(R * 16, false, s.stream));
   if (!d->states) DCHK(d, s.f64_list.reserve(R * 4, false, s.stream));
-  static const ErrorCell kZero{~0ull, 0u, 0u, ~0u, ~0u, 0u, 0u};  // (the source of an asynchronous copy: it must outlive the call)
+  static const ErrorCell kZero{~0ull, 0u, 0u, ~0u, ~0u, 0u, ~0u};  // (the source of an asynchronous copy: it must outlive the call)
   DCHK(d, hipMemcpyAsync(s.d_err.p, &kZero, sizeof(kZero), hipMemcpyHostToDevice, s.stream));
   return OK;
 }
@@ -68,7 +68,8 @@ struct Laps {
 };
 
 // Where a wire push's bytes go on the device: the span of each part's arena the push needs, one after the other (16-byte
-// aligned), then the sections the host decompressed (`extra`), then — from area_base on — the frames the device decompresses.
+// aligned), then the sections the host decompressed (`extra`), then — from area_base on — the LZ4 frames the device decompresses
+// and, behind those (snappy_base), the snappy sections'.
 struct WireLayout {
   struct Part {
     int64_t lo, len, dev;  // the span [lo, lo + len) of the caller's arena goes to `dev` of the slot's bytes
@@ -84,10 +85,13 @@ struct WireLayout {
 struct SlotNeeds {  // what a slot's buffers have to hold for a push
   size_t bytes, sections, crc_spans, floors, pinned;
   int64_t n_rec;
-  Lz4ScratchBytes lz4;
+  Lz4ScratchBytes lz4, snappy;
 };
 
 size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+// Section::byte_off while a push is planned: -1 - x = x bytes into the LZ4 area, kSnappyMark - x = x bytes into the snappy area
+constexpr int64_t kSnappyMark = -(1ll << 62);
 
 // step 1: the parts' spans and the push's section table (s.h_secs)
 int32_t layout_sections(surge_device_decoder* d, PushSlot& s, int32_t n_parts, const surge_batch_section* const* sections, const int64_t* n_sections, WireLayout& L) {
@@ -122,11 +126,13 @@ int32_t layout_sections(surge_device_decoder* d, PushSlot& s, int32_t n_parts, c
 }
 
 // step 2: one walk over the sections' first bytes on the host — the CRC spans the device finishes (s.h_crc) and the LZ4
-// frames' blocks (s.lz4: ingest_lz4.hip reads the frames)
+// frames' blocks (s.lz4: ingest_lz4.hip reads the frames) and the snappy sections' chunks (s.snappy: ingest_snappy.hip)
 int32_t plan_frames(surge_device_decoder* d, PushSlot& s, int32_t n_parts, const uint8_t* const* bytes, const surge_batch_section* const* sections,
                     const int64_t* n_sections, WireLayout& L) {
   try {
     s.lz4.clear();
+    s.snappy.clear();
+    s.snappy_host_sections = 0;
     s.h_crc.clear();
     int64_t at = 0;
     for (int32_t p = 0; p < n_parts; ++p) {
@@ -152,9 +158,26 @@ int32_t plan_frames(surge_device_decoder* d, PushSlot& s, int32_t n_parts, const
           const uint32_t expect = ((uint32_t)c[0] << 24) | ((uint32_t)c[1] << 16) | ((uint32_t)c[2] << 8) | c[3];
           s.h_crc.push_back(CrcSpan{sec.byte_off - 40, (int32_t)in.byte_len + 40, (int32_t)at, expect, ~0u});
         }
-        if ((in.codec & 0xff) != 3 || in.n_records == 0) continue;
+        if (((in.codec & 0xff) != 3 && (in.codec & 0xff) != 2) || in.n_records == 0) continue;
         const size_t ex = L.extra.size();
         int64_t area_off = 0;
+        if ((in.codec & 0xff) == 2) {
+          const char* why = "";
+          switch (snappy_plan_section(s.snappy, bytes[p] + in.byte_off, in.byte_len, sec.byte_off, (int32_t)at, &area_off, L.extra, &why)) {
+            case LZ4_ON_DEVICE:  // (resolved below, behind the LZ4 frames' area: kSnappyMark tells the two apart)
+              sec.byte_off = kSnappyMark - area_off;
+              sec.byte_len = 0;
+              break;
+            case LZ4_ON_HOST:
+              sec.byte_off = L.n_raw + (int64_t)ex;
+              sec.byte_len = (int64_t)(L.extra.size() - ex);
+              ++s.snappy_host_sections;
+              break;
+            case LZ4_TOO_LARGE:
+            case LZ4_BAD_FRAME: return dfail(d, SURGE_E_CORRUPT, std::string(why) + " (the section at base offset " + std::to_string(in.base_offset) + ")");
+          }
+          continue;
+        }
         switch (lz4_plan_section(s.lz4, bytes[p] + in.byte_off, in.byte_len, sec.byte_off, (int32_t)at, &area_off, L.extra)) {
           case LZ4_ON_DEVICE:  // byte_off: resolved below, once the raw spans' final size is known; byte_len: set by the kernel that decodes the frame's last block
             sec.byte_off = -1 - area_off;
@@ -173,8 +196,11 @@ int32_t plan_frames(surge_device_decoder* d, PushSlot& s, int32_t n_parts, const
     return dfail(d, E_NOMEM, "out of host memory");
   }
   if (s.lz4.blocks.size() >= (1ull << 31)) return dfail(d, E_UNSUPPORTED, "more than 2^31 LZ4 blocks in one push: push fewer sections at a time");
-  for (Section& sc : s.h_secs)
-    if (sc.byte_off < 0) sc.byte_off = L.area_base() + (-1 - sc.byte_off);
+  if (s.snappy.blocks.size() >= (1ull << 31)) return dfail(d, E_UNSUPPORTED, "more than 2^31 snappy chunks in one push: push fewer sections at a time");
+  for (Section& sc : s.h_secs) {
+    if (sc.byte_off <= kSnappyMark) sc.byte_off = L.area_base() + s.lz4.area + (kSnappyMark - sc.byte_off);
+    else if (sc.byte_off < 0) sc.byte_off = L.area_base() + (-1 - sc.byte_off);
+  }
   return OK;
 }
 
@@ -183,13 +209,14 @@ int32_t plan_frames(surge_device_decoder* d, PushSlot& s, int32_t n_parts, const
 // too: a copy from pageable memory waits for the stream (1.4 ms of host time per push went there)
 SlotNeeds slot_needs(const PushSlot& s, const uint8_t* const* bytes, WireLayout& L) {
   SlotNeeds n;
-  n.bytes = (size_t)(L.area_base() + s.lz4.area) + 64;
+  n.bytes = (size_t)(L.area_base() + s.lz4.area + s.snappy.area) + 64;
   n.sections = sizeof(Section) * s.h_secs.size();
   n.crc_spans = sizeof(CrcSpan) * s.h_crc.size();
   n.n_rec = L.n_rec;
   n.lz4 = lz4_scratch_bytes(s.lz4);
+  n.snappy = lz4_scratch_bytes(s.snappy);
   n.floors = 8 * s.h_floors.size();
-  n.pinned = pad16(L.extra.size()) + n.sections + n.lz4.blocks + pad16(n.crc_spans) + pad16(n.floors) + 64;
+  n.pinned = pad16(L.extra.size()) + n.sections + n.lz4.blocks + pad16(n.snappy.blocks) + pad16(n.crc_spans) + pad16(n.floors) + 64;
   for (size_t p = 0; p < L.parts.size(); ++p) {
     WireLayout::Part& part = L.parts[p];
     if (part.len == 0) continue;
@@ -205,7 +232,8 @@ int32_t size_slot(surge_device_decoder* d, PushSlot& t, const SlotNeeds& n) {
   const size_t per_event = d->states ? 0 : (size_t)n.n_rec;  // (a state decoder decodes no value)
   const std::pair<Buf*, size_t> device[] = {{&t.d_bytes, n.bytes}, {&t.d_sections, n.sections}, {&t.meta, (size_t)n.n_rec * sizeof(RecMeta)}, {&t.ev_tmp, per_event * 16},
                                             {&t.f64_list, per_event * 4}, {&t.crc_spans, n.crc_spans}, {&t.d_floors, n.floors}, {&t.lz4_blocks, n.lz4.blocks}, {&t.lz4_sizes, n.lz4.state},
-                                            {&t.lz4_nseq, n.lz4.n_seq}, {&t.lz4_seq, n.lz4.seq}, {&t.lz4_cls, n.lz4.cls}};
+                                            {&t.lz4_nseq, n.lz4.n_seq}, {&t.lz4_seq, n.lz4.seq}, {&t.lz4_cls, n.lz4.cls}, {&t.sn_blocks, n.snappy.blocks},
+                                            {&t.sn_sizes, n.snappy.state}, {&t.sn_nseq, n.snappy.n_seq}, {&t.sn_seq, n.snappy.seq}, {&t.sn_cls, n.snappy.cls}};
   for (const auto& b : device) DCHK(d, b.first->reserve(b.second, false, t.stream));
   return slot_pinned(d, t, n.pinned);
 }
@@ -248,6 +276,8 @@ int32_t stage_and_copy(surge_device_decoder* d, PushSlot& s, const uint8_t* cons
   DCHK(d, hipMemcpyAsync(s.d_sections.p, stage(s.h_secs.data(), sec_bytes), sec_bytes, hipMemcpyHostToDevice, st));
   if (crc_bytes) DCHK(d, hipMemcpyAsync(s.crc_spans.p, stage(s.h_crc.data(), crc_bytes), crc_bytes, hipMemcpyHostToDevice, st));
   if (blk_bytes) DCHK(d, hipMemcpyAsync(s.lz4_blocks.p, stage(s.lz4.blocks.data(), blk_bytes), blk_bytes, hipMemcpyHostToDevice, st));
+  const size_t sn_bytes = sizeof(Lz4Block) * s.snappy.blocks.size();
+  if (sn_bytes) DCHK(d, hipMemcpyAsync(s.sn_blocks.p, stage(s.snappy.blocks.data(), sn_bytes), sn_bytes, hipMemcpyHostToDevice, st));
   const size_t floor_bytes = 8 * s.h_floors.size();
   if (floor_bytes) DCHK(d, hipMemcpyAsync(s.d_floors.p, stage(s.h_floors.data(), floor_bytes), floor_bytes, hipMemcpyHostToDevice, st));
   return OK;
@@ -287,6 +317,8 @@ int32_t surge::ingest::host::stage1_wire(surge_device_decoder* d, PushSlot& s, i
   }
   s.n_rec = 0;
   s.wire = true;
+  s.snappy.clear();  // (stage 2 counts what this push planned: nothing, should it end before plan_frames)
+  s.snappy_host_sections = 0;
   if (L.total_sections >= (1ll << 31)) return dfail(d, E_UNSUPPORTED, "more than 2^31 batches in one push");
   int32_t rc = expand_floors(d, s, L.total_sections, n_floors, floors);
   if (rc != OK || L.total_sections == 0) return rc;
@@ -313,6 +345,9 @@ int32_t surge::ingest::host::stage1_wire(surge_device_decoder* d, PushSlot& s, i
   Lz4Work w{dbg_decode() / 10, (int32_t*)s.lz4_sizes.p, (int32_t*)s.lz4_nseq.p, (uint2*)s.lz4_seq.p, (int32_t*)s.lz4_cls.p, nullptr};
   DCHK(d, launch_lz4(s.lz4, dby, (uint8_t*)s.d_bytes.p + L.area_base(), (const Lz4Block*)s.lz4_blocks.p, w, dsec, derr, st));
   laps.lap("lz4 launches");
+  Lz4Work ws{0, (int32_t*)s.sn_sizes.p, (int32_t*)s.sn_nseq.p, (uint2*)s.sn_seq.p, (int32_t*)s.sn_cls.p, nullptr};
+  DCHK(d, launch_snappy(s.snappy, dby, (uint8_t*)s.d_bytes.p + L.area_base() + s.lz4.area, (const Lz4Block*)s.sn_blocks.p, ws, dsec, derr, st));
+  laps.lap("snappy launches");
   const JsonCtx jc = json_ctx(d, dbg_decode() % 10);
   DCHK(d, launch_sections(dby, dsec, L.total_sections, L.max_recs, seed, jc, (RecMeta*)s.meta.p, (uint4*)s.ev_tmp.p, (uint32_t*)s.f64_list.p, derr,
                           s.h_floors.empty() ? nullptr : (const int64_t*)s.d_floors.p, st));

@@ -127,14 +127,14 @@ struct Stage2 {
       PCHK(d, hipMemcpyAsync(&first_total, (unsigned long long*)d->first_scan.p + R, 8, hipMemcpyDeviceToHost, st));
       PCHK(d, hipMemcpyAsync(&kept, (uint32_t*)d->keep_pos.p + R, 4, hipMemcpyDeviceToHost, st));
       PCHK(d, wait_stream(d, st));
-      if (ec.lz4_bad == ~0u && ec.crc_bad == ~0u && ec.first_bad != ~0ull && (uint32_t)(ec.first_bad & 0xff) == RS_COLLISION && attempt < 3) {
+      if (ec.lz4_bad == ~0u && ec.snappy_bad == ~0u && ec.crc_bad == ~0u && ec.first_bad != ~0ull && (uint32_t)(ec.first_bad & 0xff) == RS_COLLISION && attempt < 3) {
         // Two different keys share a 64-bit hash (about 3 in a million pushes at 10^7 keys): the table gets another hash
         // function — every known key re-hashed from its bytes in the arena, the push's records from theirs — and the push
         // goes through again.  Nothing of it was committed.
         d->seed = (d->seed & ~(1ull << 63)) + 1;
         ++d->reseeds;
         launch_intern_reseed(dmeta, n_rec, dby, keys_of(d), d->seed, st);
-        s.h_err = ErrorCell{~0ull, 0u, ec.n_f64_host, ~0u, ~0u, ec.n_below, 0u};
+        s.h_err = ErrorCell{~0ull, 0u, ec.n_f64_host, ~0u, ~0u, ec.n_below, ~0u};
         PCHK(d, hipMemcpyAsync(derr, &s.h_err, sizeof(s.h_err), hipMemcpyHostToDevice, st));
         continue;
       }
@@ -180,7 +180,7 @@ struct Stage2 {
     return dfail(d, code, why);
   }
 
-  bool found_bad() const { return ec.crc_bad != ~0u || ec.lz4_bad != ~0u || ec.first_bad != ~0ull; }
+  bool found_bad() const { return ec.crc_bad != ~0u || ec.lz4_bad != ~0u || ec.snappy_bad != ~0u || ec.first_bad != ~0ull; }
 
   // the push as a whole fails with its first bad batch or record, by name
   int32_t name_failure() {
@@ -188,6 +188,9 @@ struct Stage2 {
     if (ec.crc_bad != ~0u) return fail(SURGE_E_CORRUPT, "record batch CRC-32C mismatch (verified on the device) in the batch at base offset " + base_offset_of(ec.crc_bad));
     if (ec.lz4_bad != ~0u)
       return fail(SURGE_E_CORRUPT, "bad LZ4 frame in the batch at base offset " + base_offset_of(ec.lz4_bad) + " (malformed sequence, or a block that is not 64 KiB where it must be)");
+    if (ec.snappy_bad != ~0u)
+      return fail(SURGE_E_CORRUPT, "bad snappy chunk in the batch at base offset " + base_offset_of(ec.snappy_bad) +
+                                       " (an element that runs past the chunk, offset 0 or beyond the output, or output that misses the preamble's length)");
     const int64_t rec = (int64_t)(ec.first_bad >> 8);
     const uint32_t status = (uint32_t)(ec.first_bad & 0xff);
     RecMeta m;
@@ -280,6 +283,10 @@ struct Stage2 {
     d->counters[2] += n_rec - kept - ec.n_below;
     d->below_floor += ec.n_below;
     ++d->pushes;
+    if (s.wire) {
+      d->snappy_device_chunks += (int64_t)s.snappy.blocks.size();
+      d->snappy_host_sections += s.snappy_host_sections;
+    }
     if (wait) {
       PCHK(d, wait_stream(d, st));
     } else {  // the slot's buffers are read until here: its next stage 1 waits for this point of the stream

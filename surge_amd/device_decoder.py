@@ -431,3 +431,11 @@ class DeviceDecoder:
         self._lib.surge_device_decoder_stats(self._h, ctypes.byref(c))
         return dict(zip(["records_seen", "records_delivered", "flush_records_skipped", "doubles_parsed_on_host", "hash_reseeds", "table_slots", "pushes",
                          "hash_function"], [int(x) for x in c]))
+
+    def route_stats(self) -> dict:
+        """What stands behind ``stats()`` (whose eight entries stay what they are): the routes compressed sections took in the pushes
+        that delivered — snappy chunks decoded on the device, snappy sections decompressed on the host while the push was planned
+        (``surge_device_decoder_route_stats``)."""
+        r = (ctypes.c_int64 * 2)()
+        self._lib.surge_device_decoder_route_stats(self._h, ctypes.byref(r))
+        return dict(zip(["snappy_device_chunks", "snappy_host_sections"], [int(x) for x in r]))

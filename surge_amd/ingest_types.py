@@ -13,7 +13,8 @@ from .schema import EVENT_DTYPE
 
 READ_UNCOMMITTED, READ_COMMITTED = 0, 1
 FRAMES = 0x100  # SURGE_INGEST_FRAMES: frame on the host, decode the records on the GPU (DeviceDecoder)
-DEVICE_LZ4 = 0x200  # SURGE_INGEST_DEVICE_LZ4: ... and leave LZ4 frames for the GPU as well
+DEVICE_LZ4 = 0x200  # SURGE_INGEST_DEVICE_LZ4: ... and leave LZ4 frames and snappy chunks for the GPU as well
+DEVICE_DECOMPRESS = DEVICE_LZ4  # SURGE_INGEST_DEVICE_DECOMPRESS: the same bit, by the name of what it has come to mean
 DEVICE_CRC = 0x400  # SURGE_INGEST_DEVICE_CRC: ... and finish a data batch's CRC-32C on the GPU (the host checksums its 40 header bytes only)
 SECTION_CRC_PENDING = 0x100  # in a section's codec: {crc, register after the 40 covered header bytes} lie in front of the section
 SECTION_CRC_WIRE = 0x200  # ... (in-place framing) the batch's own crc field and the 40 header bytes it covers do: the device runs the whole CRC
