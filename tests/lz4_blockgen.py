@@ -1,4 +1,4 @@
-"""TEST INFRASTRUCTURE: inputs for the WRITING side of the device's LZ4 path (surge_amd/csrc/frame_kernels.hip:
+"""TEST INFRASTRUCTURE: inputs for the WRITING side of the device's LZ4 path (surge_amd/csrc/frame_lz4.hip:
 frame_lz4_block_kernel, frame_lz4_pack_kernel and the uncompressed framer under them), built on the CPU, next to
 tests/lz4_seqgen.py, which does the same for the reading side.
 

@@ -1,4 +1,4 @@
-"""CPU: the arithmetic the device framer rests on (surge_amd/csrc/frame_kernels.hip), restated with numpy and checked
+"""CPU: the arithmetic the device framer rests on (surge_amd/csrc/frame_records.hip), restated with numpy and checked
 against the host record-batch writer — the closed form for the bytes of a run of records (three prefix sums, one per
 width of the offsetDelta varint) and the greedy batch cut found by binary search.  The kernels themselves are checked
 byte for byte against the same writer on the GPU (tests/test_frame_gpu.py)."""

@@ -1,4 +1,4 @@
-"""-m gpu: the uncompressed device framer (surge_amd/csrc/frame_kernels.hip) against the host record-batch writer, BYTE FOR
+"""-m gpu: the uncompressed device framer (surge_amd/csrc/frame_records.hip) against the host record-batch writer, BYTE FOR
 BYTE, at the shapes tests/test_frame_gpu.py does not reach: no value there is longer than 120 bytes.  The framer's closed-form
 sizes (c1 / c2 / c3, run_bytes) rest on varint_size(base + v), v = 1, 2, 3 the bytes of the offsetDelta -- and that
 changes between v = 1, 2, 3 exactly when a record's body is within 3 bytes of 8192 or of 2^20; the greedy cut by

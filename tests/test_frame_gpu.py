@@ -1,4 +1,4 @@
-"""-m gpu: the device framer (surge_device_framer_*, surge_amd/csrc/frame_kernels.hip) against the host record-batch writer
+"""-m gpu: the device framer (surge_device_framer_*, surge_amd/csrc/device_framer.hip, frame_records.hip) against the host record-batch writer
 (surge_snapshot_writer_*, itself checked against the independent test-side writer in tests/test_ingest.py): the same input
 must give the same bytes — records, batch cuts, headers, CRCs, offsets across publishes."""
 import numpy as np

@@ -1,5 +1,5 @@
 """-m gpu: the device LZ4 compressor and framer (frame_lz4_block_kernel, frame_lz4_pack_kernel in
-surge_amd/csrc/frame_kernels.hip) at the edges they branch on: hand-built blocks from tests/lz4_blockgen.py, whose CPU test
+surge_amd/csrc/frame_lz4.hip) at the edges they branch on: hand-built blocks from tests/lz4_blockgen.py, whose CPU test
 (tests/test_lz4_blockgen.py) has shown on a restatement of the kernel's scheme that every case reaches the edge it is
 named for.  What the CPU cannot show is what the wave does: the ballots, the one-wave barrier, the strided length writes,
 the unaligned 8-byte copies.

@@ -1,5 +1,5 @@
 """-m gpu: the LZ4 mode of the device framer (surge_device_framer_set_compression, frame_lz4_block_kernel in
-surge_amd/csrc/frame_kernels.hip).  Its output is not the host compressor's byte for byte, so it is held to what it has
+surge_amd/csrc/frame_lz4.hip).  Its output is not the host compressor's byte for byte, so it is held to what it has
 to be instead: the batches of the host writer's UNCOMPRESSED output for the same input (cuts, offsets, header fields),
 each records section one LZ4 frame that liblz4 (as Apache Arrow bundles it) decompresses to the host writer's records,
 whose compressed blocks obey the block format's end rules, about as small as the host compressor's, and read by the
