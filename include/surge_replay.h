@@ -548,6 +548,8 @@ int32_t surge_replay_encode_protobuf_state_rows(surge_replay_handle* h, const su
 #define SURGE_STATE_DECODE_AMBIGUOUS    9 /* device only, transient: a Double the fast algorithm cannot decide        */
 #define SURGE_STATE_DECODE_SURROGATE   10 /* a \uD800 .. \uDFFF escape                                                */
 #define SURGE_STATE_DECODE_ENVELOPE    11 /* protobuf State values only: not `[0x0A len id] [0x12 len payload]` and nothing else */
+#define SURGE_STATE_DECODE_SYNTAX      12 /* lenient mode only: not a JSON object, or malformed JSON outside a known field's value */
+#define SURGE_STATE_DECODE_MISSING     13 /* lenient mode only: the object closed without a field the template names  */
 #define SURGE_STATE_DECODE_SKIPPED    255 /* d_status_out only: a later record names the same aggregate; not parsed   */
 
 /* One value on the host (thread-safe; needs no device): 0 or a SURGE_STATE_DECODE_* status (> 0), SURGE_E_INVALID for a
@@ -638,6 +640,47 @@ int32_t surge_replay_merge_state_strings(surge_replay_handle* h, int32_t column,
  * so only then does a restored row equal, byte for byte, the row a fold of the aggregate's events produces — as the host
  * path's state_to_fixed does.  Tombstones stay 64 zero bytes. */
 int32_t surge_replay_set_decode_base(surge_replay_handle* h, const void* state64);
+
+/* ---- the lenient reading mode -----------------------------------------------------------------------------
+ * Everything above reads the text our own encoders write.  The reference reads its state topic with
+ * Json.parse(bytes).asOpt[State] (TestBoundedContext.scala:156, BankAccountSurgeModel.scala:23, the multilanguage side on
+ * pbState.payload), which also takes the members in any order, insignificant whitespace, and members the case class does not
+ * know — what a topic holds after a release added a field to the state, or what an SDK application's own JSON library writes.
+ * The lenient mode reads those values through the same template.  A template is usable when its parts alternate LITERAL,
+ * value, ..., LITERAL with the first literal {"<name>": each inner one ,"<name>": and the last one } — a name of at least
+ * one byte without quote or backslash, no two names equal (at most 7 fields); any other shape is SURGE_E_UNSUPPORTED for
+ * the lenient calls and nothing is launched.  Accepted:
+ *   - whitespace (0x20 \t \n \r) around every token, in front of the object and behind it.  The top level must be an
+ *     object (else SYNTAX); other bytes behind its closing brace are TRAILING;
+ *   - members in any order; a member name is a JSON string by the rules above ("count" names count), compared unescaped;
+ *   - a member the template names is parsed by the strict mode's routine for its kind and reports that routine's status:
+ *     `null` is INT, NUMBER or STRING by kind, KEY is compared with the id when a key is given, the integer rule stays
+ *     -?[0-9]+ (play-json would also take 1.0 or 1e2 for an Int);
+ *   - a name that occurs more than once: every occurrence is parsed — a refused one refuses the value — and the last one
+ *     gives the field and the STR span.  play-json's map and Python's json.loads keep the last and ignore the earlier ones:
+ *     refusing a bad earlier occurrence is narrower than either;
+ *   - any other member is skipped and validated as JSON: strings without raw bytes below 0x20, escapes \" \\ \/ \b \f \n \r
+ *     \t and \u + four hex digits (surrogates pass: nothing is unescaped); numbers -?(0|[1-9][0-9]*)(\.[0-9]+)?([eE][+-]?[0-9]+)?;
+ *     true, false, null; arrays and objects to a nesting depth of 32 below the top-level object.  Deeper nesting and anything
+ *     malformed are SYNTAX;
+ *   - a field of the template that never occurred is MISSING when the object closes (Json.format gives None there).
+ * As in strict mode: POISONED and the sign of -0.0 are not restored, bytes from 0x80 on are not checked as UTF-8, and ABI v2
+ * handles stay SURGE_E_UNSUPPORTED.  Every value the strict mode accepts gets the same row and spans. */
+#define SURGE_STATE_READ_STRICT  0 /* the default: compact text, fields in template order */
+#define SURGE_STATE_READ_LENIENT 1
+
+/* A handle setting, like surge_replay_set_decode_base: how surge_replay_decode_json_states, surge_replay_decode_protobuf_states
+ * and surge_device_decoder_load_states / _load_protobuf_states (surge_ingest.h) read from now on; a Double the device cannot
+ * decide goes through the host export of the same mode.  An unknown mode is SURGE_E_INVALID.  On an ABI v2 handle the setter
+ * succeeds and the decode refuses as it always does. */
+int32_t surge_replay_set_decode_mode(surge_replay_handle* h, int32_t mode);
+
+/* surge_decode_json_state / surge_decode_protobuf_state in lenient mode: the same arguments and return values, and
+ * SURGE_E_UNSUPPORTED for a template the lenient mode cannot read.  Never read at or beyond value + len. */
+int32_t surge_decode_json_state_lenient(const surge_json_template* tmpl, const uint8_t* value, int64_t len, const uint8_t* key,
+                                        int64_t key_len, void* state64_out, int64_t* str_span_out);
+int32_t surge_decode_protobuf_state_lenient(const surge_json_template* payload_tmpl, const uint8_t* value, int64_t len,
+                                            const uint8_t* key, int64_t key_len, void* state64_out, int64_t* str_span_out);
 
 /* ---- snapshot publishing (SURVEY §8f N2 x N3) ---------------------------------------------------------------
  * What the state topic needs after a replay / a run of micro-batches, relative to the last COMMITTED snapshot of this

@@ -4,6 +4,7 @@
     python scripts/state_topic_bench.py --envelope protobuf_state [n_aggregates] [pairs] > profiles/state_topic_restore_protobuf.json
     rocprofv3 --kernel-trace --stats -d DIR -- python scripts/state_topic_bench.py --one-push [n_aggregates]
     python scripts/state_topic_bench.py --kernel-split DIR profiles/state_topic_restore.json   # folds the trace's stats into the JSON
+    python scripts/state_topic_bench.py --lenient [n_aggregates] [pairs] > profiles/state_decode_lenient.json
 
 n Counter aggregates are folded into an engine and published as the state topic — LZ4 record batches on 4 partitions,
 framed and compressed by the device framer (``BulkSnapshotPublisher``).  Then two routes from those bytes to the same
@@ -21,7 +22,15 @@ whether the device route wins every pair by more than both spreads.  ``--one-pus
 gather its time against the bytes it moves (read + written) as a fraction of 8 TB/s — recorded, not held to a bar.
 ``--envelope protobuf_state`` (in front of the other arguments) publishes the same aggregates as a multilanguage (SDK)
 application stores them — ``encode_states(envelope="protobuf_state")`` behind the same device framer — and restores them
-through the envelope route of every call above."""
+through the envelope route of every call above.
+``--lenient`` (likewise in front) measures what the lenient reading mode costs on text that does not need it: the same compact
+topic — both modes accept it — restored in the strict and in the lenient mode, ``pairs`` alternating pairs in one process after
+a warm-up of both, for ``device_core`` and for the whole ``restore_from_state_topic``.  One JSON line: every repeat's seconds,
+medians, spreads, the rows compared, and whether the medians differ by more than the larger spread.
+``--strict-leg LABEL [n_aggregates] [pairs]`` prints the strict route alone as one JSON line — for comparing this tree with another
+one in separate processes (A / B / A); ``SURGE_BENCH_ROOT`` names the tree whose ``surge_amd`` is measured (default: this
+script's).  ``--merge-aba A1 B A2 JSON`` folds three such lines (this tree, the parent, this tree) into the JSON under
+``strict_route_aba``."""
 import csv
 import glob
 import json
@@ -31,9 +40,10 @@ import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.environ.get("SURGE_BENCH_ROOT", HERE)
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "examples"))
+sys.path.insert(0, os.path.join(HERE, "examples"))
 
 N_PART = 4
 PEAK_BYTES_PER_S = 8e12
@@ -62,12 +72,13 @@ def publish_topic(n):
     return keys, out, text
 
 
-def device_route(bl, topic):
+def device_route(bl, topic, lenient=False):
     from surge_amd.store import GpuReplayStateStore
 
     store = GpuReplayStateStore(bl)
+    mode = {"lenient": True} if lenient else {}
     t0 = time.perf_counter()
-    counts = store.restore_from_state_topic([[topic.get(p) for p in range(N_PART)]], n_partitions=N_PART, envelope=ENVELOPE)
+    counts = store.restore_from_state_topic([[topic.get(p) for p in range(N_PART)]], n_partitions=N_PART, envelope=ENVELOPE, **mode)
     return time.perf_counter() - t0, store, counts
 
 
@@ -86,7 +97,7 @@ def host_route(bl, topic):
     return time.perf_counter() - t0, store, None
 
 
-def device_core(topic, template):
+def device_core(topic, template, lenient=False):
     """framing + push + load, no store: seconds, and the engine / decoder for whoever wants to look"""
     import torch
 
@@ -105,7 +116,7 @@ def device_core(topic, template):
             parts = [(sec, arena) for sec, arena in (item if isinstance(item, list) else [item]) if sec.shape[0]]
             d.push_async(parts)
             d.finish()
-            counts = d.load_states_into(eng, template, envelope=ENVELOPE)
+            counts = d.load_states_into(eng, template, envelope=ENVELOPE, **({"lenient": True} if lenient else {}))
     dt = time.perf_counter() - t0
     d.close()
     eng.close()
@@ -152,6 +163,81 @@ def run(n, pairs):
     return out
 
 
+def run_lenient(n, pairs):
+    """the strict and the lenient mode over the same compact topic, alternating"""
+    from fixture_models import CounterBusinessLogic
+    from surge_amd.encode import JsonTemplate
+
+    bl = CounterBusinessLogic()
+    _, topic, text_bytes = publish_topic(n)
+    out = {"aggregates": n, "envelope": ENVELOPE, "partitions": N_PART, "topic_bytes": sum(len(b) for b in topic.values()), "value_bytes": text_bytes, "pairs": pairs}
+    small = {p: b for p, b in publish_topic(20000)[1].items()}
+    for lenient in (False, True):  # warm-up of both (code objects, pinned slabs' first touch, Python imports)
+        device_route(bl, small, lenient)[1].close()
+        device_core(small, JsonTemplate.counter(), lenient)
+    names = {False: "strict", True: "lenient"}
+    runs = {f"{what}_{mode}": [] for what in ("restore", "device_core") for mode in names.values()}
+    same = True
+    for i in range(pairs):
+        rows = {}
+        for lenient in ((False, True) if i % 2 == 0 else (True, False)):  # the order within a pair alternates too
+            t, store, counts = device_route(bl, topic, lenient)
+            if i == 0:
+                rows[lenient] = rows_by_key(store)
+                out[f"{names[lenient]}_counts"] = counts
+            store.close()
+            runs[f"restore_{names[lenient]}"].append(t)
+            runs[f"device_core_{names[lenient]}"].append(device_core(topic, JsonTemplate.counter(), lenient)[0])
+        if i == 0:
+            same = bool((rows[False][0] == rows[True][0]).all() and rows[False][1].tobytes() == rows[True][1].tobytes() and len(rows[True][0]) == n)
+    out["rows_equal_between_the_modes"] = same
+    for name, ts in runs.items():
+        out[name] = {"seconds": ts, "median_s": float(np.median(ts)), "spread_s": max(ts) - min(ts), "aggregates_per_s": n / float(np.median(ts))}
+    for what in ("restore", "device_core"):
+        a, b = out[f"{what}_strict"], out[f"{what}_lenient"]
+        spread = max(a["spread_s"], b["spread_s"])
+        out[f"{what}_lenient_over_strict_median"] = b["median_s"] / a["median_s"]
+        out[f"{what}_difference_exceeds_the_pairs_spread"] = bool(abs(b["median_s"] - a["median_s"]) > spread)
+    return out
+
+
+def run_strict_leg(label, n, pairs):
+    """the strict route of one tree: ``pairs`` repeats of the whole restore and of device_core after a warm-up"""
+    from fixture_models import CounterBusinessLogic
+    from surge_amd.encode import JsonTemplate
+
+    bl = CounterBusinessLogic()
+    _, topic, _ = publish_topic(n)
+    small = {p: b for p, b in publish_topic(20000)[1].items()}
+    device_route(bl, small)[1].close()
+    device_core(small, JsonTemplate.counter())
+    runs = {"restore": [], "device_core": []}
+    for _ in range(pairs):
+        t, store, _ = device_route(bl, topic)
+        store.close()
+        runs["restore"].append(t)
+        runs["device_core"].append(device_core(topic, JsonTemplate.counter())[0])
+    out = {"label": label, "root": os.path.basename(os.path.abspath(ROOT)), "aggregates": n, "pairs": pairs}
+    for name, ts in runs.items():
+        out[name] = {"seconds": ts, "median_s": float(np.median(ts)), "spread_s": max(ts) - min(ts)}
+    return out
+
+
+def merge_aba(a1, b, a2, json_path):
+    legs = [json.loads(open(p).read().strip().splitlines()[-1]) for p in (a1, b, a2)]
+    doc = json.load(open(json_path)) if os.path.exists(json_path) else {}
+    aba = {"legs": legs}
+    for what in ("restore", "device_core"):
+        this = [legs[0][what]["median_s"], legs[2][what]["median_s"]]
+        parent = legs[1][what]["median_s"]
+        spread = max(leg[what]["spread_s"] for leg in legs)
+        aba[what] = {"this_tree_median_s": this, "parent_median_s": parent, "largest_spread_s": spread,
+                     "difference_inside_the_spread": bool(abs(sum(this) / 2 - parent) <= max(spread, abs(this[0] - this[1])))}
+    doc["strict_route_aba"] = aba
+    json.dump(doc, open(json_path, "w"))
+    print(json.dumps(aba))
+
+
 def kernel_split(trace_dir, json_path):
     """rocprofv3's kernel stats of a --one-push run -> {"kernels": {name: {"calls", "total_us"}}, "value_gather": {...}} merged into json_path"""
     stats = sorted(glob.glob(os.path.join(trace_dir, "**", "*kernel_stats.csv"), recursive=True))
@@ -176,6 +262,9 @@ def kernel_split(trace_dir, json_path):
 
 if __name__ == "__main__":
     args = sys.argv[1:]
+    lenient_run = bool(args) and args[0] == "--lenient"
+    if lenient_run:
+        args = args[1:]
     if args and args[0] == "--envelope":
         ENVELOPE = args[1]
         if ENVELOPE not in ("none", "protobuf_state"):
@@ -183,6 +272,10 @@ if __name__ == "__main__":
         args = args[2:]
     if args and args[0] == "--kernel-split":
         kernel_split(args[1], args[2])
+    elif args and args[0] == "--merge-aba":
+        merge_aba(*args[1:5])
+    elif args and args[0] == "--strict-leg":
+        print(json.dumps(run_strict_leg(args[1], int(args[2]) if len(args) > 2 else 2_000_000, int(args[3]) if len(args) > 3 else 5)))
     elif args and args[0] == "--one-push":
         from surge_amd.encode import JsonTemplate
 
@@ -192,4 +285,4 @@ if __name__ == "__main__":
     else:
         n = int(args[0]) if args else 2_000_000
         pairs = int(args[1]) if len(args) > 1 else 5
-        print(json.dumps(run(n, pairs)))
+        print(json.dumps(run_lenient(n, pairs) if lenient_run else run(n, pairs)))

@@ -79,9 +79,12 @@ REPLAY_H = {
     "surge_replay_encode_protobuf_state_rows": ([_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, ctypes.POINTER(_i64)], _i32),
     "surge_replay_decode_json_states": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, ctypes.POINTER(_i64 * 4)], _i32),
     "surge_replay_set_decode_base": ([_vp, _vp], _i32),
+    "surge_replay_set_decode_mode": ([_vp, _i32], _i32),
     "surge_replay_decode_protobuf_states": ([_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, ctypes.POINTER(_i64 * 4)], _i32),
     "surge_decode_json_state": ([_vp, _vp, _i64, _vp, _i64, _vp, _vp], _i32),
     "surge_decode_protobuf_state": ([_vp, _vp, _i64, _vp, _i64, _vp, _vp], _i32),
+    "surge_decode_json_state_lenient": ([_vp, _vp, _i64, _vp, _i64, _vp, _vp], _i32),
+    "surge_decode_protobuf_state_lenient": ([_vp, _vp, _i64, _vp, _i64, _vp, _vp], _i32),
     "surge_unescape_json_string": ([_vp, _i64, _vp, _i64], _i64),
     "surge_replay_merge_state_strings": ([_vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, ctypes.POINTER(_i64)], _i32),
     "surge_replay_pack_states": ([_vp, _vp, _i64, _vp, _vp], _i32),
@@ -232,7 +235,8 @@ SNAPSHOT_H = {
 }
 
 #: the host half of the state decoder (declared in ``include/surge_replay.h``; needs no handle and no device)
-STATE_EXPORTS = ("surge_decode_json_state", "surge_decode_protobuf_state", "surge_unescape_json_string")
+STATE_EXPORTS = ("surge_decode_json_state", "surge_decode_protobuf_state", "surge_decode_json_state_lenient", "surge_decode_protobuf_state_lenient",
+                 "surge_unescape_json_string")
 #: which event class carries which string (declared in ``include/surge_ingest.h`` beside the two exports that use it)
 EVENT_STRINGS_EXPORTS = ("surge_event_strings_validate",)
 #: what each header declares beside those

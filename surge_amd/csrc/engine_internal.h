@@ -161,6 +161,7 @@ struct surge_replay_handle {
   DevBuf f64_tables, nan_count;
   DevBuf rows_off;                       // surge_replay_encode_json_rows: lengths, then offsets, of the rows asked for
   alignas(16) uint8_t decode_base[64] = {};       // surge_replay_set_decode_base: what a decoded row's unnamed bytes hold
+  int32_t decode_mode = SURGE_STATE_READ_STRICT;  // surge_replay_set_decode_mode
   DevBuf sd_ptab, sd_counts, sd_last, sd_status;  // surge_replay_decode_json_states: parse table, counters, last record per aggregate, statuses
 
   surge::CommState* comm = nullptr;  // the snapshot exchange (comm.hip), created by surge_replay_comm_init

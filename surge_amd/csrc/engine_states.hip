@@ -247,6 +247,13 @@ int32_t surge_replay_set_decode_base(surge_replay_handle* h, const void* state64
   return SURGE_OK;
 }
 
+int32_t surge_replay_set_decode_mode(surge_replay_handle* h, int32_t mode) {
+  if (!h) return fail(nullptr, SURGE_E_INVALID, "handle is NULL");
+  if (mode != SURGE_STATE_READ_STRICT && mode != SURGE_STATE_READ_LENIENT) return fail(h, SURGE_E_INVALID, "unknown decode mode (SURGE_STATE_READ_*)");
+  h->decode_mode = mode;
+  return SURGE_OK;
+}
+
 // envelope: every value is a protobuf State message around the template's text (surge_replay_decode_protobuf_states)
 static int32_t decode_states(surge_replay_handle* h, const surge_json_template* tmpl, const uint8_t* d_values, const int64_t* d_value_off,
                              int64_t n_records, const uint8_t* d_keys_utf8, const int64_t* d_key_off, const int64_t* d_agg_idx, int64_t n_agg,
@@ -254,6 +261,13 @@ static int32_t decode_states(surge_replay_handle* h, const surge_json_template* 
   if (!h) return fail(nullptr, SURGE_E_INVALID, "handle is NULL");
   if (h->v2) return fail(h, SURGE_E_UNSUPPORTED, envelope ? "decode_protobuf_states serves ABI v1 handles (a slot schema keeps its presence word elsewhere)" : "decode_json_states serves ABI v1 handles (a slot schema keeps its presence word elsewhere)");
   if (const char* why = state_template_problem(tmpl)) return fail(h, SURGE_E_INVALID, why);
+  const bool lenient = h->decode_mode == SURGE_STATE_READ_LENIENT;
+  StateFieldTable fields{};
+  if (lenient) {  // the template as the lenient parser reads it: refused here, before anything is launched
+    uint32_t bad_part = 0;
+    if (const char* why = state_field_table(tmpl, &fields, &bad_part))
+      return fail(h, SURGE_E_UNSUPPORTED, std::string("the lenient decode mode cannot read this template: ") + why + " (part " + std::to_string(bad_part) + ")");
+  }
   if (!counts_out) return fail(h, SURGE_E_INVALID, "counts_out is NULL");
   counts_out[0] = counts_out[1] = counts_out[2] = counts_out[3] = 0;
   if (n_records < 0 || n_agg < 0) return fail(h, SURGE_E_INVALID, "negative size");
@@ -280,6 +294,7 @@ static int32_t decode_states(surge_replay_handle* h, const surge_json_template* 
   p.ptab = (const F64ParseTable*)h->sd_ptab.ptr;
   p.counts = (unsigned long long*)h->sd_counts.ptr;
   p.envelope = envelope;
+  p.lenient = lenient;
   // the base row, without the bytes the template names and the flags word: the kernel ORs it into the parsed row
   alignas(16) uint8_t base[64];
   std::memcpy(base, h->decode_base, 64);
@@ -294,7 +309,7 @@ static int32_t decode_states(surge_replay_handle* h, const surge_json_template* 
   const bool resident = h->d_state && s0 < h->d_state + h->n_agg * 4 && h->d_state < s0 + n_agg * 4;
   std::unique_lock<std::shared_mutex> lk(h->mu, std::defer_lock);
   if (resident) lk.lock();
-  HIPCHK(h, launch_state_decode(*tmpl, p, h->stream));
+  HIPCHK(h, launch_state_decode(*tmpl, p, h->stream, lenient ? &fields : nullptr));
   unsigned long long c[SD_N_COUNTS] = {0};
   HIPCHK(h, hipMemcpyAsync(c, p.counts, sizeof(c), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -334,7 +349,9 @@ static int32_t decode_states(surge_replay_handle* h, const surge_json_template* 
       alignas(16) uint8_t row[64];
       int64_t span[2 * SURGE_JSON_STRING_COLUMNS];
       // (in envelope mode the span comes back relative to the value, as the kernel reports it)
-      const int32_t rc = (envelope ? surge_decode_protobuf_state : surge_decode_json_state)(tmpl, text.data(), (int64_t)text.size(), key.data(), key_len, row, span);
+      const auto host_decode = lenient ? (envelope ? surge_decode_protobuf_state_lenient : surge_decode_json_state_lenient)
+                                       : (envelope ? surge_decode_protobuf_state : surge_decode_json_state);
+      const int32_t rc = host_decode(tmpl, text.data(), (int64_t)text.size(), key.data(), key_len, row, span);
       const uint8_t st = (uint8_t)(rc < 0 ? SURGE_STATE_DECODE_NUMBER : rc);
       if (rc == SURGE_STATE_DECODE_OK) {
         for (int b = 0; b < 64; ++b) row[b] |= base[b];

@@ -198,8 +198,10 @@ struct StateDecodeParams {
   const F64ParseTable* ptab;    // device copy of the Eisel-Lemire table (f64_parse.h)
   unsigned long long* counts;   // SD_N_COUNTS entries
   bool envelope;                // every value is a protobuf State message around the template's text (the same for the whole launch)
+  bool lenient;                 // the lenient reading mode (surge_replay_set_decode_mode; likewise the same for the whole launch)
 };
-hipError_t launch_state_decode(const surge_json_template& tmpl, const StateDecodeParams& p, hipStream_t stream);
+struct StateFieldTable;  // state_parse.h
+hipError_t launch_state_decode(const surge_json_template& tmpl, const StateDecodeParams& p, hipStream_t stream, const StateFieldTable* fields = nullptr);
 // ---- state_strings.hip: the STR spans of decoded state values -> a side string column (surge_replay_merge_state_strings) ----
 struct StateStringsParams {
   const uint8_t* values;        // record r's text: values[value_off[r] .. value_off[r + 1])  (NULL: every value is empty)

@@ -10,9 +10,12 @@
 // once the whole value has parsed; a value that does not parse leaves the row alone.
 // state_decode_kernel<true> is the same kernel for values in the multilanguage module's protobuf State envelope
 // (surge_replay_decode_protobuf_states; state_parse_protobuf_state in state_parse.h): chosen at the launch, the envelope
-// being the same for every record of it.
+// being the same for every record of it.  state_decode_kernel<*, true> reads in the lenient mode (surge_replay_set_decode_mode;
+// state_parse_json_lenient): the parse call is the one thing that differs, and the template's field table is one more argument.
 #include "replay_internal.h"
 #include "state_parse.h"
+
+#include <type_traits>
 
 namespace surge {
 namespace {
@@ -40,8 +43,11 @@ __device__ __forceinline__ void count_lanes(bool pred, unsigned long long* count
   if (m && (threadIdx.x & (warpSize - 1)) == (unsigned)(__ffsll((long long)m) - 1)) atomicAdd(counter, (unsigned long long)__popcll(m));
 }
 
-template <bool ENVELOPE>
-__global__ void __launch_bounds__(kSdBlock) state_decode_kernel(const surge_json_template t, const StateDecodeParams p) {
+struct SdNoFields {};  // what a strict instantiation takes where a lenient one takes the field table
+
+template <bool ENVELOPE, bool LENIENT>
+__global__ void __launch_bounds__(kSdBlock) state_decode_kernel(const surge_json_template t, const StateDecodeParams p,
+                                                                const std::conditional_t<LENIENT, StateFieldTable, SdNoFields> fields) {
   extern __shared__ __attribute__((aligned(16))) uint8_t sd_lds[];
   uint8_t* const rows = sd_lds;                 // 256 x 64 B: every lane's row while it parses
   uint8_t* const stage = sd_lds + kSdRowBytes;  // the block's values
@@ -88,8 +94,13 @@ __global__ void __launch_bounds__(kSdBlock) state_decode_kernel(const surge_json
         const int64_t key_len = p.key_off ? p.key_off[a + 1] - p.key_off[a] : -1;
         uint8_t* row = rows + threadIdx.x * 64;
         int64_t* span = p.spans ? p.spans + r * (2 * SURGE_JSON_STRING_COLUMNS) : nullptr;
-        if constexpr (ENVELOPE) rc = state_parse_protobuf_state<false>(t, v, o1 - o0, key, key_len, p.ptab, row, span);
-        else rc = state_parse_json<false>(t, v, o1 - o0, key, key_len, p.ptab, row, span);
+        if constexpr (LENIENT) {
+          if constexpr (ENVELOPE) rc = state_parse_protobuf_state_lenient<false>(t, fields, v, o1 - o0, key, key_len, p.ptab, row, span);
+          else rc = state_parse_json_lenient<false>(t, fields, v, o1 - o0, key, key_len, p.ptab, row, span);
+        } else {
+          if constexpr (ENVELOPE) rc = state_parse_protobuf_state<false>(t, v, o1 - o0, key, key_len, p.ptab, row, span);
+          else rc = state_parse_json<false>(t, v, o1 - o0, key, key_len, p.ptab, row, span);
+        }
         if (rc == SURGE_STATE_DECODE_OK) {
           const uint4* lr = (const uint4*)row;
 #pragma unroll
@@ -117,7 +128,9 @@ constexpr size_t kSdLdsBytes = (size_t)kSdRowBytes + kSdStageBytes + 16;
 }  // namespace
 
 // p.counts: SD_N_COUNTS u64 (zeroed here, SD_FIRST_REFUSED to ~0); p.last1: n_agg u64 of scratch when p.agg_idx is given
-hipError_t launch_state_decode(const surge_json_template& tmpl, const StateDecodeParams& p, hipStream_t stream) {
+// fields: the template's field table (state_field_table), read when p.lenient
+hipError_t launch_state_decode(const surge_json_template& tmpl, const StateDecodeParams& p, hipStream_t stream, const StateFieldTable* fields) {
+  if (p.lenient && !fields) return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(p.counts, 0, SD_N_COUNTS * 8, stream);
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(p.counts + SD_FIRST_REFUSED, 0xFF, 8, stream);
@@ -128,8 +141,13 @@ hipError_t launch_state_decode(const surge_json_template& tmpl, const StateDecod
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(state_last_record_kernel, dim3(blocks), dim3(kSdBlock), 0, stream, p.agg_idx, p.n_records, p.n_agg, p.last1, p.counts);
   }
-  if (p.envelope) hipLaunchKernelGGL(state_decode_kernel<true>, dim3(blocks), dim3(kSdBlock), kSdLdsBytes, stream, tmpl, p);
-  else hipLaunchKernelGGL(state_decode_kernel<false>, dim3(blocks), dim3(kSdBlock), kSdLdsBytes, stream, tmpl, p);
+  if (p.lenient) {
+    if (p.envelope) hipLaunchKernelGGL((state_decode_kernel<true, true>), dim3(blocks), dim3(kSdBlock), kSdLdsBytes, stream, tmpl, p, *fields);
+    else hipLaunchKernelGGL((state_decode_kernel<false, true>), dim3(blocks), dim3(kSdBlock), kSdLdsBytes, stream, tmpl, p, *fields);
+  } else {
+    if (p.envelope) hipLaunchKernelGGL((state_decode_kernel<true, false>), dim3(blocks), dim3(kSdBlock), kSdLdsBytes, stream, tmpl, p, SdNoFields{});
+    else hipLaunchKernelGGL((state_decode_kernel<false, false>), dim3(blocks), dim3(kSdBlock), kSdLdsBytes, stream, tmpl, p, SdNoFields{});
+  }
   return hipGetLastError();
 }
 

@@ -337,4 +337,351 @@ SURGE_HD int state_parse_protobuf_state(const surge_json_template& t, const uint
   return SURGE_STATE_DECODE_OK;
 }
 
+// ---- the lenient reading mode: what `Json.parse(bytes).asOpt[State]` takes ------------------------------------------------
+// Every readState of the reference parses the bytes into a JSON tree and reads the case class out of it by name
+// (TestBoundedContext.scala:156, scaladsl/TestBoundedContext.scala:131-132, BankAccountSurgeModel.scala:23, and the
+// multilanguage side on pbState.payload): that reader takes the members in any order, insignificant whitespace, and members
+// the case class does not know (a field a later release added, or an SDK application's own JSON library).  The strict parser
+// above stays the default; this one reads the same template through a table of its fields:
+//   - optional whitespace (0x20 \t \n \r) around every token, in front of the object and behind it; the top level must be an
+//     object, else SYNTAX; bytes other than whitespace behind its closing brace are TRAILING;
+//   - a member name is a JSON string by sp_string's rules ("count" names count) and is compared unescaped;
+//   - a member the table knows is parsed by the routine the strict parser uses for its kind and reports that routine's
+//     status (`null` is therefore INT / NUMBER / STRING by kind; KEY is compared with the id when a key is given);
+//   - a name that occurs more than once: every occurrence is parsed and a refused one refuses the value, the last one gives
+//     the field and the STR span.  play-json's map and Python's json.loads both keep the last and never look at the earlier
+//     ones: refusing a bad earlier occurrence is narrower than either;
+//   - a member the table does not know is skipped and validated as JSON (strings: no raw byte below 0x20, the escapes
+//     \" \\ \/ \b \f \n \r \t and \u + four hex digits — surrogates pass, nothing is unescaped; numbers
+//     -?(0|[1-9][0-9]*)(\.[0-9]+)?([eE][+-]?[0-9]+)?; true / false / null; arrays and objects to a nesting depth of 32 below
+//     the top-level object, kept in a 32-bit stack of kinds: no recursion, nothing indexed per lane); deeper nesting and
+//     anything malformed are SYNTAX;
+//   - when the object closes, a field of the table that never occurred is MISSING (Json.format gives None there).
+// Unchanged: the integer rule is -?[0-9]+ (play-json would also take 1.0 or 1e2 for an Int); POISONED and the sign of -0.0
+// are not restored; bytes from 0x80 on are not checked as UTF-8.  The two promises hold as above: nothing at or beyond
+// value + len is read, nothing but row[0 .. 64) and span[0 .. 8) is written.
+
+constexpr uint32_t kStateMaxFields = (SURGE_JSON_MAX_PARTS - 1) / 2;  // LITERAL value LITERAL value ... LITERAL
+
+// The template as the lenient parser reads it: per field its name (a span of template.literals), its part kind and the
+// part's field_offset.  Built on the host once per call (state_field_table), passed to the kernel by value.
+struct StateFieldTable {
+  uint32_t n_fields;
+  struct { uint32_t name_off, name_len, kind, field_offset; } field[kStateMaxFields];
+};
+
+// 0 = `t` (already consistent: state_template_problem) has the shape the lenient parser can read and *tab describes it: the
+// parts alternate LITERAL, value, ..., LITERAL; the first literal is {"<name>": each inner one ,"<name>": the last one } ;
+// a name has at least one byte, no backslash and no quote; no two names are equal.  Else a message, and *bad_part = the part
+// that did not fit.
+inline const char* state_field_table(const surge_json_template* t, StateFieldTable* tab, uint32_t* bad_part) {
+  *tab = StateFieldTable{};
+  *bad_part = 0;
+  if (t->n_parts < 3 || t->n_parts % 2 == 0) {
+    *bad_part = t->n_parts ? t->n_parts - 1 : 0;
+    return "the parts do not alternate LITERAL, value, ..., LITERAL";
+  }
+  for (uint32_t p = 0; p < t->n_parts; ++p) {
+    *bad_part = p;
+    const auto& pt = t->part[p];
+    if ((p % 2 == 0) != (pt.kind == SURGE_JP_LITERAL)) return "the parts do not alternate LITERAL, value, ..., LITERAL";
+    if (pt.kind != SURGE_JP_LITERAL) continue;
+    const uint8_t* s = t->literals + pt.lit_off;
+    if (p == t->n_parts - 1) {
+      if (pt.lit_len != 1 || s[0] != '}') return "the last literal is not }";
+      continue;
+    }
+    // {"<name>":  or  ,"<name>":
+    if (pt.lit_len < 5 || s[0] != (p == 0 ? '{' : ',') || s[1] != '"' || s[pt.lit_len - 2] != '"' || s[pt.lit_len - 1] != ':')
+      return p == 0 ? "the first literal is not {\"<name>\":" : "an inner literal is not ,\"<name>\":";
+    const uint32_t no = pt.lit_off + 2, nl = pt.lit_len - 4;
+    for (uint32_t b = 0; b < nl; ++b)
+      if (t->literals[no + b] == '"' || t->literals[no + b] == '\\') return "a field name holds a quote or a backslash";
+    for (uint32_t f = 0; f < tab->n_fields; ++f) {
+      bool same = tab->field[f].name_len == nl;
+      for (uint32_t b = 0; same && b < nl; ++b) same = t->literals[tab->field[f].name_off + b] == t->literals[no + b];
+      if (same) return "two fields have the same name";
+    }
+    auto& fd = tab->field[tab->n_fields++];
+    fd.name_off = no;
+    fd.name_len = nl;
+    fd.kind = t->part[p + 1].kind;
+    fd.field_offset = t->part[p + 1].field_offset;
+  }
+  *bad_part = 0;
+  return nullptr;
+}
+
+SURGE_HD int64_t sp_skip_ws(const uint8_t* v, int64_t len, int64_t i) {
+  while (i < len && (v[i] == ' ' || v[i] == '\t' || v[i] == '\n' || v[i] == '\r')) ++i;
+  return i;
+}
+
+// A JSON string that is only validated (the opening quote is v[*pos]): SYNTAX for whatever is not one.
+SURGE_HD int sp_skip_string(const uint8_t* v, int64_t len, int64_t* pos) {
+  int64_t i = *pos;
+  if (i >= len || v[i] != '"') return SURGE_STATE_DECODE_SYNTAX;
+  ++i;
+  while (true) {
+    if (i >= len) return SURGE_STATE_DECODE_SYNTAX;
+    const uint32_t c = v[i++];
+    if (c == '"') break;
+    if (c < 0x20u) return SURGE_STATE_DECODE_SYNTAX;
+    if (c != '\\') continue;
+    if (i >= len) return SURGE_STATE_DECODE_SYNTAX;
+    const uint32_t e = v[i++];
+    if (e == 'u') {
+      if (len - i < 4) return SURGE_STATE_DECODE_SYNTAX;
+      for (int d = 0; d < 4; ++d)
+        if (sp_hex(v[i + d]) < 0) return SURGE_STATE_DECODE_SYNTAX;
+      i += 4;
+    } else if (!(e == '"' || e == '\\' || e == '/' || e == 'b' || e == 'f' || e == 'n' || e == 'r' || e == 't')) {
+      return SURGE_STATE_DECODE_SYNTAX;
+    }
+  }
+  *pos = i;
+  return SURGE_STATE_DECODE_OK;
+}
+
+// -?(0|[1-9][0-9]*)(\.[0-9]+)?([eE][+-]?[0-9]+)? at v[*pos]; what follows it is the caller's to judge
+SURGE_HD int sp_skip_number(const uint8_t* v, int64_t len, int64_t* pos) {
+  int64_t i = *pos;
+  if (i < len && v[i] == '-') ++i;
+  if (i >= len || v[i] < '0' || v[i] > '9') return SURGE_STATE_DECODE_SYNTAX;
+  if (v[i] == '0') ++i;
+  else while (i < len && v[i] >= '0' && v[i] <= '9') ++i;
+  if (i < len && v[i] == '.') {
+    ++i;
+    if (i >= len || v[i] < '0' || v[i] > '9') return SURGE_STATE_DECODE_SYNTAX;
+    while (i < len && v[i] >= '0' && v[i] <= '9') ++i;
+  }
+  if (i < len && (v[i] == 'e' || v[i] == 'E')) {
+    ++i;
+    if (i < len && (v[i] == '+' || v[i] == '-')) ++i;
+    if (i >= len || v[i] < '0' || v[i] > '9') return SURGE_STATE_DECODE_SYNTAX;
+    while (i < len && v[i] >= '0' && v[i] <= '9') ++i;
+  }
+  *pos = i;
+  return SURGE_STATE_DECODE_OK;
+}
+
+// the word w[0 .. n) at v[*pos]
+SURGE_HD int sp_skip_word(const uint8_t* v, int64_t len, int64_t* pos, uint32_t w, int n) {  // w: the word's bytes, first byte lowest
+  if (len - *pos < n) return SURGE_STATE_DECODE_SYNTAX;
+  for (int b = 0; b < n; ++b)
+    if (v[*pos + b] != ((w >> (8 * b)) & 0xFFu)) return SURGE_STATE_DECODE_SYNTAX;
+  *pos += n;
+  return SURGE_STATE_DECODE_OK;
+}
+
+// Any JSON value at v[*pos] (whitespace in front of it allowed), validated and passed over; *pos ends behind it.  Containers
+// are walked with a stack of kinds in one 32-bit word (bit 0 = the innermost: 1 object, 0 array) to a depth of 32.
+SURGE_HD int sp_skip_value(const uint8_t* v, int64_t len, int64_t* pos) {
+  uint32_t stack = 0, depth = 0;
+  int64_t i = *pos;
+  while (true) {
+    // a value is expected
+    i = sp_skip_ws(v, len, i);
+    if (i >= len) return SURGE_STATE_DECODE_SYNTAX;
+    const uint32_t c = v[i];
+    int rc = SURGE_STATE_DECODE_OK;
+    bool opened = false;
+    if (c == '{' || c == '[') {
+      if (depth == 32u) return SURGE_STATE_DECODE_SYNTAX;
+      const bool obj = c == '{';
+      stack = (stack << 1) | (obj ? 1u : 0u);
+      ++depth;
+      i = sp_skip_ws(v, len, i + 1);
+      if (i >= len) return SURGE_STATE_DECODE_SYNTAX;
+      if (v[i] == (obj ? '}' : ']')) {  // empty: closed at once
+        ++i;
+        stack >>= 1;
+        --depth;
+      } else {
+        opened = true;
+        if (obj) {  // the first member's name and colon; its value is the next round's
+          rc = sp_skip_string(v, len, &i);
+          if (rc != SURGE_STATE_DECODE_OK) return rc;
+          i = sp_skip_ws(v, len, i);
+          if (i >= len || v[i] != ':') return SURGE_STATE_DECODE_SYNTAX;
+          ++i;
+        }
+      }
+    } else if (c == '"') {
+      rc = sp_skip_string(v, len, &i);
+    } else if (c == '-' || (c >= '0' && c <= '9')) {
+      rc = sp_skip_number(v, len, &i);
+    } else if (c == 't') {
+      rc = sp_skip_word(v, len, &i, 0x65757274u, 4);
+    } else if (c == 'f') {
+      ++i;
+      rc = sp_skip_word(v, len, &i, 0x65736C61u, 4);
+    } else if (c == 'n') {
+      rc = sp_skip_word(v, len, &i, 0x6C6C756Eu, 4);
+    } else {
+      return SURGE_STATE_DECODE_SYNTAX;
+    }
+    if (rc != SURGE_STATE_DECODE_OK) return rc;
+    if (opened) continue;
+    // a value is complete: close what it completes, or go on to the next element
+    while (true) {
+      if (depth == 0u) {
+        *pos = i;
+        return SURGE_STATE_DECODE_OK;
+      }
+      i = sp_skip_ws(v, len, i);
+      if (i >= len) return SURGE_STATE_DECODE_SYNTAX;
+      const bool obj = (stack & 1u) != 0u;
+      const uint32_t d = v[i++];
+      if (d == (obj ? '}' : ']')) {
+        stack >>= 1;
+        --depth;
+        continue;
+      }
+      if (d != ',') return SURGE_STATE_DECODE_SYNTAX;
+      if (obj) {
+        i = sp_skip_ws(v, len, i);
+        rc = sp_skip_string(v, len, &i);
+        if (rc != SURGE_STATE_DECODE_OK) return rc;
+        i = sp_skip_ws(v, len, i);
+        if (i >= len || v[i] != ':') return SURGE_STATE_DECODE_SYNTAX;
+        ++i;
+      }
+      break;
+    }
+  }
+}
+
+// A member name (the opening quote is v[*pos]) by sp_string's rules, compared unescaped with every name of the table at
+// once: *field = the field it names, or -1.  The candidates are a bit mask; the table is read with indices that are the
+// same for every lane, the literals with the lane's own.
+SURGE_HD int sp_member_name(const surge_json_template& t, const StateFieldTable& tab, const uint8_t* v, int64_t len, int64_t* pos, int* field) {
+  int64_t i = *pos;
+  if (i >= len || v[i] != '"') return SURGE_STATE_DECODE_SYNTAX;
+  ++i;
+  uint32_t alive = (1u << tab.n_fields) - 1u;
+  uint32_t k = 0;  // unescaped bytes so far
+  while (true) {
+    if (i >= len) return SURGE_STATE_DECODE_STRING;
+    uint32_t c = v[i++];
+    if (c == '"') break;
+    uint32_t n_out = 1;
+    const int rc = sp_string_unit(v, len, &i, c, &c, &n_out);
+    if (rc != SURGE_STATE_DECODE_OK) return rc;
+    for (uint32_t b = 0; b < n_out; ++b) {
+      const uint32_t byte = sp_utf8_byte(c, n_out, b);
+      for (uint32_t f = 0; f < tab.n_fields; ++f)
+        if (((alive >> f) & 1u) && !(k < tab.field[f].name_len && t.literals[(tab.field[f].name_off + k) & 255u] == byte)) alive &= ~(1u << f);
+      ++k;
+    }
+  }
+  *field = -1;
+  for (uint32_t f = 0; f < tab.n_fields; ++f)
+    if (((alive >> f) & 1u) && tab.field[f].name_len == k) *field = (int)f;
+  *pos = i;
+  return SURGE_STATE_DECODE_OK;
+}
+
+// state_parse_json's arguments and the field table of `t` (state_field_table); the same results, for the wider grammar above.
+template <bool RESOLVE>
+SURGE_HD int state_parse_json_lenient(const surge_json_template& t, const StateFieldTable& tab, const uint8_t* v, int64_t len, const uint8_t* key,
+                                      int64_t key_len, const F64ParseTable* tb, uint8_t* row, int64_t* span) {
+  uint64_t* row8 = (uint64_t*)row;
+  for (int q = 0; q < 8; ++q) row8[q] = 0;
+  int64_t i = sp_skip_ws(v, len, 0);
+  if (i >= len || v[i] != '{') return SURGE_STATE_DECODE_SYNTAX;
+  i = sp_skip_ws(v, len, i + 1);
+  if (i >= len) return SURGE_STATE_DECODE_SYNTAX;
+  uint32_t seen = 0;
+  if (v[i] == '}') {
+    ++i;
+  } else {
+    while (true) {
+      int field = -1;
+      int rc = sp_member_name(t, tab, v, len, &i, &field);
+      if (rc != SURGE_STATE_DECODE_OK) return rc;
+      i = sp_skip_ws(v, len, i);
+      if (i >= len || v[i] != ':') return SURGE_STATE_DECODE_SYNTAX;
+      i = sp_skip_ws(v, len, i + 1);
+      if (field < 0) {
+        rc = sp_skip_value(v, len, &i);
+        if (rc != SURGE_STATE_DECODE_OK) return rc;
+      } else {
+        uint32_t kind = 0, off = 0;
+        for (uint32_t f = 0; f < tab.n_fields; ++f)  // (read with f, the same for every lane)
+          if ((int)f == field) { kind = tab.field[f].kind; off = tab.field[f].field_offset; }
+        seen |= 1u << field;
+        // (the three branches below restate state_parse_json's: sharing one routine between the two parsers changes the strict
+        // kernels' instruction streams, and those stay what they were)
+        if (kind == SURGE_JP_KEY || kind == SURGE_JP_STR) {
+          int64_t ro = 0, rl = 0;
+          rc = sp_string(v, len, &i, key, kind == SURGE_JP_KEY ? key_len : -1, &ro, &rl);
+          if (rc != SURGE_STATE_DECODE_OK) return rc;
+          if (kind == SURGE_JP_STR && span && off < SURGE_JSON_STRING_COLUMNS) { span[2 * off] = ro; span[2 * off + 1] = rl; }
+        } else if (kind == SURGE_JP_F64) {
+          int64_t e = i;
+          while (e < len && e - i < 400 && ((v[e] >= '0' && v[e] <= '9') || v[e] == '-' || v[e] == '+' || v[e] == '.' || v[e] == 'e' || v[e] == 'E')) ++e;
+          if (e - i >= 400) return SURGE_STATE_DECODE_NUMBER;
+          uint64_t bits = 0;
+          rc = f64_parse_json_number(v + i, (int)(e - i), tb, &bits);
+          if (rc == F64_PARSE_MALFORMED) return SURGE_STATE_DECODE_NUMBER;
+          if (rc == F64_PARSE_AMBIGUOUS) {
+#if !defined(__HIP_DEVICE_COMPILE__)
+            if (RESOLVE) {
+              if (surge_parse_f64_json(v + i, e - i, &bits) < 0) return SURGE_STATE_DECODE_NUMBER;
+            } else
+#endif
+              return SURGE_STATE_DECODE_AMBIGUOUS;
+          }
+          *(uint64_t*)(row + off) = bits;
+          i = e;
+        } else {
+          bool neg = false, over = false;
+          uint64_t mag = 0;
+          rc = sp_integer(v, len, &i, &neg, &mag, &over);
+          if (rc != SURGE_STATE_DECODE_OK) return rc;
+          if (kind == SURGE_JP_I32) {
+            if (over || mag > (neg ? 0x80000000ull : 0x7FFFFFFFull)) return SURGE_STATE_DECODE_RANGE;
+            *(uint32_t*)(row + off) = neg ? (uint32_t)0 - (uint32_t)mag : (uint32_t)mag;
+          } else if (kind == SURGE_JP_U32) {
+            if (over || mag > (neg ? 0ull : 0xFFFFFFFFull)) return SURGE_STATE_DECODE_RANGE;
+            *(uint32_t*)(row + off) = (uint32_t)mag;
+          } else {
+            if (over || mag > (neg ? 0x8000000000000000ull : 0x7FFFFFFFFFFFFFFFull)) return SURGE_STATE_DECODE_RANGE;
+            *(uint64_t*)(row + off) = neg ? (uint64_t)0 - mag : mag;
+          }
+        }
+      }
+      i = sp_skip_ws(v, len, i);
+      if (i >= len) return SURGE_STATE_DECODE_SYNTAX;
+      const uint32_t d = v[i++];
+      if (d == '}') break;
+      if (d != ',') return SURGE_STATE_DECODE_SYNTAX;
+      i = sp_skip_ws(v, len, i);
+    }
+  }
+  i = sp_skip_ws(v, len, i);
+  if (i != len) return SURGE_STATE_DECODE_TRAILING;
+  if (seen != (1u << tab.n_fields) - 1u) return SURGE_STATE_DECODE_MISSING;
+  *(uint32_t*)(row + 36) = SURGE_STATE_PRESENT;
+  return SURGE_STATE_DECODE_OK;
+}
+
+// sp_envelope unchanged in front of the lenient parser; the spans relative to v, as state_parse_protobuf_state reports them
+template <bool RESOLVE>
+SURGE_HD int state_parse_protobuf_state_lenient(const surge_json_template& t, const StateFieldTable& tab, const uint8_t* v, int64_t len,
+                                                const uint8_t* key, int64_t key_len, const F64ParseTable* tb, uint8_t* row, int64_t* span) {
+  int64_t pay_off = 0, pay_len = 0;
+  int rc = sp_envelope(v, len, key, key_len, &pay_off, &pay_len);
+  if (rc != SURGE_STATE_DECODE_OK) return rc;
+  rc = state_parse_json_lenient<RESOLVE>(t, tab, v + pay_off, pay_len, key, key_len, tb, row, span);
+  if (rc != SURGE_STATE_DECODE_OK || !span) return rc;
+  for (uint32_t c = 0; c < SURGE_JSON_STRING_COLUMNS; ++c) {  // (once per column, however many fields name it)
+    bool named = false;
+    for (uint32_t f = 0; f < tab.n_fields; ++f) named = named || (tab.field[f].kind == SURGE_JP_STR && tab.field[f].field_offset == c);
+    if (named) span[2 * c] += pay_off;
+  }
+  return SURGE_STATE_DECODE_OK;
+}
+
 }  // namespace surge

@@ -244,7 +244,7 @@ class DeviceDecoder:
             total = int(value_off[-1].item())
         return self._view(pa, (n.value,), "<i8"), self._view(pv, (total,), "|u1"), value_off, self._view(po, (n.value,), "<i8"), nk.value
 
-    def load_states_into(self, engine, template, envelope: str = "none"):
+    def load_states_into(self, engine, template, envelope: str = "none", lenient: bool = False):
         """A state decoder's hand-over (``surge_device_decoder_load_states``; ``envelope="protobuf_state"``:
         ``surge_device_decoder_load_protobuf_states``, the values are the multilanguage module's ``State`` messages around the
         template's text): everything delivered since the last clear is
@@ -252,11 +252,12 @@ class DeviceDecoder:
         — grown first for ids seen for the first time; per aggregate the last record wins, a tombstone zeroes the row — and
         the decoder is cleared.  Returns the decode's counts ``(rows written, tombstones, winners refused, Doubles re-parsed
         on the host)``; a refused winner raises ``IngestError`` (CORRUPT, naming the record's topic offset) after everything
-        else was loaded."""
+        else was loaded.  ``lenient``: the values are read in the engine's lenient mode (``ReplayEngine.reading_leniently``)."""
         fn = self._lib.surge_device_decoder_load_protobuf_states if check_envelope(envelope) else self._lib.surge_device_decoder_load_states
         counts = (ctypes.c_int64 * 4)()
         t = template.to_c()
-        rc = fn(self._h, engine._h, ctypes.byref(t), ctypes.byref(counts))
+        with engine.reading_leniently(lenient):
+            rc = fn(self._h, engine._h, ctypes.byref(t), ctypes.byref(counts))
         engine.n_agg = max(engine.n_agg, self.n_keys)  # (grown inside the call)
         self._check(rc)
         return tuple(int(c) for c in counts)

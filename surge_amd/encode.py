@@ -193,6 +193,8 @@ DECODE_STATUS = {0: "OK", 1: "LITERAL", 2: "STRING", 3: "ESCAPE", 4: "KEY_MISMAT
 DECODE_OK, DECODE_LITERAL, DECODE_STRING, DECODE_ESCAPE, DECODE_KEY_MISMATCH, DECODE_INT, DECODE_RANGE = 0, 1, 2, 3, 4, 5, 6
 DECODE_NUMBER, DECODE_TRAILING, DECODE_AMBIGUOUS, DECODE_SURROGATE, DECODE_SKIPPED = 7, 8, 9, 10, 255
 DECODE_ENVELOPE = 11
+DECODE_SYNTAX, DECODE_MISSING = 12, 13  # the lenient mode's own
+DECODE_STATUS.update({12: "SYNTAX", 13: "MISSING"})
 ENVELOPES = ("none", "protobuf_state")
 
 
@@ -211,31 +213,38 @@ class DecodedStates(tuple):
     refused = None
 
 
-def decode_state_host(template: JsonTemplate, value: bytes, key=None, envelope: str = "none"):
+def decode_state_host(template: JsonTemplate, value: bytes, key=None, envelope: str = "none", lenient: bool = False):
     """One serialized state value on the host (``surge_decode_json_state``: the parser the device kernel runs;
     ``envelope="protobuf_state"``: ``surge_decode_protobuf_state``, the value is the multilanguage module's
     ``State{aggregateId, payload}`` message around the template's text, field 1 is compared with ``key`` byte for byte and the
     spans are relative to the whole value).  Returns
     ``(status, state, spans)``: a ``SURGE_STATE_DECODE_*`` status, the state (a one-element ``STATE_DTYPE`` array, zeros
     unless the status is 0) and ``spans[c] = (offset, length)`` of STR column ``c``'s still-escaped bytes.  ``key``
-    (``str`` or UTF-8 ``bytes``): the id the KEY string must equal; ``None``: not compared."""
+    (``str`` or UTF-8 ``bytes``): the id the KEY string must equal; ``None``: not compared.  ``lenient``: the lenient reading
+    mode (``surge_decode_json_state_lenient`` / ``surge_decode_protobuf_state_lenient``: members in any order, whitespace,
+    unknown members skipped); a template it cannot read raises ``ValueError``."""
     from .schema import STATE_DTYPE
 
     lib = _native.load()
-    fn = lib.surge_decode_protobuf_state if check_envelope(envelope) else lib.surge_decode_json_state
+    if lenient:
+        fn = lib.surge_decode_protobuf_state_lenient if check_envelope(envelope) else lib.surge_decode_json_state_lenient
+    else:
+        fn = lib.surge_decode_protobuf_state if check_envelope(envelope) else lib.surge_decode_json_state
     t = template.to_c()
     value = bytes(value)
     kb = None if key is None else (key.encode("utf-8") if isinstance(key, str) else bytes(key))
     state = np.zeros(1, dtype=STATE_DTYPE)
     span = (ctypes.c_int64 * (2 * STRING_COLUMNS))()
     rc = fn(ctypes.byref(t), value, len(value), kb, -1 if kb is None else len(kb), state.ctypes.data_as(ctypes.c_void_p), span)
+    if rc == -5:  # SURGE_E_UNSUPPORTED
+        raise ValueError("the lenient mode reads templates of the shape {\"<name>\": value ,\"<name>\": value ... } with distinct names: not this one")
     if rc < 0:
         raise ValueError(("surge_decode_json_state" if envelope == "none" else "surge_decode_protobuf_state") + ": bad argument or inconsistent template")
     return rc, state, [(span[2 * c], span[2 * c + 1]) for c in range(STRING_COLUMNS)]
 
 
 def decode_states(engine: ReplayEngine, template: JsonTemplate, d_values, d_value_off, d_keys_utf8=None, d_key_off=None, d_agg_idx=None,
-                  out=None, want_spans: bool = False, raise_on_refused: bool = False, envelope: str = "none"):
+                  out=None, want_spans: bool = False, raise_on_refused: bool = False, envelope: str = "none", lenient: bool = False):
     """Decode state-topic record values on the device (``surge_replay_decode_json_states``; ``envelope="protobuf_state"``:
     ``surge_replay_decode_protobuf_states``, every value is a ``State{aggregateId, payload}`` message around the template's
     text and the spans are relative to the whole value): record ``r``'s text is
@@ -246,7 +255,7 @@ def decode_states(engine: ReplayEngine, template: JsonTemplate, d_values, d_valu
     record (CUDA) and ``counts = (rows written, tombstones, winners refused, Doubles re-parsed on the host)``; ``.spans`` of
     the result is the ``n_records x 4 x 2`` int64 CUDA tensor of STR spans when ``want_spans``.  Winners that do not decode
     are reported in ``counts`` (and ``.refused``), or raised as ``ReplayError`` (CORRUPT) with ``raise_on_refused``; any
-    other failure raises."""
+    other failure raises.  ``lenient``: the call reads in the lenient mode (``ReplayEngine.reading_leniently``)."""
     import torch
 
     lib = _native.load()
@@ -264,16 +273,19 @@ def decode_states(engine: ReplayEngine, template: JsonTemplate, d_values, d_valu
     counts = (ctypes.c_int64 * 4)()
     t = template.to_c()
     ptr = lambda x: ctypes.c_void_p(x.data_ptr()) if x is not None and x.numel() else None  # noqa: E731
-    rc = fn(
-        engine._h, ctypes.byref(t), ptr(d_values), ctypes.c_void_p(d_value_off.data_ptr()), n, ptr(d_keys_utf8),
-        ctypes.c_void_p(d_key_off.data_ptr()) if d_key_off is not None else None, ptr(d_agg_idx), n_agg, ctypes.c_void_p(out.data_ptr()),
-        ptr(status), ptr(spans), ctypes.byref(counts))
+    with engine.reading_leniently(lenient):
+        rc = fn(
+            engine._h, ctypes.byref(t), ptr(d_values), ctypes.c_void_p(d_value_off.data_ptr()), n, ptr(d_keys_utf8),
+            ctypes.c_void_p(d_key_off.data_ptr()) if d_key_off is not None else None, ptr(d_agg_idx), n_agg, ctypes.c_void_p(out.data_ptr()),
+            ptr(status), ptr(spans), ctypes.byref(counts))
+        msg = (lib.surge_replay_last_error(engine._h) or b"").decode() if rc else ""  # (before the mode is reset)
     res = DecodedStates((out, status, tuple(int(c) for c in counts)))
     res.spans = spans
     if rc == -7 and not raise_on_refused:  # SURGE_E_CORRUPT: everything else was decoded; counts[2] says how many were not
-        res.refused = (lib.surge_replay_last_error(engine._h) or b"").decode()
+        res.refused = msg
         return res
-    engine._check(rc)
+    if rc:
+        raise ReplayError(rc, msg)
     return res
 
 

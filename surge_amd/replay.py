@@ -102,6 +102,7 @@ class ReplayEngine:
         self.n_agg = 0
         self.state_dtype = algebra.state_dtype() if self.v2 else STATE_DTYPE  # numpy view of one 64-byte state
         self._keep = []  # tensors bound zero-copy must outlive the binding
+        self._reading_leniently = False  # reading_leniently(): the handle's decode mode, as this object set it
 
     # -- lifecycle -------------------------------------------------------------------------
     def close(self):
@@ -324,14 +325,32 @@ class ReplayEngine:
         return nv.value, nt.value
 
     @contextlib.contextmanager
-    def decoding_onto(self, defaults):
+    def decoding_onto(self, defaults, lenient: bool = False):
         """Inside the block the bytes a decoded state's template does not name are ``defaults``', a 64-byte ctypes state (an
-        algebra's ``to_c().default_state``: ``surge_replay_set_decode_base``); zeros again on the way out."""
+        algebra's ``to_c().default_state``: ``surge_replay_set_decode_base``); zeros again on the way out.  ``lenient``: the
+        block also reads in the lenient mode (``reading_leniently``)."""
         self._check(self._lib.surge_replay_set_decode_base(self._h, ctypes.byref(defaults)))
+        try:
+            with self.reading_leniently(lenient):
+                yield
+        finally:
+            self._check(self._lib.surge_replay_set_decode_base(self._h, None))
+
+    @contextlib.contextmanager
+    def reading_leniently(self, lenient: bool = True):
+        """Inside the block serialized states are read in the lenient mode (``surge_replay_set_decode_mode``: members in any
+        order, whitespace, unknown members skipped — what the reference's ``Json.parse(bytes).asOpt[State]`` takes); strict
+        again on the way out.  ``lenient=False`` changes nothing and calls nothing; blocks nest."""
+        if not lenient or self._reading_leniently:
+            yield
+            return
+        self._check(self._lib.surge_replay_set_decode_mode(self._h, 1))  # SURGE_STATE_READ_LENIENT
+        self._reading_leniently = True
         try:
             yield
         finally:
-            self._check(self._lib.surge_replay_set_decode_base(self._h, None))
+            self._reading_leniently = False
+            self._check(self._lib.surge_replay_set_decode_mode(self._h, 0))  # SURGE_STATE_READ_STRICT
 
     def get(self, agg_idx: int) -> Optional[np.ndarray]:
         """Fixed-width state of one aggregate, or ``None`` when it is absent (KTable miss)."""

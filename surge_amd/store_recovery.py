@@ -247,7 +247,7 @@ class TopicRecoveries:
             self.engine.snapshot()
         return dict(zip(("rows_written", "tombstones", "refused", "reparsed_on_host"), counts))
 
-    def restore_from_state_records(self, records, events_tail: Sequence = (), template=None, envelope: str = "none") -> dict:
+    def restore_from_state_records(self, records, events_tail: Sequence = (), template=None, envelope: str = "none", lenient: bool = False) -> dict:
         """Resume from the compacted *state* topic instead of replaying every event — what the reference's restore does
         (``SurgeStateStoreConsumer.scala:57-76``, records written by ``SurgeModel.scala:57-65``).  ``records``: ``(key,
         value_or_None)`` pairs or ``snapshot.StateRecord`` objects in offset order; per key the last record wins and
@@ -259,7 +259,10 @@ class TopicRecoveries:
         are not in the text and are not restored.  A winning value that does not decode raises ``ReplayError`` (CORRUPT).
         ``envelope="protobuf_state"``: the values are what a multilanguage (SDK) application stores, the protobuf
         ``State{aggregateId, payload}`` message around the template's text (``GenericSurgeCommandBusinessLogic.scala:25-27,
-        36-39``); any other field, order or repetition is refused, not skipped.  Returns the decoder's counts."""
+        36-39``); any other field, order or repetition is refused, not skipped.  ``lenient=True``: the texts are read as the
+        reference's ``Json.parse(bytes).asOpt[State]`` reads them — members in any order, whitespace between the tokens, members
+        the template does not name skipped (``surge_replay_set_decode_mode``); the default reads compact text in template order
+        only.  Returns the decoder's counts."""
         import torch
 
         check_envelope(envelope)
@@ -286,9 +289,9 @@ class TopicRecoveries:
             to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
             d_values = to_dev(np.frombuffer(b"".join(values), dtype=np.uint8).copy()) if off[-1] else torch.zeros(0, dtype=torch.uint8, device=dev)
             d_off, d_agg = to_dev(off), to_dev(np.asarray(agg_idx, dtype=np.int64))
-            with eng.decoding_onto(self.model.event_algebra().to_c().default_state):
+            with eng.decoding_onto(self.model.event_algebra().to_c().default_state, lenient=lenient):
                 res = decode_states(eng, template, d_values, d_off, to_dev(data), to_dev(key_off), d_agg,
-                                    out=eng.device_state(), want_spans=bool(str_columns), raise_on_refused=True, envelope=envelope)
+                                    out=eng.device_state(), want_spans=bool(str_columns), raise_on_refused=True, envelope=envelope, lenient=lenient)
             counts = res[2]
             if str_columns:  # the STR fields the values carry, kept beside the rows
                 self.state_strings = [merge_state_strings(eng, c, d_values, d_off, d_agg, res[1], res.spans, n_agg=n_agg) if c in str_columns else None
@@ -299,7 +302,7 @@ class TopicRecoveries:
 
     def restore_from_state_topic(self, fetches, n_partitions: int = 0, template=None, events_tail: Sequence = (), framing_threads: int = 4,
                                  device_crc: bool = True, in_place: bool = True, envelope: str = "none", events_fetches=None, events_from=None,
-                                 events_partitions: int = 0, host_keys: bool = True, keep_event_strings: bool = False) -> dict:
+                                 events_partitions: int = 0, host_keys: bool = True, keep_event_strings: bool = False, lenient: bool = False) -> dict:
         """``restore_from_state_records`` from what a consumer of the state topic actually receives: ``fetches`` yields the
         topic's bytes — message-format-v2 record batches, LZ4 or uncompressed, transactional, with the producer's flush
         records, tombstones as null values and the offset gaps log compaction leaves — one ``bytes`` per fetch, or with
@@ -307,7 +310,8 @@ class TopicRecoveries:
         ``restore_from_fetches``' (``FramedFetches`` / ``PartitionedFramedFetches``, ``read_committed``); a state-mode
         ``DeviceDecoder`` finds the records and interns the ids on the device (up to four pushes in flight; the oldest is
         finished, then loaded: ``load_states_into``) — no per-record work in Python.  The loaded states become the snapshot
-        baseline, then ``events_tail`` is folded on top, exactly as ``restore_from_state_records`` does (``envelope`` as there).
+        baseline, then ``events_tail`` is folded on top, exactly as ``restore_from_state_records`` does (``envelope`` and
+        ``lenient`` as there).
         ``events_fetches`` (instead of a non-empty ``events_tail``: both raise ``ValueError``) is the tail as BYTES — what a
         consumer of the events topic that seeks to ``events_from`` is sent, fetch by fetch, from the batch that contains each
         first offset on (``events_partitions`` as ``n_partitions``; ``events_from``: one first offset per events partition, or
@@ -361,10 +365,10 @@ class TopicRecoveries:
 
             def finish_one():  # the oldest push is finished, then loaded, BEFORE the next fetch is asked for
                 d.finish()
-                for i, c in enumerate(d.load_states_into(eng, template, envelope=envelope)):
+                for i, c in enumerate(d.load_states_into(eng, template, envelope=envelope, lenient=lenient)):
                     totals[i] += c
 
-            with eng.decoding_onto(self.model.event_algebra().to_c().default_state):
+            with eng.decoding_onto(self.model.event_algebra().to_c().default_state, lenient=lenient):
                 with _pushes_driven(_framer(fetches, n_partitions, framing_threads, depth, True, device_crc, in_place), push, finish_one, depth, lambda: d) as framed:
                     counters = framed.counters()
             counters.update(d.counters())
