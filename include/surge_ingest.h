@@ -289,7 +289,7 @@ int32_t surge_ingest_use_pinned_arena(surge_ingest* g);
 
 typedef struct surge_device_decoder surge_device_decoder;
 /* (Calls on the same decoder must not overlap, with one exception made for throughput: ONE thread may enqueue pushes
- * (push_async / push_parts_async) while ONE other thread finishes them and consumes the results (push_finish*, result,
+ * (push_async / push_parts_async / push_records_async) while ONE other thread finishes them and consumes the results (push_finish*, result,
  * clear, surge_replay_append_decoded*): the host work of framing tables and launches of fetch i + depth then runs beside
  * the interning and the fold of fetch i.) */
 /* tmpl == NULL: record values are 16-byte surge_event16; otherwise the reference's JSON event text, decoded by the
@@ -373,6 +373,22 @@ int32_t surge_device_decoder_push_parts_floored_async(surge_device_decoder* d, i
 int32_t surge_device_decoder_push_floored(surge_device_decoder* d, const uint8_t* bytes, const surge_batch_section* sections, int64_t n_sections, int64_t n_floors,
                                           const surge_section_floor* floors);
 int32_t surge_device_decoder_below_floor(const surge_device_decoder* d, int64_t* n_out); /* records passed over below a floor so far */
+/* Stage 1 of a push of records that are ALREADY FRAMED (surge_device_decoder_push_records below: a KafkaConsumer's poll — key
+ * bytes, value bytes and an offset per record), enqueued on the next free slot: the copy to the device and the record stage —
+ * the key cut at its ':' and hashed, the value decoded — run on a stream of their own, and the call returns.  Arguments and
+ * refusals are push_records' (spans that run backwards and n >= 2^32 - 1 are refused before any launch; a NULL decoder).  It
+ * takes one of the five slots: wire pushes and records pushes may be in flight in any mix (a sixth: SURGE_E_STATE), and
+ * push_finish / push_finish_async finish the OLDEST push whatever its kind, with what the synchronous call would have returned;
+ * results are appended in push order.  UNLIKE push_async, which reads `bytes` and `sections` until the matching push_finish,
+ * this call copies keys, key_off, values, value_off and offsets into the slot's page-locked staging before it returns: the
+ * caller's arrays may be reused or freed as soon as it has returned (a JVM caller releases its pinned arrays right behind the
+ * call).  n == 0 returns SURGE_OK and occupies no slot — there is nothing to finish —, and so does a call that fails.  Works on
+ * every kind of decoder as push_records does: events (bare, enveloped and 16-byte values, kept event strings), states (the id
+ * is the whole key, an empty value is the tombstone, the values are gathered at the finish) and a state decoder that continued
+ * as an events decoder.  No floors, as push_records:
+ *     loop over the polls: push_records_async(poll i + 4); push_finish_async() -> surge_replay_append_decoded_async (poll i) */
+int32_t surge_device_decoder_push_records_async(surge_device_decoder* d, const uint8_t* keys, const int64_t* key_off, const uint8_t* values,
+                                                const int64_t* value_off, const int64_t* offsets, int64_t n);
 int32_t surge_device_decoder_push_finish(surge_device_decoder* d);
 /* push_finish without its closing wait for the device: the results are complete in the order of the decoder's stream
  * (hand them over with surge_replay_append_decoded_async, or synchronise that stream before reading them).  The one
@@ -386,7 +402,8 @@ int32_t surge_device_decoder_reserve(surge_device_decoder* d, int64_t n_keys, in
 /* The same for records that arrive already framed — what a JVM's KafkaConsumer hands over (ConsumerRecord key / value
  * bytes and offset): record i's key is keys[key_off[i] .. key_off[i+1]), its value values[value_off[i] .. value_off[i+1]),
  * offsets nullable (then 0, 1, 2 ..).  A record with an empty key AND an empty value is the producer's flush record and
- * is skipped, as in the wire path. */
+ * is skipped, as in the wire path.  Synchronous: push_records_async, then push_finish, when nothing is pending (SURGE_E_STATE
+ * while a push is). */
 int32_t surge_device_decoder_push_records(surge_device_decoder* d, const uint8_t* keys, const int64_t* key_off, const uint8_t* values,
                                           const int64_t* value_off, const int64_t* offsets, int64_t n);
 /* Everything appended since the last clear: device arrays of n_records entries (valid until the next push / clear). */

@@ -144,6 +144,7 @@ INGEST_H = {
     "surge_device_decoder_last_error": ([_vp], ctypes.c_char_p),
     "surge_device_decoder_push": ([_vp, _vp, _vp, _i64], _i32),
     "surge_device_decoder_push_records": ([_vp, _vp, _vp, _vp, _vp, _vp, _i64], _i32),
+    "surge_device_decoder_push_records_async": ([_vp, _vp, _vp, _vp, _vp, _vp, _i64], _i32),
     "surge_device_decoder_push_async": ([_vp, _vp, _vp, _i64], _i32),
     "surge_device_decoder_push_parts_async": ([_vp, _i32, _vp, _vp, _vp], _i32),
     "surge_device_decoder_push_parts_floored_async": ([_vp, _i32, _vp, _vp, _vp, _i64, _vp], _i32),

@@ -398,15 +398,25 @@ int32_t surge_device_decoder_continue_as_events(surge_device_decoder* d, const s
   return OK;
 }
 
+// Stage 1 of a push of framed records on the next free slot.  stage1_records copies the caller's arrays into the slot's
+// page-locked staging before it returns, so — unlike a wire push — nothing of the caller's is read behind this call.
+int32_t surge_device_decoder_push_records_async(surge_device_decoder* d, const uint8_t* keys, const int64_t* key_off, const uint8_t* values,
+                                                const int64_t* value_off, const int64_t* offsets, int64_t n) {
+  if (!d) return refuse_null_decoder();
+  if (n < 0 || (n > 0 && (!key_off || !value_off))) return dfail(d, E_INVALID, "bad argument");
+  if (n == 0) return OK;  // (no slot: there is nothing to finish)
+  DeviceScope scope(d->device);
+  return enqueue_push(d, [&](PushSlot& s) { return stage1_records(d, s, keys, key_off, values, value_off, offsets, n); });
+}
+
 int32_t surge_device_decoder_push_records(surge_device_decoder* d, const uint8_t* keys, const int64_t* key_off, const uint8_t* values,
                                           const int64_t* value_off, const int64_t* offsets, int64_t n) {
   if (!d) return refuse_null_decoder();
   if (n < 0 || (n > 0 && (!key_off || !value_off))) return dfail(d, E_INVALID, "bad argument");
   if (d->n_pending != 0) return refuse_pending(d, kPushOrder);
   if (n == 0) return OK;
-  DeviceScope scope(d->device);
-  const int32_t rc = enqueue_push(d, [&](PushSlot& s) { return stage1_records(d, s, keys, key_off, values, value_off, offsets, n); });
-  return rc != OK ? rc : finish_oldest(d, true);
+  const int32_t rc = surge_device_decoder_push_records_async(d, keys, key_off, values, value_off, offsets, n);
+  return rc != OK ? rc : surge_device_decoder_push_finish(d);
 }
 
 int32_t surge_device_decoder_result(surge_device_decoder* d, int64_t* n_records, const int64_t** d_agg_idx, const void** d_events16,

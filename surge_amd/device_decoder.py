@@ -13,6 +13,43 @@ from .ingest_types import FLOOR_DTYPE, NO_FLOORS, SECTION_DTYPE, EventJsonTempla
 from .replay import device_view
 
 
+def _record_table(items, what: str):
+    """``(data_uint8, off_int64)`` of one side of a poll: a list of ``bytes`` (``None``: empty) joined, or the pair of arrays as
+    it is — contiguous, ``off`` inside ``data``."""
+    if isinstance(items, tuple) and len(items) == 2 and isinstance(items[1], np.ndarray):
+        data, off = np.ascontiguousarray(items[0], dtype=np.uint8).reshape(-1), np.ascontiguousarray(items[1], dtype=np.int64).reshape(-1)
+        if off.shape[0] < 1:
+            raise ValueError(f"push_records: {what} offsets need n + 1 entries (got none)")
+        if off[0] < 0 or off[-1] < off[0] or off[-1] > data.shape[0]:
+            raise ValueError(f"push_records: {what} offsets [{int(off[0])}, {int(off[-1])}] do not lie inside the {data.shape[0]} bytes given")
+        return (data if data.shape[0] else np.zeros(1, np.uint8)), off
+    items = [b"" if x is None else x for x in items]
+    off = np.zeros(len(items) + 1, dtype=np.int64)
+    if items:
+        np.cumsum([len(x) for x in items], out=off[1:])
+    return (np.frombuffer(b"".join(items), dtype=np.uint8) if off[-1] else np.zeros(1, np.uint8)), off
+
+
+def records_arguments(keys, values, offsets=None):
+    """What ``surge_device_decoder_push_records[_async]`` takes behind the handle, for a poll in either form (lists of
+    ``bytes``, or ``(data_uint8, off_int64)`` arrays): ``((keys, key_off, values, value_off, offsets, n), arrays)`` — the
+    pointers as ``c_void_p`` and the arrays they point into, to be held until the call has returned.  A poll whose sides
+    differ in length, or whose offsets are not one per record, raises ``ValueError`` before the library is touched."""
+    kd, ko = _record_table(keys, "key")
+    vd, vo = _record_table(values, "value")
+    n = ko.shape[0] - 1
+    if vo.shape[0] - 1 != n:
+        raise ValueError(f"push_records: {n} keys for {vo.shape[0] - 1} values")
+    of = None
+    if offsets is not None:
+        of = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if of.shape[0] != n:
+            raise ValueError(f"push_records: {of.shape[0]} offsets for {n} records")
+    arrays = (kd, ko, vd, vo, of)
+    ptr = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+    return (ptr(kd), ptr(ko), ptr(vd), ptr(vo), ptr(of) if of is not None and n else None, n), arrays
+
+
 class DeviceDecoder:
     """``surge_device_decoder``: records sections (host bytes) -> device-resident ``(agg_idx, events, offsets)`` and a
     device key table.  ``template=None``: record values are 16-byte events; otherwise the model's ``EventJsonTemplate``.
@@ -193,21 +230,23 @@ class DeviceDecoder:
     def pending(self) -> int:
         return int(self._lib.surge_device_decoder_pending(self._h))
 
-    def push_records(self, keys: List[bytes], values: List[bytes], offsets=None) -> None:
-        """Records that are already framed (a consumer's key / value byte arrays), in bulk."""
-        def table(items):
-            off = np.zeros(len(items) + 1, dtype=np.int64)
-            if items:
-                np.cumsum([len(x) for x in items], out=off[1:])
-            data = np.frombuffer(b"".join(items), dtype=np.uint8) if off[-1] else np.zeros(1, np.uint8)
-            return data, off
+    def push_records(self, keys, values, offsets=None) -> None:
+        """Records that are already framed (a consumer's key / value byte arrays), in bulk: ``keys`` and ``values`` are lists
+        of ``bytes``, or each a pair of arrays ``(data_uint8, off_int64)`` — record ``i`` is ``data[off[i]:off[i + 1]]`` —
+        which go to the library as they are (no Python loop over the records); ``offsets``: the records' Kafka offsets
+        (``None``: 0, 1, 2 ..)."""
+        args = records_arguments(keys, values, offsets)
+        self._check(self._lib.surge_device_decoder_push_records(self._h, *args[0]))
 
-        kd, ko = table(keys)
-        vd, vo = table(values)
-        of = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
-        self._check(self._lib.surge_device_decoder_push_records(
-            self._h, kd.ctypes.data_as(ctypes.c_void_p), ko.ctypes.data_as(ctypes.c_void_p), vd.ctypes.data_as(ctypes.c_void_p),
-            vo.ctypes.data_as(ctypes.c_void_p), of.ctypes.data_as(ctypes.c_void_p) if of is not None else None, len(keys)))
+    def push_records_async(self, keys, values, offsets=None) -> None:
+        """Stage 1 of ``push_records`` — the copy and the record stage — enqueued on a stream of its own
+        (``surge_device_decoder_push_records_async``); ``finish()`` completes the oldest push, wire or records, up to five may
+        be in flight.  The arrays are copied inside the call: the caller may reuse them as soon as it returns (a wire push's
+        arena must stay until its ``finish()``).  No record at all takes no slot, and there is nothing to finish."""
+        args = records_arguments(keys, values, offsets)
+        self._check(self._lib.surge_device_decoder_push_records_async(self._h, *args[0]))
+        if args[0][-1]:
+            self._inflight.append(())  # (finish() pops one entry per push; this one keeps nothing alive)
 
     def push_from(self, ingest) -> int:
         """Everything ``ingest`` (an ``EventsTopicIngest`` created with ``frames=True``) can deliver now; returns the number of batches."""

@@ -12,7 +12,7 @@ import numpy as np
 from . import _native
 from .core import SerializedMessage
 from .encode import STRING_COLUMNS, JsonTemplate, check_envelope, decode_states, key_table_utf8, merge_state_strings
-from .ingest import DeviceDecoder, EventsTopicIngest, FramedFetches, IngestError, PartitionedFramedFetches, PushPipeline, pushes_in_flight
+from .ingest import COUNTER_NAMES, DeviceDecoder, EventsTopicIngest, FramedFetches, IngestError, PartitionedFramedFetches, PushPipeline, pushes_in_flight
 from .schema import ALGO_AUTO, EVENT_DTYPE
 from .store_reads import _str_columns
 
@@ -397,6 +397,220 @@ class TopicRecoveries:
 
             counters.update(self._resumed(d.n_keys, totals, events_tail, publish=host_keys, settle=settle))
         return counters
+
+    # -- recoveries from records that are already framed: a KafkaConsumer's polls (keys, values, offsets) -------------------------
+    def restore_from_consumer_records(self, polls, capacity: int = 0, depth: int = 4, bound_log: bool = False, host_keys: bool = True,
+                                      keep_strings: bool = False, algo: int = ALGO_AUTO) -> dict:
+        """``restore_from_fetches`` for a consumer that is handed RECORDS, not fetch bytes — what Kafka Streams' restore callback and
+        every JVM ``KafkaConsumer`` receive (``SurgeStateStoreConsumer.scala:57-76``, in polls of ``restore-consumer-max-poll-records``).
+        ``polls`` yields ``(keys, values, offsets)`` per poll, in offset order per partition: ``keys`` and ``values`` are lists of
+        ``bytes`` or ``(data_uint8, off_int64)`` array pairs (``DeviceDecoder.push_records``), ``offsets`` the records' offsets or
+        ``None``; transactions are resolved already (a consumer hands over committed records only).  Per poll: stage 1 enqueued
+        (``push_records_async``: the arrays are copied inside the call, a generator may reuse them), up to ``depth`` (1 .. 5) polls in
+        flight; the oldest is finished without the closing wait and folded onto the resident state without a host wait (or, with
+        ``bound_log``, staged for the one fold at the end) — the loop ``restore_from_fetches`` runs behind its framer.  The values
+        are 16-byte fixed events, or JSON read through the model's ``event_json_template`` (a model without one is refused by
+        name).  ``capacity``, ``bound_log`` / ``algo``, ``host_keys`` and ``keep_strings`` as in ``restore_from_fetches``.  Returns the
+        same counters: there is no framer, so ``batches`` counts the polls that carried a record, ``records_decoded`` their
+        records, and what a framer alone knows is 0.  Polls of flush records only that come before the first deliverable record —
+        before the values have said which decoder the topic gets — are not pushed; they are counted (``records_decoded``,
+        ``records_seen``, ``flush_records_skipped``) as if they had been."""
+        if not 1 <= depth <= 5:
+            raise ValueError("depth must be 1 .. 5 (the decoder has five push slots)")
+        strings = _event_strings_of(self.model) if keep_strings else None
+        with contextlib.ExitStack() as closing:
+            def new_decoder(template):
+                if strings is not None and template is None:
+                    raise ValueError("keep_strings: the topic's values are 16-byte fixed events, which carry no strings")
+                self._drop_decoder()  # (not sooner: until the first record says what the values are nothing of the store has changed)
+                return closing.enter_context(DeviceDecoder(template, device=self.engine.device, event_strings=strings))
+
+            counters, n_agg, d, lead = self._fold_polls(polls, new_decoder, -1, capacity=capacity, depth=depth, bound_log=bound_log)
+            if d is None:
+                self._drop_decoder()
+            self.read_template, self.read_envelope = None, "none"
+            if bound_log and d is not None:
+                n_agg = max(n_agg, capacity, d.n_keys)
+                self.engine.pack_staged(n_agg)
+                self.engine.fold(algo)
+                self.engine.synchronize()
+            elif n_agg < 0:  # nothing deliverable in any poll
+                self._bind_all_none(capacity)
+            if d is not None:
+                counters.update(_plus_leading_flush(d.counters(), lead))
+            if strings is not None:
+                self.state_strings = None if d is None else [None if col is None else (col[0].clone(), col[1].clone()) for col in d.state_strings()]
+            self._recovery_ends(d, closing, host_keys)
+        self._restored = True
+        return counters
+
+    def _fold_polls(self, polls, decoder_for, n_agg: int, *, capacity: int = 0, depth: int = 4, bound_log: bool = False):
+        """``_fold_fetches`` without a framer: every poll pushed as records, up to ``depth`` in flight, the oldest finished and
+        folded (or staged).  ``decoder_for`` and ``n_agg`` as there.  Returns ``(counters, n_agg, the decoder or None, the flush
+        records of the polls that came before a decoder existed and were counted instead of pushed)``."""
+        template = self.model.event_json_template()
+        d = None
+        lead = 0
+        counters = dict.fromkeys(COUNTER_NAMES, 0)
+
+        def push(poll):
+            nonlocal d, lead
+            keys, values, offsets = poll
+            n = _poll_records(keys)
+            if n == 0:
+                return False
+            if d is None:
+                kind = "json" if _enveloped(template) else _poll_value_kind(keys, values)
+                if kind is None:  # flush records only, and no decoder yet to skip them: counted here
+                    lead += n
+                    counters["records_decoded"] += n
+                    return False
+                if kind == "json" and template is None:
+                    raise _NotDeviceDecodable(f"JSON event values need an event_json_template(): {type(self.model).__name__} has none")
+                d = decoder_for(template if kind == "json" else None)
+            d.push_records_async(keys, values, offsets)
+            counters["batches"] += 1
+            counters["records_decoded"] += n
+            return True
+
+        def finish_one():
+            nonlocal n_agg
+            d.finish(wait=False)
+            if bound_log:
+                _, n_keys = d.stage_into(self.engine)
+                n_agg = max(n_agg, n_keys)
+                return
+            if n_agg < 0:
+                n_agg = capacity
+                self._bind_all_none(n_agg)
+            _, n_keys = d.fold_into(self.engine, wait=False)
+            if n_keys > n_agg:
+                self.engine.n_agg = n_agg = n_keys  # (grown inside the call)
+
+        with _pushes_finished_on_the_way_out(lambda: d):
+            for _ in pushes_in_flight(polls, push, depth):
+                finish_one()
+        if d is not None:
+            self.engine.synchronize()
+        return counters, n_agg, d, lead
+
+    def restore_from_state_consumer_records(self, polls, template=None, envelope: str = "none", lenient: bool = False, host_keys: bool = True,
+                                            keep_strings: bool = False, events_polls=None, keep_event_strings: bool = False) -> dict:
+        """``restore_from_state_topic`` for a consumer that is handed the state topic's RECORDS: ``polls`` yields ``(keys, values,
+        offsets)`` as in ``restore_from_consumer_records``, the key being the aggregate id and a ``None`` or empty value its
+        tombstone.  A state-mode ``DeviceDecoder`` interns the ids (stage 1 of up to four polls in flight; a finish here includes the
+        closing wait, which the load behind it needs); every finished poll is loaded
+        (``load_states_into``: ``template``, ``envelope`` and ``lenient`` as in ``restore_from_state_records``), the loaded states
+        become the snapshot baseline.  ``events_polls``: the events behind the snapshot, as polls — the decoder then continues as
+        the events decoder of the same aggregates and the tail is folded as ``restore_from_consumer_records`` folds a topic (a
+        consumer that has sought hands over no record below its position: there are no start offsets here).
+        ``keep_strings=True`` (a ``template`` with STR parts; ``ValueError`` otherwise): the string fields the values carry stay
+        on the device beside the rows, as ``restore_from_state_topic`` keeps them; ``keep_event_strings=True`` (with
+        ``keep_strings`` and ``events_polls``; a model without the hook ``event_string_fields()`` is refused by name): the
+        tail's events replace and extend those columns.  Every refusal of an argument comes before anything of the store
+        changes — also that of a model without an ``event_json_template`` when ``events_polls`` is a list whose values are JSON.
+        Returns the counters of ``restore_from_consumer_records`` for the state polls, the summed decode counts, and the tail's
+        under ``tail_*`` names."""
+        check_envelope(envelope)
+        template = template or JsonTemplate.counter()
+        if keep_strings and not _str_columns(template):
+            raise ValueError("keep_strings: the template names no STR part whose strings could be kept")
+        tail_strings = None
+        if keep_event_strings:
+            if events_polls is None or not keep_strings:
+                raise ValueError("keep_event_strings: the tail's strings go into the columns keep_strings restores, from events_polls")
+            tail_strings = _event_strings_of(self.model)
+        event_template = self.model.event_json_template()
+        if isinstance(events_polls, (list, tuple)) and event_template is None:
+            for keys, values, _ in events_polls:
+                if _poll_value_kind(keys, values) == "json":
+                    raise _NotDeviceDecodable(f"JSON event values need an event_json_template(): {type(self.model).__name__} has none")
+        self._drop_decoder()
+        self.read_template, self.read_envelope = template, envelope
+        eng = self.engine
+        self._bind_all_none(0)  # no aggregate yet: the loads grow the state for the ids they meet
+        totals = [0, 0, 0, 0]
+        self.state_strings = None
+        counters = dict.fromkeys(COUNTER_NAMES, 0)
+        with contextlib.ExitStack() as closing:
+            d = closing.enter_context(DeviceDecoder(states=True, device=eng.device, keep_strings=keep_strings))
+
+            def push(poll):
+                keys, values, offsets = poll
+                n = _poll_records(keys)
+                if n:
+                    d.push_records_async(keys, values, offsets)
+                    counters["batches"] += 1
+                    counters["records_decoded"] += n
+                return bool(n)
+
+            def finish_one():  # the oldest poll is finished, then loaded
+                d.finish()
+                for i, c in enumerate(d.load_states_into(eng, template, envelope=envelope, lenient=lenient)):
+                    totals[i] += c
+
+            with eng.decoding_onto(self.model.event_algebra().to_c().default_state, lenient=lenient):
+                with _pushes_finished_on_the_way_out(lambda: d):
+                    for _ in pushes_in_flight(polls, push, 4):
+                        finish_one()
+            counters.update(d.counters())
+
+            def settle():
+                if events_polls is not None:
+                    def as_events_decoder(tmpl):
+                        d.continue_as_events(tmpl)
+                        if tail_strings is not None:
+                            if tmpl is None:
+                                raise ValueError("keep_event_strings: the tail's values are 16-byte fixed events, which carry no strings")
+                            d.keep_event_strings(tail_strings)
+                        return d
+
+                    state_counts = d.counters()
+                    tail, _, _, lead = self._fold_polls(events_polls, as_events_decoder, d.n_keys)
+                    after = _plus_leading_flush(d.counters(), lead)
+                    tail.update({k: after[k] - state_counts[k] for k in after})
+                    counters.update({"tail_" + k: v for k, v in tail.items()})
+                if keep_strings:  # (the decoder's buffers go with it: the columns are cloned out)
+                    self.state_strings = [None if col is None else (col[0].clone(), col[1].clone()) for col in d.state_strings()]
+                self._recovery_ends(d, closing, host_keys, publish=False)
+
+            counters.update(self._resumed(d.n_keys, totals, (), publish=host_keys, settle=settle))
+        return counters
+
+
+def _plus_leading_flush(decoder_counters: dict, lead: int) -> dict:
+    """A decoder's counters with the ``lead`` flush records ``_fold_polls`` counted instead of pushing them."""
+    return {**decoder_counters, "records_seen": decoder_counters["records_seen"] + lead, "flush_records_skipped": decoder_counters["flush_records_skipped"] + lead}
+
+
+def _poll_records(side) -> int:
+    """How many records one side of a poll holds (a list, or ``(data, off)`` arrays)."""
+    return int(side[1].shape[0]) - 1 if isinstance(side, tuple) and len(side) == 2 and isinstance(side[1], np.ndarray) else len(side)
+
+
+def _poll_value_kind(keys, values):
+    """``_sniff_value_kind`` for a poll: what its first deliverable record's value looks like — ``"fixed16"``, ``"json"``, or ``None``
+    when it holds flush records only (or nothing)."""
+    def spans(side):
+        if isinstance(side, tuple) and len(side) == 2 and isinstance(side[1], np.ndarray):
+            return np.asarray(side[0], dtype=np.uint8).reshape(-1), np.asarray(side[1], dtype=np.int64)
+        return None, None
+
+    (kd, ko), (vd, vo) = spans(keys), spans(values)
+    n = min(_poll_records(keys), _poll_records(values))
+    if ko is not None and vo is not None and n:  # the first record that is not a flush record, without a Python loop
+        live = np.flatnonzero((np.diff(ko[: n + 1]) > 0) | (np.diff(vo[: n + 1]) > 0))
+        if not live.shape[0]:
+            return None
+        first = int(live[0])
+        value = vd[vo[first]:vo[first + 1]].tobytes()
+        return "fixed16" if len(value) == 16 and value[:1] != b"{" else "json"
+    for i in range(n):
+        key = bytes(kd[ko[i]:ko[i + 1]]) if ko is not None else (keys[i] or b"")
+        value = bytes(vd[vo[i]:vo[i + 1]]) if vo is not None else (values[i] or b"")
+        if key or value:
+            return "fixed16" if len(value) == 16 and value[:1] != b"{" else "json"
+    return None
 
 
 def _framer(fetches, n_partitions: int, framing_threads: int, depth: int, overlap: bool, device_crc: bool, in_place: bool, start_offsets=None):
