@@ -543,7 +543,8 @@ int32_t surge_device_decoder_event_strings_pending(surge_device_decoder* d, int6
  * already up to date with nothing pending): out[0] = out[1] = 0, NULL.  For tests. */
 int32_t surge_device_decoder_event_strings_next_column(surge_device_decoder* d, int32_t column, int64_t out[3], uint8_t** d_utf8, int64_t** d_off);
 /* The key table (aggregate ids in first-delivered order): to the host (NULL / NULL = size query), or where it lives on
- * the device (n_keys + 1 offsets; what the GPU state encoders and K4 take). */
+ * the device (n_keys + 1 offsets; what the GPU state encoders and the UTF-8 shard map,
+ * surge_replay_partition_hash_utf8_device, take — K4 itself hashes UTF-16 code units and does not). */
 int32_t surge_device_decoder_keys(surge_device_decoder* d, uint8_t* utf8_out, int64_t utf8_capacity, int64_t* key_off_out, int64_t* n_keys_out,
                                   int64_t* utf8_bytes_out);
 int32_t surge_device_decoder_key_table(surge_device_decoder* d, const uint8_t** d_utf8, const int64_t** d_key_off);

@@ -731,6 +731,27 @@ int32_t surge_replay_partition_hash_device(surge_replay_handle* h, const uint16_
 int32_t surge_replay_partition_hash_up_to_colon_device(surge_replay_handle* h, const uint16_t* d_utf16,
                                                        const int64_t* d_str_off, int64_t n,
                                                        int32_t n_partitions, int32_t* d_part_out);
+/* The same shard map straight from UTF-8: string i is utf8[str_off[i] .. str_off[i+1]), hashed as the string the JVM sees
+ * after new String(bytes, UTF_8) — the bytes are transcoded to UTF-16 code units on the fly (a code point from 0x10000 on
+ * is its surrogate pair) and the units hashed as above; no UTF-16 table is built.  up_to_colon != 0: the hashed span ends
+ * in front of the first byte ':' (PartitionStringUpToColon.partitionBy); the bytes behind it are neither hashed nor
+ * validated.  str_off[0] need not be 0: rows [first, n_keys) of a key table are hashed by passing key_off + first and
+ * n_keys - first (surge_device_decoder_key_table is what the device form takes).
+ * Only well-formed UTF-8 is hashed (the Unicode table of well-formed byte sequences, what a strict decoder accepts).  An id
+ * with anything else in its hashed span — a lone continuation byte, an over-long form, an encoded surrogate, a value above
+ * U+10FFFF, F5..FF, a sequence cut by the span's end — is MALFORMED: its partition is -1 (the JVM would substitute U+FFFD;
+ * that is not reproduced).  Every other id still gets its partition, and the call returns SURGE_E_CORRUPT with
+ * *first_bad_out (nullable) the lowest malformed index (-1 when the call returns SURGE_OK); last_error of the device form
+ * says how many there were.  No byte at or beyond an id's end is read for that id, and nothing outside
+ * utf8[str_off[0] .. str_off[n]) at all: neither form needs slack behind the last id.
+ * n == 0: SURGE_OK, nothing is read.  SURGE_E_INVALID, with nothing written: n < 0, n_partitions <= 0, a NULL str_off or
+ * part_out; host form: offsets that are not monotone, a NULL utf8 unless every id is empty; device form: a NULL handle or
+ * d_utf8 (an id whose offsets are not monotone is malformed there, and nothing of it is read).
+ * The device form is enqueued on the handle's stream and returns when d_part_out is complete (it reports the count). */
+int32_t surge_replay_partition_hash_utf8(const uint8_t* utf8, const int64_t* str_off, int64_t n, int32_t n_partitions,
+                                         int32_t up_to_colon, int32_t* part_out, int64_t* first_bad_out);
+int32_t surge_replay_partition_hash_utf8_device(surge_replay_handle* h, const uint8_t* d_utf8, const int64_t* d_str_off, int64_t n,
+                                                int32_t n_partitions, int32_t up_to_colon, int32_t* d_part_out, int64_t* first_bad_out);
 
 /* Wire form of a snapshot for the xGMI exchange: only the first 40 bytes of a state carry information (the
  * 24-byte reserved tail is always zero), so shards travel packed (n x 40 B) and are expanded back to the

@@ -93,7 +93,9 @@ REPLAY_H = {
     "surge_replay_partition_hash_device": ([_vp, _vp, _vp, _i64, _i32, _vp], _i32),
     "surge_replay_partition_hash_up_to_colon": ([_vp, _vp, _i64, _i32, _vp], _i32),
     "surge_replay_partition_hash_up_to_colon_device": ([_vp, _vp, _vp, _i64, _i32, _vp], _i32),
-    "surge_replay_set_state_out": ([_vp, _vp], _i32),
+    "surge_replay_partition_hash_utf8": ([_vp, _vp, _i64, _i32, _i32, _vp, ctypes.POINTER(_i64)], _i32),
+    "surge_replay_partition_hash_utf8_device": ([_vp, _vp, _vp, _i64, _i32, _i32, _vp, ctypes.POINTER(_i64)], _i32),
+    "surge_replay_set_state_out":([_vp, _vp], _i32),
     "surge_replay_grow": ([_vp, _i64], _i32),
     "surge_replay_comm_unique_id": ([_vp], _i32),
     "surge_replay_comm_init": ([_vp, _i32, _i32, _vp], _i32),

@@ -163,6 +163,7 @@ struct surge_replay_handle {
   alignas(16) uint8_t decode_base[64] = {};       // surge_replay_set_decode_base: what a decoded row's unnamed bytes hold
   int32_t decode_mode = SURGE_STATE_READ_STRICT;  // surge_replay_set_decode_mode
   DevBuf sd_ptab, sd_counts, sd_last, sd_status;  // surge_replay_decode_json_states: parse table, counters, last record per aggregate, statuses
+  DevBuf shard_counts;  // surge_replay_partition_hash_utf8_device: {malformed ids, the lowest of them}
 
   surge::CommState* comm = nullptr;  // the snapshot exchange (comm.hip), created by surge_replay_comm_init
   DevBuf gathered[2];         // handle-owned output of allgather_snapshot(d_out = NULL), per slot

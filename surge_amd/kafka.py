@@ -4,8 +4,8 @@
 ``modules/common/src/main/scala/surge/kafka/KafkaPartitioner.scala:8``; the default partitioner cuts
 the key at the first ``':'`` (``PartitionStringUpToColon``, :38-42) so events keyed
 ``"<id>:<seq>"`` land with their aggregate.  The hash itself is computed by the C ABI
-(``surge_replay_partition_hash[_up_to_colon]``: CPU; ``..._device``: GPU kernel K4); the cut belongs to the
-partitioner's ``partitionBy``, not to ``partitionForKey``.
+(``surge_replay_partition_hash[_up_to_colon]``: CPU; ``..._device``: GPU kernel K4; ``surge_replay_partition_hash_utf8[_device]``:
+the same from UTF-8 bytes, no UTF-16 table); the cut belongs to the partitioner's ``partitionBy``, not to ``partitionForKey``.
 """
 from __future__ import annotations
 
@@ -47,6 +47,30 @@ def partition_for_keys(keys: Sequence[str], n_partitions: int, up_to_colon: bool
     )
     if rc != 0:
         raise RuntimeError(f"surge_replay_partition_hash failed: {rc}")
+    return out
+
+
+def partition_for_utf8(data, off, n_partitions: int, up_to_colon: bool = False) -> np.ndarray:
+    """Batch ``partitionForKey`` of ids given as UTF-8 (``surge_replay_partition_hash_utf8``, the CPU form): id ``i`` is
+    ``data[off[i]:off[i + 1]]`` (``data``: ``bytes`` or a ``uint8`` array; ``off``: ``n + 1`` offsets, ``off[0]`` need not be 0) —
+    what ``partition_for_keys`` gives for the decoded strings, without a string or a UTF-16 table being built.  An id whose
+    hashed span is not well-formed UTF-8 gets ``-1`` (the JVM would substitute U+FFFD; that is not reproduced): the caller
+    decides what a ``-1`` means to it."""
+    if n_partitions <= 0:
+        raise ValueError("numberOfPartitions must be positive")
+    data = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    n = off.shape[0] - 1
+    out = np.zeros(max(n, 0), dtype=np.int32)
+    if n <= 0:
+        return out
+    if (np.diff(off) < 0).any() or off[0] < 0 or off[-1] > data.size:
+        raise ValueError("the offsets are not monotone or leave the data")
+    rc = _native.load().surge_replay_partition_hash_utf8(
+        data.ctypes.data_as(ctypes.c_void_p) if data.size else None, off.ctypes.data_as(ctypes.c_void_p), n, n_partitions, 1 if up_to_colon else 0,
+        out.ctypes.data_as(ctypes.c_void_p), None)
+    if rc not in (0, -7):  # -7 (CORRUPT): some ids are malformed; theirs are the -1s
+        raise RuntimeError(f"surge_replay_partition_hash_utf8 failed: {rc}")
     return out
 
 

@@ -497,3 +497,25 @@ class ReplayEngine:
         n = d_str_off.numel() - 1
         fn = self._lib.surge_replay_partition_hash_up_to_colon_device if up_to_colon else self._lib.surge_replay_partition_hash_device
         self._check(fn(self._h, _dev_ptr(d_utf16), _dev_ptr(d_str_off), n, n_partitions, _dev_ptr(d_out)))
+
+    def partition_hash_utf8_device(self, d_utf8, d_str_off, n_partitions: int, d_out, up_to_colon: bool = False) -> None:
+        """The shard map straight from UTF-8 ids in device memory (``surge_replay_partition_hash_utf8_device``): id ``i`` is
+        ``d_utf8[d_str_off[i]:d_str_off[i + 1]]`` — ``d_str_off`` may be a slice of a key table's offsets that does not start at 0
+        (``d_key_off[first:]`` hashes the rows from ``first`` on), ``d_utf8`` is the table's first byte either way — and ``d_out`` an
+        ``int32`` CUDA tensor of as many entries.  Enqueued on the engine's stream; returns when ``d_out`` is complete.  An id that is
+        not well-formed UTF-8 gets ``-1`` and every other id its partition; then ``ReplayError`` (CORRUPT) is raised, the lowest
+        such index its ``first_bad``."""
+        n = int(d_str_off.numel()) - 1
+        if int(d_out.numel()) < n:
+            raise ValueError("d_out is shorter than the ids")
+        if n > 0 and int(d_utf8.numel()) == 0:  # every id is empty: the library still wants an address
+            d_utf8 = d_str_off.new_zeros(16, dtype=d_utf8.dtype)
+        first_bad = ctypes.c_int64(-1)
+        rc = self._lib.surge_replay_partition_hash_utf8_device(self._h, _dev_ptr(d_utf8), _dev_ptr(d_str_off), n, n_partitions, 1 if up_to_colon else 0,
+                                                               _dev_ptr(d_out), ctypes.byref(first_bad))
+        if rc == -7:
+            msg = self._lib.surge_replay_last_error(self._h)
+            err = ReplayError(rc, msg.decode() if msg else "")
+            err.first_bad = int(first_bad.value)
+            raise err
+        self._check(rc)

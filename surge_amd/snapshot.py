@@ -15,6 +15,7 @@ last-record-per-key rule, which is also what the KTable applies on restore
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import time
 from dataclasses import dataclass, field
@@ -220,7 +221,8 @@ class BulkSnapshotPublisher:
 
         delta kernel (what changed since the last publish: PersistentActor.scala:212,257)
           -> GPU encoder restricted to the changed Some aggregates (writeState text; N3)
-          -> K4 partitions of the aggregate ids (once per key table)
+          -> K4 partitions of the aggregate ids (once per key table; a publisher that follows a decoder's key table: the
+             UTF-8 shard map over the rows that are new, before every publish)
           -> uncompressed batches: DeviceFramer (records + headers written on the GPU, one D2H, CRC-32C on the host)
              lz4 batches, ``device_compression=True``: the same, every batch's records compressed on the GPU first
              lz4 batches otherwise: one D2H of {kinds, text, offsets} -> RecordBatch v2 encoder (C++; N2)
@@ -230,9 +232,17 @@ class BulkSnapshotPublisher:
 
     def __init__(self, engine, keys: Optional[Sequence[str]], n_partitions: int, template=None, device=None, tables=None,
                  compression: str = "none", device_framing: bool = True, device_compression: bool = False, strings=(),
-                 envelope: str = "none"):
+                 envelope: str = "none", decoder=None):
         """``keys``: aggregate ids in dense-index order; or ``tables = (keys_utf8, key_off, keys_utf16, off16)`` as
-        tensors / arrays built without Python strings (large synthetic populations).  ``compression``: "none" or "lz4"
+        tensors / arrays built without Python strings (large synthetic populations); or ``keys=None, decoder=d``: the
+        publisher FOLLOWS the key table of that ``DeviceDecoder`` where it lives — before every publish it re-reads
+        ``d.device_key_table()`` (the tensors move when a push interns an id) and partitions the rows it has not partitioned
+        yet, from their UTF-8 bytes on the device (``ReplayEngine.partition_hash_utf8_device``): no id becomes a Python string,
+        no UTF-16 table is built, and a store that keeps interning ids needs no new publisher.  The decoder's stream has to be
+        ordered with the engine's and every push finished, as for ``encode.encode_rows`` over that table; an id that is not
+        well-formed UTF-8 makes ``publish`` raise ``ReplayError`` (CORRUPT) before anything is framed.  The arms that frame on
+        the host (lz4 without ``device_compression``, or ``device_framing=False``) download the table's bytes as arrays, again
+        when it has grown.  ``compression``: "none" or "lz4"
         (the reference producer's ``compression.type``).  ``device_compression``: lz4 batches are framed AND compressed
         by the ``DeviceFramer`` (needs ``device_framing``); without it they go through the host writer and its compressor.
         ``strings``: the side string columns of a template with ``(JP_STR, column)`` parts, as ``encode_states`` takes them
@@ -250,27 +260,38 @@ class BulkSnapshotPublisher:
         self.template = template or JsonTemplate.counter()
         self.strings = strings
         self.device = torch.device(device or f"cuda:{engine.device}")
-        self.writer = RecordBatchWriter(n_partitions, compression=compression)
-        if tables is None:
-            data, off = key_table_utf8(keys)
-            u16, o16 = utf16_table(keys)
-            u16 = u16.view(np.int16)
-        else:
-            data, off, u16, o16 = tables
-        as_t = lambda a: a.to(self.device) if hasattr(a, "to") else torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
-        self.d_keys, self.d_key_off = as_t(data), as_t(off)
-        self.h_keys, self.h_key_off = self.d_keys.cpu().numpy(), self.d_key_off.cpu().numpy()
-        n_keys = int(self.d_key_off.numel()) - 1
-        d_part = torch.zeros(n_keys, dtype=torch.int32, device=self.device)
-        if n_keys:
-            torch.cuda.current_stream(self.device).synchronize()
-            engine.partition_hash_device(as_t(u16), as_t(o16), n_partitions, d_part, up_to_colon=True)
-            engine.synchronize()
-        self.partitions = d_part.cpu().numpy()
-        self.d_part = d_part
         # uncompressed batches are framed on the device (DeviceFramer: byte-identical to the host writer); lz4 batches
         # go through the host writer and its compressor unless the device's compressor was asked for
         on_device = device_framing and (compression == "none" or device_compression)
+        self.decoder = decoder
+        if decoder is not None and (keys is not None or tables is not None):
+            raise ValueError("a publisher that follows a decoder's key table takes neither keys nor tables")
+        self.writer = RecordBatchWriter(n_partitions, compression=compression)
+        if decoder is not None:
+            # nothing is read here: the first publish finds every row new (_follow)
+            self.d_keys = self.d_key_off = self.h_keys = self.h_key_off = None
+            self._part_buf = torch.zeros(0, dtype=torch.int32, device=self.device)  # d_part is its first _hashed entries
+            self.d_part, self._hashed = self._part_buf, 0
+            self.partitions = np.zeros(0, dtype=np.int32)  # on the host only where the host frames
+            self._host_tables = not on_device
+        else:
+            if tables is None:
+                data, off = key_table_utf8(keys)
+                u16, o16 = utf16_table(keys)
+                u16 = u16.view(np.int16)
+            else:
+                data, off, u16, o16 = tables
+            as_t = lambda a: a.to(self.device) if hasattr(a, "to") else torch.from_numpy(np.ascontiguousarray(a)).to(self.device)  # noqa: E731
+            self.d_keys, self.d_key_off = as_t(data), as_t(off)
+            self.h_keys, self.h_key_off = self.d_keys.cpu().numpy(), self.d_key_off.cpu().numpy()
+            n_keys = int(self.d_key_off.numel()) - 1
+            d_part = torch.zeros(n_keys, dtype=torch.int32, device=self.device)
+            if n_keys:
+                torch.cuda.current_stream(self.device).synchronize()
+                engine.partition_hash_device(as_t(u16), as_t(o16), n_partitions, d_part, up_to_colon=True)
+                engine.synchronize()
+            self.partitions = d_part.cpu().numpy()
+            self.d_part = d_part
         self.framer = DeviceFramer(n_partitions, device=self.device.index or 0, compression=compression) if on_device else None
         self.timings: Dict[str, float] = {}
 
@@ -278,6 +299,44 @@ class BulkSnapshotPublisher:
         self.writer.close()
         if self.framer is not None:
             self.framer.close()
+
+    def _follow(self) -> int:
+        """How many ids the publisher has partitions for.  A publisher that follows a decoder catches up with its key table
+        first: the table's tensors are read again, the rows behind the last one partitioned are hashed from their UTF-8
+        bytes on the device (the offsets' slice from that row on: no row is hashed twice) and, where the host frames, the
+        table's bytes and the partitions are downloaded again.  A malformed id raises before anything else has moved; the
+        rows stay unpartitioned."""
+        d = self.decoder
+        if d is None:
+            return len(self.partitions)
+        import torch
+
+        from .replay import ReplayError
+
+        d_keys, d_key_off = d.device_key_table()
+        n_keys = int(d_key_off.numel()) - 1
+        first, grown = self._hashed, n_keys > self._hashed
+        if grown:
+            if n_keys > int(self._part_buf.numel()):
+                buf = torch.zeros(max(n_keys, 2 * int(self._part_buf.numel())), dtype=torch.int32, device=self.device)
+                buf[:first] = self._part_buf[:first]
+                self._part_buf = buf
+            torch.cuda.current_stream(self.device).synchronize()  # (the buffer was filled on torch's stream, the hash runs on the engine's)
+            try:
+                self.engine.partition_hash_utf8_device(d_keys, d_key_off[first:], self.n_partitions, self._part_buf[first:n_keys], up_to_colon=True)
+            except ReplayError as e:
+                if e.status != -7:
+                    raise
+                row = first + e.first_bad
+                lo, hi = (int(v) for v in d_key_off[row:row + 2].tolist())
+                raw = d_keys[lo:hi].cpu().numpy().tobytes()
+                raise ReplayError(-7, f"row {row} of the key table is not well-formed UTF-8 and has no partition: {raw!r} ({e})") from e
+            self._hashed = n_keys
+        self.d_keys, self.d_key_off, self.d_part = d_keys, d_key_off, self._part_buf[:n_keys]
+        if self._host_tables and (grown or self.h_keys is None):
+            self.h_keys, self.h_key_off = d_keys.cpu().numpy(), d_key_off.cpu().numpy()
+            self.partitions = self.d_part.cpu().numpy()
+        return n_keys
 
     def publish(self, commit: bool = True, timestamp_ms: Optional[int] = None) -> Dict[int, bytes]:
         """Record batches (per partition) for everything that changed since the last committed publish.
@@ -292,7 +351,7 @@ class BulkSnapshotPublisher:
 
         eng = self.engine
         n = eng.n_agg
-        if n > len(self.partitions):
+        if n > self._follow():  # (a following publisher has caught up with its key table by now)
             raise ValueError("the resident state has aggregates the publisher has no key for: rebuild it with the current key table")
         lib = _native.load()
         t0 = time.perf_counter()
@@ -366,7 +425,7 @@ class BulkSnapshotPublisher:
             return pending
         eng = self.engine
         n = eng.n_agg
-        if n > len(self.partitions):
+        if n > self._follow():  # (a following publisher has caught up with its key table by now)
             raise ValueError("the resident state has aggregates the publisher has no key for: rebuild it with the current key table")
         lib = _native.load()
         t0 = time.perf_counter()
@@ -446,6 +505,44 @@ class PendingPublish:
         if self._exc is not None:
             raise self._exc
         return self._out
+
+
+class StoreSnapshotPublisher(BulkSnapshotPublisher):
+    """What ``GpuReplayStateStore.snapshot_publisher`` gives on the device route: a publisher that follows the store's decoder.
+    Every publish takes the store's ``_device_lock`` and first checks that the store still holds that decoder — a store that
+    has left the route since (``store.keys`` was touched) or was restored again has closed it, and it is never touched then.
+    ``strings`` left out: the store's ``state_string_columns()``, read again before every publish."""
+
+    def __init__(self, store: GpuReplayStateStore, n_partitions: int, **kw):
+        with store._device_lock:
+            d = store._decoder
+            if d is None:
+                raise RuntimeError("the store is not on the device route: publish from its host key table (store.keys.keys)")
+            self.store = store
+            self._store_strings = "strings" not in kw
+            kw.setdefault("template", store.read_template)
+            kw.setdefault("envelope", store.read_envelope)
+            if self._store_strings:
+                kw["strings"] = store.state_string_columns()
+            super().__init__(store.engine, None, n_partitions, decoder=d, **kw)
+
+    @contextlib.contextmanager
+    def _on_route(self):
+        with self.store._device_lock:
+            if self.store._decoder is not self.decoder:
+                raise RuntimeError("the store has left the device route, or was restored again, since this publisher was made: its decoder is "
+                                   "closed — ask the store for a new publisher (snapshot_publisher)")
+            if self._store_strings:
+                self.strings = self.store.state_string_columns()
+            yield
+
+    def publish(self, commit: bool = True, timestamp_ms: Optional[int] = None):
+        with self._on_route():
+            return super().publish(commit, timestamp_ms)
+
+    def publish_async(self, timestamp_ms: Optional[int] = None) -> "PendingPublish":
+        with self._on_route():
+            return super().publish_async(timestamp_ms)
 
 
 def compact(records: Iterable[StateRecord]) -> Dict[str, Optional[bytes]]:

@@ -116,6 +116,21 @@ class GpuReplayStateStore(TopicRecoveries, StoreReads):
         self._uploaded_keys = None
         self._sorted_keys = None
 
+    def snapshot_publisher(self, n_partitions: int, **kw):
+        """The ``snapshot.BulkSnapshotPublisher`` of this store's state topic (``kw``: its keyword arguments).  On the host route
+        that is what callers write themselves — ``BulkSnapshotPublisher(store.engine, store.keys.keys, n_partitions, **kw)``.  On
+        the device route the publisher follows the decoder's key table instead (``snapshot.StoreSnapshotPublisher``): the ids are
+        partitioned from their UTF-8 bytes on the GPU, none is downloaded, and the store STAYS on the device route however
+        often it publishes; ``template`` / ``envelope`` / ``strings`` default to ``read_template`` / ``read_envelope`` /
+        ``state_string_columns()``.  Such a publisher belongs to the recovery it was made after: once the store has left the
+        route or been restored again, its ``publish`` raises ``RuntimeError`` — ask for a new one."""
+        from .snapshot import BulkSnapshotPublisher, StoreSnapshotPublisher
+
+        with self._device_lock:
+            if self._decoder is not None:
+                return StoreSnapshotPublisher(self, n_partitions, **kw)
+        return BulkSnapshotPublisher(self.engine, self.keys.keys, n_partitions, **kw)
+
     # -- recovery through the host key table ---------------------------------------------------------------
     def restore(self, events_in_offset_order: Sequence, prior: Optional[Dict[str, object]] = None,
                 capacity: int = 0, algo: int = ALGO_AUTO) -> None:
